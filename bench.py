@@ -1,6 +1,7 @@
 """Benchmark: 10-stage GGTV-GGLR image filter on sigma=25 noisy 256x256 RGB patches.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR]
+    python bench.py --full [--no-cpu-baseline] [--no-secondary] [--breakdown] ...
 
 One "step" = one forward of the image-domain GGTV-GGLR filter (MultiScaleGraphFilter,
 G=32 graphs x F=3, C=96, S=10 unrolled stages, v13 feature CNN; SURVEY.md §8(d) "P")
@@ -10,9 +11,14 @@ N>1: one process per GPU (under torchrun, or spawned by this script when started
 by patch — no data-path collective; scaling "weak"); the timed region is bracketed by
 barrier + synchronize on both sides and the max over ranks is reported.
 
-Rank 0 prints ONE JSON line with the metric, the roofline of the dominant solver kernel
-(grr_system_step2: two CG stages per launch; timed live with HIP events on its launch
-stream) and the CPU baseline (the oracle, timed on this host's cores on a bounded sample).
+A plain run sets up, warms up, times the K steps and rank 0 prints ONE JSON line with the
+metric (value, ms_per_step).  --dump-outputs DIR also writes what the last timed step returned
+(DIR/denoised.npy; the inputs are seeded, so two builds compare output for output).
+
+--full adds to that line everything that takes runs of its own: the roofline of the dominant
+solver kernel (grr_system_step2: two CG stages per launch; timed live with HIP events on its
+launch stream) and the per-kernel times, the streaming-copy ceiling, the secondary workload and
+the CPU baseline with PSNR parity (the oracle, timed on this host's cores on a bounded sample).
 """
 from __future__ import annotations
 
@@ -220,13 +226,23 @@ def main():
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=64, help="patches per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/denoised.npy (float32; per rank "
+                         "denoised_rank<r>.npy when N > 1; a seeded sample of patches above 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also: per-kernel times and rooflines (an instrumented loop of its own), the streaming-copy "
+                         "ceiling, the secondary workload, the CPU baseline and PSNR parity")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and PSNR")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary workload (v1.0 AbtractMultiScaleGraphFilter, SURVEY.md §8d 'D')")
-    ap.add_argument("--breakdown", action="store_true", help="print the per-kernel table to stderr")
+                    help="with --full: skip the secondary workload (v1.0 AbtractMultiScaleGraphFilter, "
+                         "SURVEY.md §8d 'D')")
+    ap.add_argument("--breakdown", action="store_true",
+                    help="with --full: print the per-kernel table to stderr")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher check: every rank prints its rank / world and exits (no HIP)")
     args = ap.parse_args()
+    if args.breakdown and not args.full:
+        ap.error("--breakdown prints the instrumented loop's table: it needs --full")
 
     # --gpus N: one process per GPU.  Under torchrun the ranks exist already (WORLD_SIZE must
     # equal N); started plainly, this process spawns the N ranks and exits with their status
@@ -239,7 +255,6 @@ def main():
     ranks = benchlib.check_ranks(world, dev)     # every rank in the group, over the data backend
 
     import irdu_amd
-    from irdu_amd import kernels as K
     irdu_amd.load_native()
     model = build_model(dev, trained=os.path.exists(TRAINED))
     b = args.batch
@@ -260,22 +275,10 @@ def main():
             out = model(noisy)
         barrier()
         dt = time.perf_counter() - t0
-        # then the same steps again with HIP events around every launch (per-kernel breakdown and
-        # the roofline's kernel time); this loop's wall time is not the headline.  It runs on one
-        # stream (no feature side stream), so each kernel's time is its own and not shared with a
-        # concurrent kernel
-        from irdu_amd import graph_filter as GF
-        saved = GF.FEATURE_STREAMS
-        GF.FEATURE_STREAMS = False
-        timer = K.LaunchTimer()
-        timer.split_lnb = True      # the feature CNN's head and mix kernels timed apart
-        K.set_timer(timer)
-        for _ in range(max(1, min(args.steps, 5))):
-            out = model(noisy)
-        K.set_timer(None)
-        GF.FEATURE_STREAMS = saved
-        n_inst = max(1, min(args.steps, 5))
-    kern = timer.summary()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, world, rank)
+    if args.full:
+        kern, n_inst = instrumented_loop(model, noisy, args.steps)
     rank_dts = [r[0] for r in benchlib.gather_floats([dt], world, dev)]
     dt = benchlib.max_over_ranks(dt, world, dev)
     if rank != 0:
@@ -284,6 +287,65 @@ def main():
 
     px_total = world * b * H * W * args.steps
     value = px_total / dt / 1e6
+    res = {"metric": METRIC, "value": round(value, 3), "unit": "MPix/s", "n_gpus": world, "steps": args.steps,
+           "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True,
+           "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+           "config": {"workload": "MultiScaleGraphFilter (image-domain GGTV-GGLR, v13 feature CNN) "
+                                  f"G={G} F={CIN} C={G * CIN}, S={STAGES} stages, {H}x{W} RGB sigma=25, "
+                                  + ("weights: trained fixture" if os.path.exists(TRAINED) else
+                                     "reference-init weights, output 1x1 = per-colour graph mean"),
+                      "global_batch": world * b, "per_gpu_batch": b, "image": f"{H}x{W}x{CIN}",
+                      "parallelism": f"batch-sharded x{world}, no collective in the data path"}}
+    if world > 1:
+        res.update(ranks)
+        res["ranks"] = {"backend": ranks["backend"], "visible_gpus": torch.cuda.device_count(),
+                        "ms_per_step_per_rank": [round(d / args.steps * 1e3, 3) for d in rank_dts]}
+    if args.full:
+        full_report(res, args, kern, n_inst, model, dev, value, world, b)
+    print(json.dumps(res), flush=True)
+    benchlib.finish(world)
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, out, world, rank):
+    """--dump-outputs: what the last timed step returned, as float32 .npy.  Every rank writes its own
+    file; the ranks share the 64 MB budget.  An output above its share is cut to a fixed, seeded sample
+    of whole patches (sorted indices of RandomState(0).choice), the same in every run."""
+    os.makedirs(dirname, exist_ok=True)
+    a = out.detach().to(torch.float32).cpu().numpy()
+    keep = (DUMP_BUDGET_BYTES // world) // a[0].nbytes
+    if keep < a.shape[0]:
+        a = a[np.sort(np.random.RandomState(0).choice(a.shape[0], max(keep, 1), replace=False))]
+    np.save(os.path.join(dirname, "denoised.npy" if world == 1 else f"denoised_rank{rank}.npy"), a)
+
+
+def instrumented_loop(model, noisy, steps):
+    """--full: the same steps again with HIP events around every launch (per-kernel breakdown and
+    the roofline's kernel time); this loop's wall time is not the headline.  It runs on one
+    stream (no feature side stream), so each kernel's time is its own and not shared with a
+    concurrent kernel.  Returns (LaunchTimer summary, instrumented steps)."""
+    from irdu_amd import kernels as K
+    with torch.no_grad():
+        from irdu_amd import graph_filter as GF
+        saved = GF.FEATURE_STREAMS
+        GF.FEATURE_STREAMS = False
+        timer = K.LaunchTimer()
+        timer.split_lnb = True      # the feature CNN's head and mix kernels timed apart
+        K.set_timer(timer)
+        for _ in range(max(1, min(steps, 5))):
+            out = model(noisy)
+        K.set_timer(None)
+        GF.FEATURE_STREAMS = saved
+        n_inst = max(1, min(steps, 5))
+    return timer.summary(), n_inst
+
+
+def full_report(res, args, kern, n_inst, model, dev, value, world, b):
+    """--full, rank 0: rooflines and per-kernel times of the instrumented loop, the streaming-copy
+    ceiling, the secondary workload and the CPU baseline with PSNR parity, added to the result line."""
+    from irdu_amd import kernels as K
     # the dominant solver kernel: the two-stage launch where the filter uses it
     kind, kname = ("system_step2", STEP2_KERNEL) if "system_step2" in kern else ("system_step", STEP_KERNEL)
     step = kern[kind]
@@ -312,20 +374,7 @@ def main():
     del src, dst
     roofline["copy_gbps"] = round(copy_gbps, 1)
     roofline["frac_of_copy"] = round(achieved / copy_gbps, 4)
-    res = {"metric": METRIC, "value": round(value, 3), "unit": "MPix/s", "n_gpus": world, "steps": args.steps,
-           "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True,
-           "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-           "config": {"workload": "MultiScaleGraphFilter (image-domain GGTV-GGLR, v13 feature CNN) "
-                                  f"G={G} F={CIN} C={G * CIN}, S={STAGES} stages, {H}x{W} RGB sigma=25, "
-                                  + ("weights: trained fixture" if os.path.exists(TRAINED) else
-                                     "reference-init weights, output 1x1 = per-colour graph mean"),
-                      "global_batch": world * b, "per_gpu_batch": b, "image": f"{H}x{W}x{CIN}",
-                      "parallelism": f"batch-sharded x{world}, no collective in the data path"},
-           "roofline": roofline}
-    if world > 1:
-        res.update(ranks)
-        res["ranks"] = {"backend": ranks["backend"], "visible_gpus": torch.cuda.device_count(),
-                        "ms_per_step_per_rank": [round(d / args.steps * 1e3, 3) for d in rank_dts]}
+    res["roofline"] = roofline
     if "lnb_head" in kern:   # the feature CNN: head (LN + W1 + depthwise + gate) and mix (W2 + skip) apart
         hd, mx = kern["lnb_head"], kern["lnb_mix"]
         res["roofline_secondary"] = {
@@ -415,8 +464,6 @@ def main():
                        "weights": ("tests/golden/msgf_trained_g32_s10.safetensors (trained here: no reference "
                                    "checkpoint exists)") if os.path.exists(TRAINED) else "reference init"}
         res["speedup_vs_cpu"] = round(value / world / cb["value"], 1)
-    print(json.dumps(res), flush=True)
-    benchlib.finish(world)
 
 
 if __name__ == "__main__":

@@ -3,7 +3,7 @@
 set -o pipefail
 mkdir -p gpurun_out
 for v in 1 0 1 0; do
-  GRR_STEP2=$v timeout -k 10 240 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-secondary --breakdown \
+  GRR_STEP2=$v timeout -k 10 240 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-secondary --breakdown \
     > gpurun_out/ab_step2_$v.json 2> gpurun_out/ab_step2_$v.err || exit 1
   python - "$v" <<'PY'
 import json, sys

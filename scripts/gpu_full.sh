@@ -8,6 +8,6 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -q -rf --timeout 300 --timeou
 rc=$?
 tail -12 $out/gpu_tests.log
 case $rc in 0|1) ;; *) exit $rc ;; esac
-timeout -k 10 400 python bench.py --no-cpu-baseline > $out/bench.json 2> $out/bench.err || { tail -20 $out/bench.err; exit 1; }
+timeout -k 10 400 python bench.py --full --no-cpu-baseline > $out/bench.json 2> $out/bench.err || { tail -20 $out/bench.err; exit 1; }
 tail -c 1200 $out/bench.json
 exit $rc

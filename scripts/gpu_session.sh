@@ -29,17 +29,17 @@ if [ "$MODE" = all ] || [ "$MODE" = smoke ]; then
   step smoke 300 0 python -c "import __graft_entry__ as g; g.smoke()"
 fi
 if [ "$MODE" = all ] || [ "$MODE" = bench ]; then
-  step bench 900 0 python bench.py --steps 10 --warmup 3 --breakdown
+  step bench 900 0 python bench.py --full --steps 10 --warmup 3 --breakdown
 fi
 if [ "$MODE" = prof ]; then
   step rocprof 900 0 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- \
-    python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-secondary
+    python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-secondary
 fi
 if [ "$MODE" = traffic ]; then
   step pmc_fetch 600 0 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -o run -- \
-    python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-secondary
+    python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-secondary
   step pmc_write 600 0 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write" -o run -- \
-    python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-secondary
+    python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-secondary
   python scripts/collect_traffic.py "$OUT/pmc_fetch" "$OUT/pmc_write" --out "$OUT/traffic_system_step.json"
 fi
 echo "session done"

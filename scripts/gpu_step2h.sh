@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 timeout -k 10 400 python -u -m pytest tests/test_gpu_step2.py tests/test_gpu_parity.py tests/test_gpu_streams.py -x -q \
   -rf --timeout 120 --timeout-method thread -p no:cacheprovider > $out/tests.log 2>&1
 rc=$?; tail -5 $out/tests.log; [ $rc -eq 0 ] || exit $rc
-timeout -k 10 300 python -u bench.py > $out/bench.json 2> $out/bench.err || exit $?
+timeout -k 10 300 python -u bench.py --full > $out/bench.json 2> $out/bench.err || exit $?
 python -c "
 import json; d=json.load(open('$out/bench.json'))
 print(d['value'], d['ms_per_step'], d['roofline']['frac'], d['kernel_ms_per_step'])"

@@ -7,7 +7,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"; export TMPDIR=/tmp
 OUT=gpurun_out/pmcb; mkdir -p $OUT
 B=${1:-64}
-CMD="python bench.py --steps 2 --warmup 1 --batch $B --no-cpu-baseline --no-secondary"
+CMD="python bench.py --full --steps 2 --warmup 1 --batch $B --no-cpu-baseline --no-secondary"
 RX="graph_step2|lnb_head16|lnb_mix|lnb_rep_kernel|lnb_fused16|graph_row_kernel|feat_edge_kernel"
 for ctr in FETCH_SIZE WRITE_SIZE; do
   timeout -s KILL 240 rocprofv3 --pmc $ctr --kernel-include-regex "$RX" --output-format csv -d $OUT/$ctr -o run -- \

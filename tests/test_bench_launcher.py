@@ -42,6 +42,15 @@ def test_single_gpu_dry_run_does_not_spawn():
     assert lines == [{"dry_run": True, "rank": 0, "local_rank": 0, "world": 1, "master": ":"}]
 
 
+def test_breakdown_belongs_to_full():
+    # the per-kernel table comes from the instrumented loop, which only --full runs: refused before any launch
+    r = _run("bench.py", ["--breakdown", "--dry-run"], _env())
+    assert r.returncode == 2
+    assert "--full" in r.stderr
+    r = _run("bench.py", ["--full", "--breakdown", "--dump-outputs", "unused", "--dry-run"], _env())
+    assert r.returncode == 0, r.stderr
+
+
 def test_torchrun_world_must_match_gpus():
     r = _run("bench.py", ["--gpus", "4", "--dry-run"], _env(WORLD_SIZE="2", RANK="0", LOCAL_RANK="0"))
     assert r.returncode != 0
