@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from oracle import graph_oracle as O
+from tests import term_ref
 from tests.test_gpu_parity import DEV, perturb_mixture, rand, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -97,6 +98,37 @@ def test_lowpass_block_grad(irdu, term_path, case):
         blk.skip_weight.copy_(torch.tensor([0.4, 0.9]))
     x = rand(case["b"], c, case["h"], case["w"], seed=19)
     check(blk, lambda xd, p: O.lowpass_block(xd, p, case["g"]), x)
+
+
+def _check_wide(module, x, fn, ratio):
+    """check() at the default knobs and GTOL, with the thresholds set by the gap rule (tests/term_ref.py:
+    every edge of both levels at least 1e-4 gamma from its graph's threshold, asserted there from the
+    oracle alone), and the forward error at least 10x below the smallest half-gap over max|t|: the fp32
+    prox input then cannot carry an edge across its threshold."""
+    errs = check(module, fn, x)
+    print(f"forward rel err {errs['out']:.3e}, smallest half-gap / max|t| {ratio:.3e}, "
+          f"input {errs['input']:.2e}, gamma {max(v for k, v in errs.items() if 'gamma' in k):.2e}")
+    assert 10.0 * errs["out"] <= ratio, (errs["out"], ratio)
+    return errs
+
+
+@pytest.mark.parametrize("case", term_ref.WIDE_LOWPASS, ids=lambda c: "g{g}f{f}h{h}w{w}".format(**c))
+def test_lowpass_block_grad_wide(irdu, case):
+    """LocalLowpassFilteringBlock at the widths the C4 configuration trains at (column strips, the tail
+    launch, row segments with halo rows; the half level at W / 2 on other lanes), every knob at its
+    default, every parameter at GTOL.  Measured on an MI355X, per case: forward rel err 1.19e-6 / 3.13e-7 /
+    5.11e-7 against a smallest half-gap over max|t| of 1.40e-5 / 1.11e-5 / 3.12e-5; worst gradient rel err
+    5.1e-5 (muys01) / 1.9e-5 / 2.8e-6."""
+    blk, x, fn, ratio = term_ref.wide_lowpass(irdu, case)
+    _check_wide(blk, x, fn, ratio)
+
+
+def test_msgf_grad_wide(irdu):
+    """MultiScaleGraphFilter (v13 feature CNN, ngraphs = 4, S = 3) on (1, 3, 16, 264): the LNB reverse's
+    V = 8 gate ring and the term reverses' strips inside one full gradient.  Measured on an MI355X: forward
+    rel err 4.14e-7 against a smallest half-gap over max|t| of 5.49e-6; worst gradient rel err 2.9e-5."""
+    m, x, fn, ratio = term_ref.wide_msgf(irdu)
+    _check_wide(m, x, fn, ratio)
 
 
 def test_msgf_grad(irdu):

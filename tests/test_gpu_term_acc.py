@@ -4,8 +4,9 @@ grr_bwd_term_fused_acc (the row-streaming term reverse with the x-gradient pass 
 grr_bwd_term_fused + grr_bwd_stencil mode 3 on the same inputs, for the three operator terms: the
 accumulated x-gradient, the weight gradient and the per-graph / per-channel reductions.  Shapes cover
 one- and two-column lanes (W <= 128, where the fused pass runs), row segments with a ragged last segment
-(the segment's halo rows), the image's first and last rows, F up to 16.  The two-pass path
-is itself pinned by test_gpu_term_rows.py and the gradient tests.  grr_bwd_cg_glue with the half level's
+(the segment's halo rows), the image's first and last rows, F up to 16.  A HIP-vs-HIP comparison: both
+paths, the pass inside included (in strips and in the tail launch, at set_term_acc_max_w(1 << 20)), are
+pinned to float64 oracle autograd by test_gpu_term_oracle.py.  grr_bwd_cg_glue with the half level's
 x-gradient folded in (gx_half) against grr_bwd_unpool2_acc + the plain glue."""
 import pytest
 import torch

@@ -6,8 +6,9 @@ reductions to fp32 summation-order accuracy (the ring kernel's column strips are
 64 V - 8 owned columns against 62 V).  Covers ring depths 4-6, one and two
 workgroups per CU, segmented grids with ragged ends, one- to three-row images, F up to the ring's
 limit (7 at 4-column lanes, 12 below) and shapes the ring does not take (W % 4 != 0, F above it),
-which must fall back to the same result.  The register kernel is pinned against the per-pixel kernel
-by test_gpu_term_rows.py."""
+which must fall back to the same result.  A HIP-vs-HIP comparison: the register kernel is compared with
+the per-pixel kernel by test_gpu_term_rows.py, and all three (with the strips, the tail launch and the row
+segments) with float64 oracle autograd by test_gpu_term_oracle.py."""
 import pytest
 import torch
 

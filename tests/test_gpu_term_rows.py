@@ -1,8 +1,10 @@
 """grr_bwd_term_fused's row-streaming kernel (W <= 256; wider rows as column strips) against its per-pixel kernel, for the three
 operator terms (GLR, pair Laplacian, prox) and every instantiated F: the v output, the weight
 gradient (summed over the graph's channels through LDS), and the per-graph / per-channel
-reductions (<a, z>, gamma, taps).  The per-pixel kernel is itself pinned by the gradient tests
-(reference autograd golden + float64 oracle autograd, test_gpu_grad.py)."""
+reductions (<a, z>, gamma, taps).  A HIP-vs-HIP comparison: the per-pixel kernel, the row kernels, their
+strips, tail launch and segments are each pinned to float64 oracle autograd by test_gpu_term_oracle.py
+(per term, across the dispatch matrix) and by test_gpu_grad.py (end to end: W <= 20 in
+test_lowpass_block_grad, strip widths in test_lowpass_block_grad_wide)."""
 import pytest
 import torch
 
