@@ -155,6 +155,8 @@ def main():
                     help="full level's x-gradient sweep folded into the next glue pass (solver_grad.PADJ_GLUE; A/B)")
     ap.add_argument("--ln-skip", type=int, choices=[0, 1], default=1,
                     help="LNB skip term inside the norm's reverse pass (solver_grad.LN_SKIP_FUSED; A/B runs)")
+    ap.add_argument("--native-convs", type=int, choices=[0, 1], default=None,
+                    help="the v1.0 model's plain convolutions on libgrr (1) or on MIOpen (0); default: GRR_NATIVE_CONVS")
     ap.add_argument("--watchdog", type=float, default=0.0,
                     help="dump every thread's Python stack to stderr each N seconds (hang diagnosis)")
     ap.add_argument("--gpus", type=int, default=1, help="ranks (one process per GPU; spawned when not under torchrun)")
@@ -189,6 +191,9 @@ def main():
     SGK.UNPOOL_GLUE = bool(args.unpool_glue)
     SGK.PADJ_GLUE = bool(args.padj_glue)
     SGK.LN_SKIP_FUSED = bool(args.ln_skip)
+    if args.native_convs is not None:
+        irdu_amd.native_convs(bool(args.native_convs))
+    from irdu_amd import graph_filter as GF
     torch.manual_seed(2204)
     if args.model == "abstract":
         model = irdu_amd.AbtractMultiScaleGraphFilter(3, 3, n_cgd_iters=args.stages, **D_ARGS)
@@ -229,6 +234,7 @@ def main():
                "config": {"workload": f"{desc}, S={args.stages}, {args.size}x{args.size} RGB sigma=25",
                           "per_gpu_batch": args.batch, "aux_losses": args.aux_losses,
                           "parallelism": f"data parallel x{world}, bucketed RCCL grad all-reduce"},
+               "native_convs": int(GF.NATIVE_CONVS),
                "loss": loss, "hip_kernel_ms_per_step": round(hip_ms, 2),
                "peak_mem_gb": round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 1),
                "kernel_ms_per_step": {k: round(v["total_ms"] / args.steps, 3) for k, v in kern.items()}}

@@ -12,7 +12,8 @@ Importing changes no process-wide setting.  A drop-in training script with its o
 ``irdu_amd.miopen_training_defaults()`` before its first convolution (MIOpen's find-db otherwise costs
 seconds of host time per step on the v1.0 model's stock convolutions after a box's first run,
 DESIGN.md §4.r4); the first training-mode forward of AbtractMultiScaleGraphFilter warns once when
-MIOPEN_DEBUG_DISABLE_FIND_DB is unset.
+MIOPEN_DEBUG_DISABLE_FIND_DB is unset.  ``irdu_amd.native_convs(True)`` (or GRR_NATIVE_CONVS=1) runs that model's
+plain convolutions on libgrr as well; no MIOpen setting matters then and the warning stays silent.
 """
 from ._native import GrrError, NativeUnavailable, load as load_native  # noqa: F401
 from .graph_filter import (  # noqa: F401
@@ -28,6 +29,7 @@ from .graph_filter import (  # noqa: F401
     MultiScaleGraphFilter,
     ReginalPixelEmbeding,
     Upsampling,
+    native_convs,
 )
 from . import kernels  # noqa: F401
 from . import glr_v10 as v10  # noqa: F401  (GLR-only drop-ins of lib/model_GLR_GTV_deep_v10.py)

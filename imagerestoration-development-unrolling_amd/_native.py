@@ -71,6 +71,16 @@ SIGNATURES = {
     "grr_conv1x1_workspace_bytes": [I, I],
     "grr_conv1x1_ws": [P, P, P, P, I, I, I, L, P],
     "grr_conv2x2s2": [P, P, P, I, I, I, I, I, P],
+    "grr_conv3x3_embed_supported": [I, I],
+    "grr_conv3x3_embed": [P, P, P, I, I, I, I, I, P],
+    "grr_conv3x3_embed_bwd_w_workspace_bytes": [I, I, I, I, I],
+    "grr_conv3x3_embed_bwd_w": [P, P, P, P, I, I, I, I, I, P],
+    "grr_conv3x3_embed_bwd_x": [P, P, P, I, I, I, I, I, P],
+    "grr_convt2x2s2_workspace_bytes": [I, I, I, I, I],
+    "grr_convt2x2s2": [P, P, P, P, I, I, I, I, I, P],
+    "grr_conv1x1_cat2_supported": [I, I, I, L],
+    "grr_conv1x1_cat2_workspace_bytes": [I, I, I],
+    "grr_conv1x1_cat2": [P, P, P, P, P, I, I, I, I, L, P],
     "grr_ffn_workspace_bytes": [I, I, I, I, I],
     "grr_ffn_forward": [P, P, P, P, P, P, P, P, I, I, I, I, I, P],
     "grr_wgrad_workspace_bytes": [I, I, I, L],
@@ -154,7 +164,8 @@ SIGNATURES = {
 _RESTYPES = {"grr_version": c_int, "grr_last_error": ctypes.c_char_p, "grr_lnb_workspace_bytes": c_int64,
              "grr_conv1x1_workspace_bytes": c_int64, "grr_wgrad_workspace_bytes": c_int64,
              "grr_ffn_workspace_bytes": c_int64, "grr_scratch_bytes": c_int64,
-             "grr_lnb_fused_workspace_bytes": c_int64, "grr_feature_edges_workspace_bytes": c_int64}
+             "grr_lnb_fused_workspace_bytes": c_int64, "grr_feature_edges_workspace_bytes": c_int64,
+             "grr_conv3x3_embed_bwd_w_workspace_bytes": c_int64, "grr_conv1x1_cat2_workspace_bytes": c_int64, "grr_convt2x2s2_workspace_bytes": c_int64}
 
 _lib = None
 

@@ -427,6 +427,8 @@ struct X3Args {
   int64_t P;
   int K, M, nch, tiles;    // tiles: X3_PX-pixel tiles per image
   uint32_t nblk;
+  const float* x2;         // CAT: rows Ka .. K - 1 come from x2 [B, K - Ka, P] (Ka % 16 == 0), rows < Ka from x [B, Ka, P]
+  int Ka;
 };
 
 
@@ -434,7 +436,7 @@ struct X3Args {
 #define GRR_X3_WAVES 8
 #endif
 constexpr int X3_WV = GRR_X3_WAVES, X3_PX = 32 * X3_WV;   // pixels per workgroup
-template <int KS, bool LN>
+template <int KS, bool LN, bool CAT = false>
 __global__ __launch_bounds__(64 * X3_WV) void gemm_x3_kernel(X3Args a) {
   extern __shared__ __attribute__((aligned(16))) float x3_lds[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -468,14 +470,28 @@ __global__ __launch_bounds__(64 * X3_WV) void gemm_x3_kernel(X3Args a) {
   // wave-uniform slab base + 32-bit lane offsets (K P < 2^30, checked on the host); rows past K load
   // row K - 1 and are zeroed by a select (no per-load branches)
   // (through a buffer descriptor: row 16 s + j in soffset, rows >= K past num_records read 0)
+  // CAT: the K rows are the Ka rows of x followed by the K - Ka rows of x2 (the concatenation is never
+  // written): a k-step lies in one source (Ka % 16 == 0), each source has its own descriptor
+  const int Kx = CAT ? a.Ka : K;
   const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.x + (int64_t)b * K * P), (short)0, (int)(4u * (uint32_t)K * (uint32_t)P), 0x00020000);
+      const_cast<float*>(a.x + (int64_t)b * Kx * P), (short)0, (int)(4u * (uint32_t)Kx * (uint32_t)P), 0x00020000);
+  const __amdgpu_buffer_rsrc_t xrs2 = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<float*>(CAT ? a.x2 + (int64_t)b * (K - Kx) * P : a.x), (short)0,
+      CAT ? (int)(4u * (uint32_t)(K - Kx) * (uint32_t)P) : 0, 0x00020000);
   const uint32_t xvo = 4u * ((uint32_t)(8 * hf) * (uint32_t)P + (uint32_t)pc), xPb = 4u * (uint32_t)P;
 #pragma unroll
-  for (int s = 0; s < KS; ++s)
+  for (int s = 0; s < KS; ++s) {
+    if (!CAT || 16 * s < Kx) {
 #pragma unroll
-    for (int j = 0; j < 8; ++j)
-      xv[s][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xrs, xvo, (uint32_t)(16 * s + j) * xPb, 0));
+      for (int j = 0; j < 8; ++j)
+        xv[s][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xrs, xvo, (uint32_t)(16 * s + j) * xPb, 0));
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        xv[s][j] =
+            __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xrs2, xvo, (uint32_t)(16 * s - Kx + j) * xPb, 0));
+    }
+  }
   float rstd = 1.f;
   if constexpr (LN) {                          // CustomLayerNorm statistics (REF:916-922)
     float sum = 0.f;
@@ -552,14 +568,14 @@ __global__ __launch_bounds__(64 * X3_WV) void gemm_x3_kernel(X3Args a) {
   }
 }
 
-template <bool LN>
+template <bool LN, bool CAT = false>
 static grr_status launch_x3(const float* x, const uint16_t* frag, float* out, int B, int K, int M, int64_t P,
-                            hipStream_t s, const char* name) {
+                            hipStream_t s, const char* name, const float* x2 = nullptr, int Ka = 0) {
   GRR_REQUIRE(K >= 1 && K <= 128, GRR_ERR_UNSUPPORTED, "%s: K=%d outside [1, 128]", name, K);
   GRR_REQUIRE((int64_t)(K + 16) * P < (1ll << 30) && (int64_t)(M + 32) * P < (1ll << 30), GRR_ERR_UNSUPPORTED,
               "%s: K*P or M*P too large for 32-bit offsets", name);
   X3Args a{};
-  a.x = x; a.frag = frag; a.out = out; a.P = P; a.K = K; a.M = M;
+  a.x = x; a.frag = frag; a.out = out; a.P = P; a.K = K; a.M = M; a.x2 = x2; a.Ka = Ka;
   a.nch = (M + X3_MCH - 1) / X3_MCH;
   a.tiles = (int)((P + X3_PX - 1) / X3_PX);
   const uint64_t n = (uint64_t)B * a.tiles;
@@ -569,7 +585,7 @@ static grr_status launch_x3(const float* x, const uint16_t* frag, float* out, in
   const size_t lds = 2 * (size_t)x3_chunk_bytes(KS);
   switch (KS) {
 #define GRR_X3_CASE(ks) \
-    case ks: hipLaunchKernelGGL((gemm_x3_kernel<ks, LN>), dim3(a.nblk), dim3(64 * X3_WV), lds, s, a); break;
+    case ks: hipLaunchKernelGGL((gemm_x3_kernel<ks, LN, CAT>), dim3(a.nblk), dim3(64 * X3_WV), lds, s, a); break;
     GRR_X3_CASE(1) GRR_X3_CASE(2) GRR_X3_CASE(3) GRR_X3_CASE(4)
     GRR_X3_CASE(5) GRR_X3_CASE(6) GRR_X3_CASE(7) GRR_X3_CASE(8)
 #undef GRR_X3_CASE
@@ -612,9 +628,11 @@ struct X3KArgs {
   int K, M, KS, ngroups, nmt, tiles;
   int64_t CB;              // bytes per 32-row group image
   uint32_t nblk;
+  const float* x2;         // CAT: rows Ka .. K - 1 come from x2 [B, K - Ka, P] (Ka % 16 == 0), rows < Ka from x [B, Ka, P]
+  int Ka;
 };
 
-template <int TM, int EPI>
+template <int TM, int EPI, bool CAT = false>
 __global__ __launch_bounds__(64 * X3_WV, 4) void gemm_x3k_kernel(X3KArgs a) {
   static_assert(X3_NT == 1, "gemm_x3k_kernel reads the one-tile pack layout");
   extern __shared__ __attribute__((aligned(16))) float x3_lds[];
@@ -665,15 +683,27 @@ __global__ __launch_bounds__(64 * X3_WV, 4) void gemm_x3k_kernel(X3KArgs a) {
   // 4 (8 hf P + pc) + soffset 4 (16 s + j) P (wave-uniform, SGPR) -- no per-row address arithmetic in
   // the vector or scalar units; rows past K fall past num_records and read 0 ((K + 16) P < 2^30,
   // checked on the host)
-  const float* xs = a.x + (int64_t)b * K * P;
+  // CAT: rows < Ka from x [B, Ka, P], the others from x2 [B, K - Ka, P], each through its own descriptor (a
+  // k-step lies in one source, Ka % 16 == 0; a wave-uniform branch per k-step)
+  const int Kx = CAT ? a.Ka : K;
+  const float* xs = a.x + (int64_t)b * Kx * P;
   const uint32_t P32 = (uint32_t)P, pc32 = (uint32_t)pc;
   const __amdgpu_buffer_rsrc_t xrs =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xs), (short)0, (int)(4u * (uint32_t)K * P32), 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xs), (short)0, (int)(4u * (uint32_t)Kx * P32), 0x00020000);
+  const __amdgpu_buffer_rsrc_t xrs2 = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<float*>(CAT ? a.x2 + (int64_t)b * (K - Kx) * P : xs), (short)0,
+      CAT ? (int)(4u * (uint32_t)(K - Kx) * P32) : 0, 0x00020000);
   const uint32_t voff = 4u * ((uint32_t)(8 * hf) * P32 + pc32), Pb = 4u * P32;
   auto load = [&](int s, float (&v)[8]) {
+    if (!CAT || 16 * s < Kx) {
 #pragma unroll
-    for (int j = 0; j < 8; ++j)
-      v[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xrs, voff, (uint32_t)(16 * s + j) * Pb, 0));
+      for (int j = 0; j < 8; ++j)
+        v[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xrs, voff, (uint32_t)(16 * s + j) * Pb, 0));
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        v[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xrs2, voff, (uint32_t)(16 * s - Kx + j) * Pb, 0));
+    }
   };
 
   f32x16 acc[TM];
@@ -764,14 +794,15 @@ __global__ __launch_bounds__(64 * X3_WV, 4) void gemm_x3k_kernel(X3KArgs a) {
     }
 }
 
-template <int EPI = X3K_STORE>
+template <int EPI = X3K_STORE, bool CAT = false>
 static grr_status launch_x3k(const float* x, const uint16_t* frag, float* out, int B, int K, int M, int64_t P,
                              hipStream_t s, const char* name, const float* sd = nullptr, const float* res = nullptr,
-                             const float* skip = nullptr) {
+                             const float* skip = nullptr, const float* x2 = nullptr, int Ka = 0) {
   GRR_REQUIRE((int64_t)(K + 16) * P < (1ll << 30) && (int64_t)(M + 128) * P < (1ll << 30), GRR_ERR_UNSUPPORTED,
               "%s: K*P or M*P too large for 32-bit offsets", name);
   X3KArgs a{};
   a.x = x; a.frag = frag; a.out = out; a.P = P; a.K = K; a.M = M; a.sd = sd; a.res = res; a.skip = skip;
+  a.x2 = x2; a.Ka = Ka;
   a.KS = (K + 15) / 16;
   a.ngroups = (M + 31) / 32;
   a.CB = x3_chunk_bytes(a.KS);
@@ -784,10 +815,10 @@ static grr_status launch_x3k(const float* x, const uint16_t* frag, float* out, i
   a.nblk = (uint32_t)n;
   const size_t lds = 3 * (size_t)X3K_KC * TM * 3 * 1024;
   switch (TM) {
-    case 1: hipLaunchKernelGGL((gemm_x3k_kernel<1, EPI>), dim3(a.nblk), dim3(64 * X3_WV), lds, s, a); break;
-    case 2: hipLaunchKernelGGL((gemm_x3k_kernel<2, EPI>), dim3(a.nblk), dim3(64 * X3_WV), lds, s, a); break;
-    case 3: hipLaunchKernelGGL((gemm_x3k_kernel<3, EPI>), dim3(a.nblk), dim3(64 * X3_WV), lds, s, a); break;
-    default: hipLaunchKernelGGL((gemm_x3k_kernel<4, EPI>), dim3(a.nblk), dim3(64 * X3_WV), lds, s, a); break;
+    case 1: hipLaunchKernelGGL((gemm_x3k_kernel<1, EPI, CAT>), dim3(a.nblk), dim3(64 * X3_WV), lds, s, a); break;
+    case 2: hipLaunchKernelGGL((gemm_x3k_kernel<2, EPI, CAT>), dim3(a.nblk), dim3(64 * X3_WV), lds, s, a); break;
+    case 3: hipLaunchKernelGGL((gemm_x3k_kernel<3, EPI, CAT>), dim3(a.nblk), dim3(64 * X3_WV), lds, s, a); break;
+    default: hipLaunchKernelGGL((gemm_x3k_kernel<4, EPI, CAT>), dim3(a.nblk), dim3(64 * X3_WV), lds, s, a); break;
   }
   return launch_status(name);
 }
@@ -860,6 +891,43 @@ grr_status grr_conv1x1_ws(const float* x, const float* wt, float* out, void* wor
   }
   if (K > 128) return launch_x3k(x, frag, out, B, K, M, P, s, "grr_conv1x1_ws");
   return launch_x3<false>(x, frag, out, B, K, M, P, s, "grr_conv1x1_ws");
+}
+
+// nn.Conv2d(Ka + Kb, M, 1) on cat([xa, xb], 1) without the concatenation: the x3 kernels' B-operand loader
+// takes each k-step's rows from xa or xb; the summation order is grr_conv1x1_ws's on the concatenated tensor
+// (the same packed weights, the same MFMA sequence), so the two results are bitwise equal
+int grr_conv1x1_cat2_supported(int Ka, int Kb, int M, int64_t P) {
+  const int64_t K = (int64_t)Ka + Kb;
+  return Ka >= 16 && Ka % 16 == 0 && Kb >= 1 && K <= 4096 && M >= 1 && M <= (1 << 20) && P >= 1 &&
+         (K + 16) * P < (1ll << 30) && ((int64_t)M + 128) * P < (1ll << 30);
+}
+
+int64_t grr_conv1x1_cat2_workspace_bytes(int Ka, int Kb, int M) {
+  if (Ka < 1 || Kb < 1) return 0;
+  return grr_conv1x1_workspace_bytes(Ka + Kb, M);
+}
+
+grr_status grr_conv1x1_cat2(const float* xa, const float* xb, const float* wt, float* out, void* workspace, int B,
+                            int Ka, int Kb, int M, int64_t P, void* stream) {
+  clear_error();
+  GRR_REQUIRE(xa && xb && wt && out && workspace && B > 0 && Ka > 0 && Kb > 0 && M > 0 && P > 0, GRR_ERR_INVALID_ARG,
+              "grr_conv1x1_cat2: bad args");
+  GRR_REQUIRE(out != xa && out != xb, GRR_ERR_INVALID_ARG, "grr_conv1x1_cat2: out aliases an input");
+  GRR_REQUIRE(((uintptr_t)workspace & 255) == 0, GRR_ERR_INVALID_ARG, "grr_conv1x1_cat2: workspace not 256-B aligned");
+  GRR_REQUIRE(grr_conv1x1_cat2_supported(Ka, Kb, M, P), GRR_ERR_UNSUPPORTED,
+              "grr_conv1x1_cat2: Ka=%d (a multiple of 16), Kb=%d, M=%d, P=%lld not supported", Ka, Kb, M, (long long)P);
+  hipStream_t s = (hipStream_t)stream;
+  const int K = Ka + Kb, KS = (K + 15) / 16, nch = (M + X3_MCH - 1) / X3_MCH;
+  uint16_t* frag = (uint16_t*)workspace;
+  const int64_t nf = (int64_t)nch * x3_chunk_bytes(KS) / 2;
+  hipLaunchKernelGGL(x3_pack_kernel, dim3((unsigned)std::min<int64_t>((nf + 255) / 256, 1 << 16)), dim3(256), 0, s,
+                     wt, nullptr, frag, M, K, KS, nch);
+  grr_status st = launch_status("grr_conv1x1_cat2/pack");
+  if (st != GRR_OK) return st;
+  if (K > 128)
+    return launch_x3k<X3K_STORE, true>(xa, frag, out, B, K, M, P, s, "grr_conv1x1_cat2", nullptr, nullptr, nullptr, xb,
+                                       Ka);
+  return launch_x3<false, true>(xa, frag, out, B, K, M, P, s, "grr_conv1x1_cat2", xb, Ka);
 }
 
 grr_status grr_conv2x2s2(const float* x, const float* wt, float* out, int B, int K, int M, int H, int W,

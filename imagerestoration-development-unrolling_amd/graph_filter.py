@@ -44,6 +44,25 @@ FEATURE_STREAMS = os.environ.get("GRR_FEATURE_STREAMS", "1") == "1"
 # GEMMs co-resident on both streams; those reductions now run on grr_wgrad
 FEATURE_STREAMS_TRAIN = os.environ.get("GRR_FEATURE_STREAMS_TRAIN", "1") == "1"
 _SIDE_STREAMS = {}
+# The v1.0 model's plain convolutions (ReginalPixelEmbeding, Downsampling, Upsampling, the three combines,
+# linear_output) on libgrr instead of MIOpen: a forward and a training step then issue no library convolution
+# or GEMM (GRR_NATIVE_CONVS=1 or native_convs(True); default off: the stock nn.Conv2d / nn.ConvTranspose2d run)
+NATIVE_CONVS = os.environ.get("GRR_NATIVE_CONVS", "0") == "1"
+
+
+def native_convs(flag: bool) -> None:
+    """Turn the HIP encoder / decoder convolutions of AbtractMultiScaleGraphFilter on or off (process-wide)."""
+    global NATIVE_CONVS
+    NATIVE_CONVS = bool(flag)
+
+
+def _native_ok(*tensors) -> bool:
+    """The native convolutions take fp32 GPU tensors only; anything else stays on the stock module.  (While
+    Dynamo traces, the device is not asked: the captured graph holds the irdu:: ops like the rest of the model.)"""
+    if not NATIVE_CONVS:
+        return False
+    tracing = torch.compiler.is_compiling()
+    return all((t.is_cuda or tracing) and t.dtype == torch.float32 and t.dim() == 4 for t in tensors)
 
 
 def _side_stream(dev: torch.device) -> "torch.cuda.Stream":
@@ -654,7 +673,13 @@ class ReginalPixelEmbeding(HipModule):
                                                     padding_mode="replicate", bias=False)
 
     def forward(self, x):
-        return self.channels_local_linear_op01(x)
+        conv = self.channels_local_linear_op01
+        if _native_ok(x, conv.weight) and K.conv3x3_embed_ok(x.shape[1], conv.out_channels) \
+                and x.shape[1] == conv.in_channels:
+            if records_grad(self, x):
+                return SG.Conv3x3EmbedFn.apply(x.contiguous(), conv.weight)
+            return OPS.conv3x3_embed(x.contiguous(), conv.weight)
+        return conv(x)
 
 
 class Downsampling(HipModule):
@@ -663,7 +688,13 @@ class Downsampling(HipModule):
         self.local_linear = nn.Conv2d(dim_in, dim_out, kernel_size=2, stride=2, padding=0, groups=nsubnets, bias=False)
 
     def forward(self, x):
-        return self.local_linear(x)
+        conv = self.local_linear
+        if conv.groups == 1 and _native_ok(x, conv.weight) and x.shape[1] == conv.in_channels \
+                and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0:
+            if records_grad(self, x):
+                return SG.Conv2x2s2Fn.apply(x.contiguous(), conv.weight)
+            return OPS.conv2x2s2(x.contiguous(), conv.weight)
+        return conv(x)
 
 
 class Upsampling(HipModule):
@@ -673,7 +704,31 @@ class Upsampling(HipModule):
                                                bias=False)
 
     def forward(self, x):
-        return self.local_linear(x)
+        conv = self.local_linear
+        if conv.groups == 1 and _native_ok(x, conv.weight) and x.shape[1] == conv.in_channels \
+                and K.convt2x2s2_ok(conv.in_channels, conv.out_channels, x.shape[2], x.shape[3]):
+            if records_grad(self, x):
+                return SG.ConvT2x2s2Fn.apply(x.contiguous(), conv.weight)
+            return OPS.convt2x2s2(x.contiguous(), conv.weight)
+        return conv(x)
+
+
+def _combine(conv: nn.Conv2d, a, b):
+    """conv(cat([a, b], 1)) for a decoder combine (1x1, no bias); native: the concatenation is not written."""
+    if conv.groups == 1 and _native_ok(a, b, conv.weight) and a.shape[1] + b.shape[1] == conv.in_channels:
+        if records_grad(conv, a, b):
+            return SG.Conv1x1Cat2Fn.apply(a.contiguous(), b.contiguous(), conv.weight)
+        return OPS.conv1x1_cat2(a.contiguous(), b.contiguous(), conv.weight)
+    return conv(torch.cat([a, b], 1))
+
+
+def _project(conv: nn.Conv2d, x):
+    """conv(x) for a plain 1x1 convolution without bias (linear_output)."""
+    if conv.groups == 1 and _native_ok(x, conv.weight) and x.shape[1] == conv.in_channels:
+        if records_grad(conv, x):
+            return SG.Conv1x1Fn.apply(x.contiguous(), conv.weight)
+        return OPS.conv1x1(x.contiguous(), conv.weight)
+    return conv(x)
 
 
 _MIOPEN_CHECKED = False
@@ -743,18 +798,26 @@ class AbtractMultiScaleGraphFilter(HipModule):
 
     def decode(self, coefs):
         e0, e1, e2, e3 = coefs
-        d = self.combine_channels_02(torch.cat([self.up_sample_03_02(e3), e2], 1))
+        d = _combine(self.combine_channels_02, self.up_sample_03_02(e3), e2)
         d = self.decoder_scale_02(d)
-        d = self.combine_channels_01(torch.cat([self.up_sample_02_01(d), e1], 1))
+        d = _combine(self.combine_channels_01, self.up_sample_02_01(d), e1)
         d = self.decoder_scale_01(d)
-        d = self.combine_channels_00(torch.cat([self.up_sample_01_00(d), e0], 1))
+        d = _combine(self.combine_channels_00, self.up_sample_01_00(d), e0)
         d = self.decoder_scale_00(d)
-        return self.linear_output(self.refining_block(d))
+        return _project(self.linear_output, self.refining_block(d))
 
     def enc_dec(self, img):
         return self.decode(self.encode(img))
 
+    def _native_covered(self, img) -> bool:
+        """True when NATIVE_CONVS takes every plain convolution of this forward (no MIOpen call is left)."""
+        emb = self.patch_3x3_embeding.channels_local_linear_op01
+        return (_native_ok(img) and K.conv3x3_embed_ok(emb.in_channels, emb.out_channels)
+                and img.shape[2] % 8 == 0 and img.shape[3] % 8 == 0
+                and all(c.groups == 1 for c in (self.combine_channels_02, self.combine_channels_01,
+                                                self.combine_channels_00, self.up_sample_03_02.local_linear)))
+
     def forward(self, img):
-        if self.training and torch.is_grad_enabled():
+        if self.training and torch.is_grad_enabled() and not self._native_covered(img):
             _warn_miopen_find_db()
         return self.decode(self.filtering(self.encode(img)))

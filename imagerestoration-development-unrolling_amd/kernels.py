@@ -630,6 +630,123 @@ def conv2x2s2(x: Tensor, weight: Tensor) -> Tensor:
     return out
 
 
+# ---- v1.0 encoder / decoder convolutions (csrc/codec_ops.hip) -----------------
+def _ws(nbytes: int, dev) -> Tensor:
+    return torch.empty((max(int(nbytes), 4) + 3) // 4, dtype=torch.float32, device=dev)  # allocator: 512-B aligned
+
+
+def conv3x3_embed_ok(cin: int, m: int) -> bool:
+    """grr_conv3x3_embed_supported in plain Python (traceable; tests/test_codec_abi.py checks the two agree)."""
+    return 1 <= cin <= 4 and 1 <= m <= 128
+
+
+def convt2x2s2_ok(k: int, m: int, h: int, w: int) -> bool:
+    """Where grr_convt2x2s2 applies (grr_convt2x2s2_workspace_bytes > 0 and its H*W limit), in plain Python."""
+    return 1 <= k <= 4096 and 1 <= m <= (1 << 20) and h >= 1 and w >= 1 and h * w * 16 < (1 << 31)
+
+
+def conv1x1_cat2_ok(ka: int, kb: int, m: int, p: int) -> bool:
+    """grr_conv1x1_cat2_supported in plain Python: a k-step of 16 rows must lie in one source."""
+    k = ka + kb
+    return (ka >= 16 and ka % 16 == 0 and kb >= 1 and k <= 4096 and 1 <= m <= (1 << 20) and p >= 1
+            and (k + 16) * p < (1 << 30) and (m + 128) * p < (1 << 30))
+
+
+def _embed_shapes(name: str, x: Tensor, weight: Tensor) -> Tuple[int, int, int, int, int]:
+    if x.dim() != 4 or weight.dim() != 4:
+        raise ValueError(f"{name}: expected x [B,Cin,H,W] and weight [M,Cin,3,3]")
+    b, cin, h, w = x.shape
+    m = weight.shape[0]
+    if tuple(weight.shape[1:]) != (cin, 3, 3):
+        raise ValueError(f"{name}: weight {tuple(weight.shape)} vs input channels {cin}")
+    if not conv3x3_embed_ok(cin, m) or min(b, h, w) < 1:
+        raise ValueError(f"{name}: Cin={cin}, M={m} outside the kernel's range (Cin <= 4, M <= 128)")
+    return b, cin, m, h, w
+
+
+def conv3x3_embed(x: Tensor, weight: Tensor) -> Tensor:
+    """nn.Conv2d(Cin, M, 3, padding=1, padding_mode="replicate", bias=False) with weight [M,Cin,3,3]."""
+    dev = _check("conv3x3_embed", x, weight)
+    b, cin, m, h, w = _embed_shapes("conv3x3_embed", x, weight)
+    out = torch.empty((b, m, h, w), dtype=torch.float32, device=dev)
+    _launch("conv3x3_embed", 4 * b * h * w * (cin + m), "grr_conv3x3_embed", x.data_ptr(), weight.data_ptr(),
+            out.data_ptr(), b, cin, m, h, w, _stream(dev), flops=2 * b * h * w * 9 * cin * m)
+    return out
+
+
+def conv3x3_embed_bwd_w(g: Tensor, x: Tensor) -> Tensor:
+    """Weight gradient of conv3x3_embed: g [B,M,H,W], x [B,Cin,H,W] -> [M,Cin,3,3] (fixed summation order)."""
+    dev = _check("conv3x3_embed_bwd_w", g, x)
+    if x.dim() != 4 or g.dim() != 4 or g.shape[0] != x.shape[0] or g.shape[2:] != x.shape[2:]:
+        raise ValueError(f"conv3x3_embed_bwd_w: g {tuple(g.shape)} vs x {tuple(x.shape)}")
+    b, cin, h, w = x.shape
+    m = g.shape[1]
+    if not conv3x3_embed_ok(cin, m) or min(b, h, w) < 1:
+        raise ValueError(f"conv3x3_embed_bwd_w: Cin={cin}, M={m} outside the kernel's range (Cin <= 4, M <= 128)")
+    gw = torch.empty((m, cin, 3, 3), dtype=torch.float32, device=dev)
+    ws = _ws(_native.load().grr_conv3x3_embed_bwd_w_workspace_bytes(b, cin, m, h, w), dev)
+    _launch("conv3x3_embed_bwd_w", 4 * b * h * w * (m + cin + 18 * cin), "grr_conv3x3_embed_bwd_w", g.data_ptr(),
+            x.data_ptr(), gw.data_ptr(), ws.data_ptr(), b, cin, m, h, w, _stream(dev),
+            flops=2 * b * h * w * 9 * cin * m)
+    return gw
+
+
+def conv3x3_embed_bwd_x(g: Tensor, weight: Tensor) -> Tensor:
+    """Data gradient of conv3x3_embed: g [B,M,H,W], weight [M,Cin,3,3] -> [B,Cin,H,W]."""
+    dev = _check("conv3x3_embed_bwd_x", g, weight)
+    if g.dim() != 4 or weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or weight.shape[0] != g.shape[1]:
+        raise ValueError(f"conv3x3_embed_bwd_x: g {tuple(g.shape)} vs weight {tuple(weight.shape)}")
+    b, m, h, w = g.shape
+    cin = weight.shape[1]
+    if not conv3x3_embed_ok(cin, m) or min(b, h, w) < 1:
+        raise ValueError(f"conv3x3_embed_bwd_x: Cin={cin}, M={m} outside the kernel's range (Cin <= 4, M <= 128)")
+    gx = torch.empty((b, cin, h, w), dtype=torch.float32, device=dev)
+    _launch("conv3x3_embed_bwd_x", 4 * b * h * w * (m + cin), "grr_conv3x3_embed_bwd_x", g.data_ptr(),
+            weight.data_ptr(), gx.data_ptr(), b, cin, m, h, w, _stream(dev), flops=2 * b * h * w * 9 * cin * m)
+    return gx
+
+
+def convt2x2s2(x: Tensor, weight: Tensor) -> Tensor:
+    """nn.ConvTranspose2d(K, M, 2, stride=2, bias=False) with weight [K,M,2,2]: x [B,K,H,W] -> [B,M,2H,2W]."""
+    dev = _check("convt2x2s2", x, weight)
+    if x.dim() != 4 or weight.dim() != 4:
+        raise ValueError("convt2x2s2: expected x [B,K,H,W] and weight [K,M,2,2]")
+    b, k, h, w = x.shape
+    m = weight.shape[1]
+    if tuple(weight.shape) != (k, m, 2, 2):
+        raise ValueError(f"convt2x2s2: weight {tuple(weight.shape)} vs input channels {k}")
+    if not convt2x2s2_ok(k, m, h, w) or b < 1:
+        raise ValueError(f"convt2x2s2: shape {tuple(x.shape)} -> {m} channels outside the kernel's range")
+    out = torch.empty((b, m, 2 * h, 2 * w), dtype=torch.float32, device=dev)
+    ws = _ws(_native.load().grr_convt2x2s2_workspace_bytes(b, k, m, h, w), dev)
+    kind = f"convt2x2s2[{k}->{m},{b}x{h}x{w}]" if TIMER_SHAPES else "convt2x2s2"
+    _launch(kind, 4 * b * h * w * (k + 4 * m), "grr_convt2x2s2", x.data_ptr(), weight.data_ptr(), out.data_ptr(),
+            ws.data_ptr(), b, k, m, h, w, _stream(dev), flops=2 * b * h * w * k * 4 * m)
+    return out
+
+
+def conv1x1_cat2(xa: Tensor, xb: Tensor, weight: Tensor) -> Tensor:
+    """nn.Conv2d(Ka + Kb, M, 1, bias=False) on cat([xa, xb], 1), weight [M,Ka+Kb,1,1].  Where grr_conv1x1_cat2
+    applies (conv1x1_cat2_ok) the concatenation is never written and the result is bitwise conv1x1's on it;
+    elsewhere this concatenates and calls conv1x1."""
+    dev = _check("conv1x1_cat2", xa, xb, weight)
+    if xa.dim() != 4 or xb.dim() != 4 or xa.shape[0] != xb.shape[0] or xa.shape[2:] != xb.shape[2:]:
+        raise ValueError(f"conv1x1_cat2: inputs {tuple(xa.shape)} and {tuple(xb.shape)} disagree")
+    b, ka, h, w = xa.shape
+    kb = xb.shape[1]
+    m = weight.shape[0]
+    if weight.numel() != m * (ka + kb) or weight.shape[1] != ka + kb:
+        raise ValueError(f"conv1x1_cat2: weight {tuple(weight.shape)} vs input channels {ka} + {kb}")
+    if not conv1x1_cat2_ok(ka, kb, m, h * w):
+        return conv1x1(torch.cat([xa, xb], 1), weight)
+    out = torch.empty((b, m, h, w), dtype=torch.float32, device=dev)
+    ws = _ws(_native.load().grr_conv1x1_cat2_workspace_bytes(ka, kb, m), dev)
+    kind = f"conv1x1_cat2[{ka}+{kb}->{m},{b}x{h}x{w}]" if TIMER_SHAPES else "conv1x1_cat2"
+    _launch(kind, 4 * b * h * w * (ka + kb + m), "grr_conv1x1_cat2", xa.data_ptr(), xb.data_ptr(), weight.data_ptr(),
+            out.data_ptr(), ws.data_ptr(), b, ka, kb, m, h * w, _stream(dev), flops=2 * b * h * w * (ka + kb) * m)
+    return out
+
+
 def ffn_forward(x: Tensor, ln_w: Tensor, w_in: Tensor, w_dw: Tensor, w_out: Tensor, skip: Tensor) -> Tensor:
     """FFBlock of the window models' feature CNN (grr_ffn_forward, REF7:13-67): x [B,C,H,W]; ln_w [C];
     w_in [2 hid, C]; w_dw [2 hid, 9]; w_out [C, hid]; skip [2]."""

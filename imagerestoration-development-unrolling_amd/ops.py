@@ -76,6 +76,37 @@ def _(x, weight, fold):
     return x.new_empty((x.shape[0], weight.shape[0], x.shape[2] // 2, x.shape[3] // 2))
 
 
+# ---- v1.0 encoder / decoder convolutions -------------------------------------------------
+@custom_op(f"{NS}::conv3x3_embed", mutates_args=())
+def conv3x3_embed_op(x: Tensor, weight: Tensor) -> Tensor:
+    return K.conv3x3_embed(x.contiguous(), weight.contiguous())
+
+
+@conv3x3_embed_op.register_fake
+def _(x, weight):
+    return x.new_empty((x.shape[0], weight.shape[0], x.shape[2], x.shape[3]))
+
+
+@custom_op(f"{NS}::convt2x2s2", mutates_args=())
+def convt2x2s2_op(x: Tensor, weight: Tensor) -> Tensor:
+    return K.convt2x2s2(x.contiguous(), weight.contiguous())
+
+
+@convt2x2s2_op.register_fake
+def _(x, weight):
+    return x.new_empty((x.shape[0], weight.shape[1], 2 * x.shape[2], 2 * x.shape[3]))
+
+
+@custom_op(f"{NS}::conv1x1_cat2", mutates_args=())
+def conv1x1_cat2_op(xa: Tensor, xb: Tensor, weight: Tensor) -> Tensor:
+    return K.conv1x1_cat2(xa.contiguous(), xb.contiguous(), weight.contiguous())
+
+
+@conv1x1_cat2_op.register_fake
+def _(xa, xb, weight):
+    return xa.new_empty((xa.shape[0], weight.shape[0], xa.shape[2], xa.shape[3]))
+
+
 @custom_op(f"{NS}::lnb_forward", mutates_args=())
 def lnb_forward_op(x: Tensor, ln_w: Tensor, w1: Tensor, wdw: Tensor, w2: Tensor, skip: Tensor) -> Tensor:
     return K.lnb_forward(x.contiguous(), ln_w.contiguous(), w1.contiguous(), wdw.contiguous(), w2.contiguous(),
@@ -387,7 +418,7 @@ def _(e6, w, *args):
 OPS = [conv1x1_op, conv2x2s2_op, lnb_forward_op, lnb_forward_rep_op, repeat_graphs_op, pool2_op, edge_weights_op,
        edge_weights_block_op, gtv_pair_weights_op, system_half_op, gtv_rhs_half_op, gtv_rhs_full_op, system_step_op,
        system_step2_op, system_first_pair_op, glr_stage_op, neighbor_gather_op, normalize_features_op, stats_conv_op, glr_op_L_norm_op, gtv_op_C_op,
-       gtv_op_C_transpose_op]
+       gtv_op_C_transpose_op, conv3x3_embed_op, convt2x2s2_op, conv1x1_cat2_op]
 
 
 # =========================================================================================
@@ -417,6 +448,18 @@ def conv2x2s2(x, weight, fold=False):
     if _tracing():
         return torch.ops.irdu.conv2x2s2(x, weight, fold)
     return K.conv2x2s2(x, _fold(weight, x.shape[1]) if fold else weight)
+
+
+def conv3x3_embed(x, weight):
+    return torch.ops.irdu.conv3x3_embed(x, weight) if _tracing() else K.conv3x3_embed(x, weight)
+
+
+def convt2x2s2(x, weight):
+    return torch.ops.irdu.convt2x2s2(x, weight) if _tracing() else K.convt2x2s2(x, weight)
+
+
+def conv1x1_cat2(xa, xb, weight):
+    return torch.ops.irdu.conv1x1_cat2(xa, xb, weight) if _tracing() else K.conv1x1_cat2(xa, xb, weight)
 
 
 def lnb_forward(x, ln_w, w1, wdw, w2, skip):

@@ -504,6 +504,99 @@ def _repeat_fake(consts, img: Tensor):
 REPEAT_GRAPHS = OpaqueFunction("repeat_graphs_train", 1, _repeat_fwd, _repeat_bwd, _repeat_fake)
 
 
+# ---- v1.0 encoder / decoder convolutions (csrc/codec_ops.hip) ------------------
+# ReginalPixelEmbeding's 3x3 replicate-padded conv (REF:991-1009): the weight gradient gathers the clamped
+# taps and reduces them on grr_wgrad; the data gradient runs only when the image asks for one
+def _embed_fwd(consts, x: Tensor, weight: Tensor):
+    return [K.conv3x3_embed(x.contiguous(), weight.contiguous())], []
+
+
+def _embed_bwd(consts, inputs, outs, saved, gouts, needs):
+    x, weight = inputs
+    g = gouts[0].contiguous()
+    gx = K.conv3x3_embed_bwd_x(g, weight.contiguous()) if needs[0] else None
+    gw = K.conv3x3_embed_bwd_w(g, x.contiguous()) if needs[1] else None
+    return gx, gw
+
+
+def _embed_fake(consts, x: Tensor, weight: Tensor):
+    return [_new(x, x.shape[0], weight.shape[0], x.shape[2], x.shape[3])], []
+
+
+CONV3X3_EMBED = OpaqueFunction("conv3x3_embed_train", 1, _embed_fwd, _embed_bwd, _embed_fake)
+
+
+# nn.ConvTranspose2d(K, M, 2, stride=2, bias=False) (REF:1019-1025), weight [K, M, 2, 2]: the data gradient is
+# the 2x2 / stride-2 convolution of g with the same weight read as [out = K, in = M, 2, 2]; the weight
+# gradient is grr_wgrad of x against g's 2x2 patches in (m, di, dj) order
+def _convt_fwd(consts, x: Tensor, weight: Tensor):
+    return [K.convt2x2s2(x.contiguous(), weight.contiguous())], []
+
+
+def _convt_bwd(consts, inputs, outs, saved, gouts, needs):
+    x, weight = inputs
+    g = gouts[0].contiguous()
+    b, k, h, w = x.shape
+    m = weight.shape[1]
+    gx = K.conv2x2s2(g, weight.contiguous()) if needs[0] else None
+    gw = None
+    if needs[1]:
+        patches = g.reshape(b, m, h, 2, w, 2).permute(0, 1, 3, 5, 2, 4).reshape(b, m * 4, -1)
+        gw = K.wgrad(x.contiguous(), patches).view_as(weight)
+    return gx, gw
+
+
+def _convt_fake(consts, x: Tensor, weight: Tensor):
+    return [_new(x, x.shape[0], weight.shape[1], 2 * x.shape[2], 2 * x.shape[3])], []
+
+
+CONVT2X2S2 = OpaqueFunction("convt2x2s2_train", 1, _convt_fwd, _convt_bwd, _convt_fake)
+
+
+# the decoder's combine nn.Conv2d(Ka + Kb, M, 1) on cat([xa, xb], 1), never concatenated: the reverse is two
+# transposed-weight conv1x1 calls and two grr_wgrad calls joined along K
+def _cat2_fwd(consts, xa: Tensor, xb: Tensor, weight: Tensor):
+    return [K.conv1x1_cat2(xa.contiguous(), xb.contiguous(), weight.contiguous())], []
+
+
+def _cat2_bwd(consts, inputs, outs, saved, gouts, needs):
+    xa, xb, weight = inputs
+    g = gouts[0].contiguous()
+    m, ka, kb = weight.shape[0], xa.shape[1], xb.shape[1]
+    w2 = weight.reshape(m, ka + kb)
+    gxa = K.conv1x1(g, w2[:, :ka].t().contiguous().view(ka, m, 1, 1)) if needs[0] else None
+    gxb = K.conv1x1(g, w2[:, ka:].t().contiguous().view(kb, m, 1, 1)) if needs[1] else None
+    gw = None
+    if needs[2]:
+        gw = torch.cat([K.wgrad(g, xa.contiguous()), K.wgrad(g, xb.contiguous())], 1).view_as(weight)
+    return gxa, gxb, gw
+
+
+def _cat2_fake(consts, xa: Tensor, xb: Tensor, weight: Tensor):
+    return [_new(xa, xa.shape[0], weight.shape[0], xa.shape[2], xa.shape[3])], []
+
+
+CONV1X1_CAT2 = OpaqueFunction("conv1x1_cat2_train", 1, _cat2_fwd, _cat2_bwd, _cat2_fake)
+
+
+class Conv3x3EmbedFn:
+    @staticmethod
+    def apply(x: Tensor, weight: Tensor) -> Tensor:
+        return CONV3X3_EMBED([], x, weight)
+
+
+class ConvT2x2s2Fn:
+    @staticmethod
+    def apply(x: Tensor, weight: Tensor) -> Tensor:
+        return CONVT2X2S2([], x, weight)
+
+
+class Conv1x1Cat2Fn:
+    @staticmethod
+    def apply(xa: Tensor, xb: Tensor, weight: Tensor) -> Tensor:
+        return CONV1X1_CAT2([], xa, xb, weight)
+
+
 class Conv1x1Fn:
     @staticmethod
     def apply(x: Tensor, weight: Tensor) -> Tensor:

@@ -41,6 +41,8 @@ _TRIVIAL = {
     "squeeze", "permute", "expand", "t", "transpose", "unbind", "split", "split_with_sizes", "chunk",
     "narrow", "contiguous", "record_stream", "set_", "resize_", "_local_scalar_dense", "cat", "stack",
     "flip", "_pin_memory", "is_pinned", "index_select", "masked_fill", "masked_fill_",
+    # autograd's reverse of select / slice (skip_weight[0] * y): a zero fill and a strided copy
+    "select_backward", "slice_backward",
 }
 
 

@@ -421,6 +421,11 @@ class Trainer:
         self.w_perturb = float(tconf.get("loss03_weight", 0.5))
         self.latent_noise = float(tconf.get("latent_noise", 0.05))
         self.bucket_mb = float(tconf.get("allreduce_bucket_mb", 32.0))
+        # train.native_convs: the v1.0 model's plain convolutions on libgrr (graph_filter.NATIVE_CONVS); absent:
+        # the process-wide switch (GRR_NATIVE_CONVS, default off) is left as it is
+        if tconf.get("native_convs") is not None:
+            from . import graph_filter
+            graph_filter.native_convs(bool(int(tconf["native_convs"])))
         # all-reduces overlapped with the reverse sweep (post-accumulate-grad hooks); inert on one rank
         self.reducer = sharding.OverlappedGradReducer(self.model.parameters(), bucket_mb=self.bucket_mb)
         self.i = 0

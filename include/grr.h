@@ -298,6 +298,46 @@ grr_status grr_conv1x1_ws(const float* x, const float* wt, float* out, void* wor
 grr_status grr_conv2x2s2(const float* x, const float* wt, float* out, int B, int K, int M, int H, int W,
                          void* stream);
 
+/* ---- v1.0 encoder / decoder convolutions (codec_ops.hip) ---------------------- */
+
+/* ReginalPixelEmbeding (REF:991-1009): 3x3 convolution, replicate padding, no bias.  x [B,Cin,H,W],
+ * wt [M,Cin,3,3] -> out [B,M,H,W]; 1 <= Cin <= 4, 1 <= M <= 128 (grr_conv3x3_embed_supported), any H, W >= 1.
+ * Every output is one fmaf chain over (c, ky, kx) in ascending order: bitwise independent of tiling,
+ * batch and position. */
+int grr_conv3x3_embed_supported(int Cin, int M);
+grr_status grr_conv3x3_embed(const float* x, const float* wt, float* out, int B, int Cin, int M, int H, int W,
+                             void* stream);
+/* Its weight gradient gw[m,c,ky,kx] = sum_b sum_p g[b,m,p] x[b,c,clamp(p + (ky-1, kx-1))]: g [B,M,H,W] (16-B
+ * aligned), x [B,Cin,H,W] -> gw [M,Cin,3,3].  The clamped taps are gathered into [B, 9 Cin, P] in the
+ * workspace and reduced on grr_wgrad (fixed order, no atomics).  workspace:
+ * grr_conv3x3_embed_bwd_w_workspace_bytes(B, Cin, M, H, W) bytes, 256-B aligned. */
+int64_t grr_conv3x3_embed_bwd_w_workspace_bytes(int B, int Cin, int M, int H, int W);
+grr_status grr_conv3x3_embed_bwd_w(const float* g, const float* x, float* gw, void* workspace, int B, int Cin, int M,
+                                   int H, int W, void* stream);
+/* Its data gradient (the adjoint of the clamped gather, as a gather): g [B,M,H,W], wt [M,Cin,3,3] ->
+ * gx [B,Cin,H,W]. */
+grr_status grr_conv3x3_embed_bwd_x(const float* g, const float* wt, float* gx, int B, int Cin, int M, int H, int W,
+                                   void* stream);
+
+/* Upsampling (REF:1019-1025): nn.ConvTranspose2d(K, M, 2, stride=2, bias=False).  x [B,K,H,W], wt [K,M,2,2] ->
+ * out [B,M,2H,2W] (8-B aligned): the 1x1 GEMM with the 4M rows (m, di, dj) on the split-bf16 kernels of
+ * grr_conv1x1_ws (K <= 4096), then a 2x2 interleave.  workspace: grr_convt2x2s2_workspace_bytes(B, K, M, H, W)
+ * bytes, 256-B aligned (the packed weights and the [B, 4M, H, W] GEMM output). */
+int64_t grr_convt2x2s2_workspace_bytes(int B, int K, int M, int H, int W);
+grr_status grr_convt2x2s2(const float* x, const float* wt, float* out, void* workspace, int B, int K, int M, int H,
+                          int W, void* stream);
+
+/* The decoder's combine (REF:1150-1160): nn.Conv2d(Ka + Kb, M, 1, bias=False) on cat([xa, xb], 1) without
+ * materialising the concatenation.  xa [B,Ka,P], xb [B,Kb,P], wt [M,Ka+Kb] -> out [B,M,P].  The GEMM's
+ * B-operand loader takes each 16-row k-step from xa or xb, so Ka % 16 == 0 is required
+ * (grr_conv1x1_cat2_supported; also Ka + Kb <= 4096 and the 32-bit lane offsets (Ka + Kb + 16) P < 2^30,
+ * (M + 128) P < 2^30); the summation order is grr_conv1x1_ws's on the concatenated tensor and the result is
+ * bitwise equal to it.  workspace: grr_conv1x1_cat2_workspace_bytes(Ka, Kb, M) bytes, 256-B aligned. */
+int grr_conv1x1_cat2_supported(int Ka, int Kb, int M, int64_t P);
+int64_t grr_conv1x1_cat2_workspace_bytes(int Ka, int Kb, int M);
+grr_status grr_conv1x1_cat2(const float* xa, const float* xb, const float* wt, float* out, void* workspace, int B,
+                            int Ka, int Kb, int M, int64_t P, void* stream);
+
 /* FeedForward block of the window models' feature CNN (FFBlock, REF7:13-67, nn.Conv2d bias=False):
  * out = skip[0] x + skip[1] W_out (gelu(d1) * d2), [d1; d2] = dwconv3x3_zero(W_in (ln_w * x / sigma)),
  * sigma = sqrt(var_c x (unbiased) + 1e-5).  x, out [B,C,H,W]; ln_w [C]; w_in [2 hid, C]; w_dw [2 hid, 9];
