@@ -122,7 +122,11 @@ __global__ __launch_bounds__(CD_NT) void embed_patches_kernel(const float* __res
 
 // gx[b][c][q] = sum_m sum_(ky,kx) sum_{p : clamp(p + (ky - 1, kx - 1)) = q} g[b][m][p] wt[m][c][ky][kx].
 // The candidates p lie in q's 3x3 neighbourhood; bit j of ym[ky] says that row qy - 1 + j reaches row qy
-// through tap row ky (xm likewise); one fmaf chain in (m, ky, kx, j, i) order.
+// through tap row ky (xm likewise); one fma chain in (m, ky, kx, j, i) order, accumulated in fp64 (each
+// product of two floats is exact there) and rounded once: a single fp32 accumulator over the up to 81 M
+// terms of a small image drifted past the fp32-class bound of a blocked CPU reduction (1.18e-6 against
+// 1.02e-6 at M = 128 on a 2 x 2 image, tests/test_gpu_gemm_class.py).  Off the training path, so the fp64
+// rate does not matter.
 __global__ __launch_bounds__(CD_NT) void embed_bwd_x_kernel(const float* __restrict__ g, const float* __restrict__ wt,
                                                             float* __restrict__ gx, int Cin, int M, int H, int W,
                                                             int64_t n) {
@@ -143,7 +147,7 @@ __global__ __launch_bounds__(CD_NT) void embed_bwd_x_kernel(const float* __restr
         if (px >= 0 && px < W && clampi(px + k - 1, 0, W - 1) == qx) xm[k] |= 1 << j;
       }
     }
-    float acc = 0.f;
+    double acc = 0.0;
     for (int m = 0; m < M; ++m) {
       const float* gp = g + (b * M + m) * HW;
       const float* wm = wt + ((int64_t)m * Cin + c) * 9;
@@ -162,10 +166,10 @@ __global__ __launch_bounds__(CD_NT) void embed_bwd_x_kernel(const float* __restr
           for (int j = 0; j < 3; ++j)
 #pragma unroll
             for (int k = 0; k < 3; ++k)
-              if ((ym[ky] >> j & 1) && (xm[kx] >> k & 1)) acc = __builtin_fmaf(nb[j][k], w, acc);
+              if ((ym[ky] >> j & 1) && (xm[kx] >> k & 1)) acc = __builtin_fma((double)nb[j][k], (double)w, acc);
         }
     }
-    gx[i] = acc;
+    gx[i] = (float)acc;
   }
 }
 

@@ -217,8 +217,10 @@ static grr_status launch_gemm(GemmArgs a, int B, hipStream_t s, const char* name
   const uint64_t n = (uint64_t)B * a.mt * a.nt;
   GRR_REQUIRE(n < (1ull << 31), GRR_ERR_UNSUPPORTED, "%s: grid too large", name);
   a.nblk = (uint32_t)n;
-  // 16-byte vector staging needs 4-aligned row strides (and base pointers, which torch provides)
-  const bool vec = (a.K % 4 == 0) && (a.P % 4 == 0) && ((uintptr_t)a.x % 16 == 0) && ((uintptr_t)a.wt % 16 == 0);
+  // 16-byte vector staging and the epilogue's 16-byte stores (and residual loads) need 4-aligned row
+  // strides and 16-byte aligned base pointers (torch's allocations are; a view at an odd offset is not)
+  const bool vec = (a.K % 4 == 0) && (a.P % 4 == 0) && ((uintptr_t)a.x % 16 == 0) && ((uintptr_t)a.wt % 16 == 0) &&
+                   ((uintptr_t)a.out % 16 == 0) && (EPI != EP_SKIP || (uintptr_t)a.res % 16 == 0);
   if (vec) hipLaunchKernelGGL((gemm_f32_kernel<LOADER, EPI, true>), dim3(a.nblk), dim3(GT), 0, s, a);
   else hipLaunchKernelGGL((gemm_f32_kernel<LOADER, EPI, false>), dim3(a.nblk), dim3(GT), 0, s, a);
   return launch_status(name);

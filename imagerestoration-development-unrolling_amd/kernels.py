@@ -23,6 +23,12 @@ def _ptr(t: Optional[Tensor]):
     return None if t is None else t.data_ptr()
 
 
+def _aligned16(t: Tensor) -> Tensor:
+    """t, or a copy of it in a fresh allocation where its data pointer is not 16-byte aligned (torch's
+    allocations are; a contiguous view at a storage offset that is no multiple of 4 floats is not)."""
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
 def _check(name: str, *ts: Optional[Tensor]) -> torch.device:
     dev = None
     for t in ts:
@@ -683,6 +689,7 @@ def conv3x3_embed_bwd_w(g: Tensor, x: Tensor) -> Tensor:
     m = g.shape[1]
     if not conv3x3_embed_ok(cin, m) or min(b, h, w) < 1:
         raise ValueError(f"conv3x3_embed_bwd_w: Cin={cin}, M={m} outside the kernel's range (Cin <= 4, M <= 128)")
+    g = _aligned16(g)   # grr_wgrad's 16-byte row loads; x is read by the scalar patch gather
     gw = torch.empty((m, cin, 3, 3), dtype=torch.float32, device=dev)
     ws = _ws(_native.load().grr_conv3x3_embed_bwd_w_workspace_bytes(b, cin, m, h, w), dev)
     _launch("conv3x3_embed_bwd_w", 4 * b * h * w * (m + cin + 18 * cin), "grr_conv3x3_embed_bwd_w", g.data_ptr(),
@@ -769,8 +776,11 @@ def ffn_forward(x: Tensor, ln_w: Tensor, w_in: Tensor, w_dw: Tensor, w_out: Tens
 def wgrad(a: Tensor, bop: Tensor) -> Tensor:
     """Weight gradient out[m, k] = sum_b sum_p a[b, m, p] bop[b, k, p] (grr_wgrad): a [B, M, ...],
     bop [B, K, ...] with the same trailing pixel extent.  The reverse of a 1x1 conv / LNB GEMM's
-    weight (REF:556-612 under autograd) without a library GEMM: fp32 MFMA, fixed summation order."""
+    weight (REF:556-612 under autograd) without a library GEMM: split-bf16 MFMA (three exact bf16 terms per
+    operand, six products accumulated in fp32: fp32-accurate), fixed summation order.  grr_wgrad wants 16-byte
+    aligned operands; a contiguous view that is not (a batch slice at an odd offset) is copied first."""
     dev = _check("wgrad", a, bop)
+    a, bop = _aligned16(a), _aligned16(bop)
     b, m = a.shape[:2]
     k = bop.shape[1]
     p = a.numel() // (b * m)

@@ -432,7 +432,7 @@ def mixture_solve(mod, y: Tensor, f0: Tensor, f1: Tensor) -> Tensor:
 
 # ---- feature convolutions ----------------------------------------------------
 # nn.Conv2d(K, M, 1, bias=False): forward and data gradient on the HIP GEMM; the weight gradient (a
-# reduction over B*H*W) is grr_wgrad (fp32 MFMA partial tiles per pixel chunk, added in a fixed order)
+# reduction over B*H*W) is grr_wgrad (split-bf16 MFMA partial tiles per pixel chunk, added in a fixed order)
 def _conv1x1_fwd(consts, x: Tensor, weight: Tensor):
     return [K.conv1x1(x.contiguous(), weight.contiguous())], []
 
@@ -465,15 +465,23 @@ def _conv2x2_bwd(consts, inputs, outs, saved, gouts, needs):
     g = gouts[0].contiguous()
     b, k, h, w = x.shape
     m = weight.shape[0]
+    # the forward drops an odd last row / column: the reverse runs on the even crop, and the dropped row /
+    # column gets a zero data gradient (the kernels below take even sizes only)
+    he, we = h // 2 * 2, w // 2 * 2
     gx = None
     if needs[0]:
-        # one 4K-row GEMM (split-bf16 for M <= 128, fp32 MFMA above) + interleave (W % 4 == 0)
-        if w % 4 == 0:
-            gx = K.conv2x2s2_bwd_data_gemm(g, weight.contiguous(), h, w)
+        # one 4K-row split-bf16 GEMM (gemm_x3 up to M = 128 channels of g, gemm_x3k above) + interleave
+        # (W % 4 == 0), else the direct kernel
+        if we % 4 == 0:
+            gx = K.conv2x2s2_bwd_data_gemm(g, weight.contiguous(), he, we)
         else:
-            gx = K.conv2x2s2_bwd_data(g, weight.contiguous(), h, w)
+            gx = K.conv2x2s2_bwd_data(g, weight.contiguous(), he, we)
+        if (he, we) != (h, w):
+            full = gx.new_zeros(b, k, h, w)
+            full[:, :, :he, :we] = gx
+            gx = full
     # patch rows in the weight's (k, dy, dx) order: [B, 4K, H/2 * W/2]
-    patches = x.reshape(b, k, h // 2, 2, w // 2, 2).permute(0, 1, 3, 5, 2, 4).reshape(b, k * 4, -1)
+    patches = x[:, :, :he, :we].reshape(b, k, he // 2, 2, we // 2, 2).permute(0, 1, 3, 5, 2, 4).reshape(b, k * 4, -1)
     gw = K.wgrad(g, patches)
     return gx, gw.view_as(weight)
 

@@ -1,8 +1,9 @@
 """grr_wgrad (the weight gradients of the feature CNN's convolutions and LNB GEMMs, REF:556-612 /
-REF13:564-575 under autograd) against a float64 CPU reduction.  fp32 products and sums in a fixed
-order: within fp32 rounding of the exact sum, normwise 1e-5 at these sizes (the reduction runs over up
-to 2^19 pixels; fp32 summation error grows like sqrt(n) eps); bitwise repeatable; ragged pixel
-counts, P % 4 != 0, row counts that are not multiples of the 128 x 96 tile."""
+REF13:564-575 under autograd) against a float64 CPU reduction.  Split-bf16 MFMA (each operand split exactly
+into three bf16 terms, six products accumulated in fp32) and sums in a fixed order: within fp32 rounding of
+the exact sum, normwise 1e-5 at these sizes (the reduction runs over up to 2^19 pixels; fp32 summation
+error grows like sqrt(n) eps); bitwise repeatable; ragged pixel counts, P % 4 != 0, row counts that are not
+multiples of the 128 x 96 tile.  (tests/test_gpu_gemm_class.py holds the same kernel to the fp32-class bound.)"""
 import pytest
 import torch
 
