@@ -6,6 +6,13 @@ packed cores, each output pixel once).
     python bench_tiled.py [--images 2] [--size 2048] [--tile 256] [--halo 32] [--micro-batch 64]
 
 Prints one JSON line: MPix/s of output image pixels (whole job), window overhead factor.
+
+    python bench_tiled.py --image-api [--size 2048] [--tile 256] [--halo 32] [--micro-batch 64] [--steps 3]
+
+compares, on one 8-bit size^2 RGB image and one GPU, (a) irdu_amd.restore_image with (b) the same windows
+through host /255 + permute + upload, tiling.tiled_forward, clamp x255 round uint8 + permute + download:
+wall time per image and torch.cuda.max_memory_allocated, the sides alternated and each run twice, then the
+mean HIP-event time of the gather and scatter launches beside the float4 copy.  One JSON line.
 """
 from __future__ import annotations
 
@@ -21,6 +28,77 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 
+def image_api(args):
+    """restore_image (a) against host conversion + tiled_forward + ATen quantisation (b), see the module text."""
+    import numpy as np
+    import irdu_amd
+    from irdu_amd import kernels, tiling
+    from bench import TRAINED, build_model, synthetic_patches
+    if args.gpus != 1:
+        raise SystemExit("--image-api is a single-process comparison (--gpus 1)")
+    dev = torch.device("cuda:0")
+    irdu_amd.load_native()
+    trained = os.path.exists(TRAINED)
+    model = build_model(dev, trained=trained)
+    _, noisy = synthetic_patches(1, seed=2204, h=args.size, w=args.size)
+    img = (noisy[0].clamp(0, 1) * 255).round().to(torch.uint8).permute(1, 2, 0).contiguous().numpy()    # HWC uint8
+
+    def side_a():
+        return irdu_amd.restore_image(model, img, factor=16, tile=args.tile, halo=args.halo,
+                                      micro_batch=args.micro_batch)
+
+    def side_b():
+        x = torch.from_numpy(img.astype(np.float32) / 255.0).permute(2, 0, 1).unsqueeze(0).to(dev)
+        y = tiling.tiled_forward(model, x, tile=args.tile, halo=args.halo, align=16, micro_batch=args.micro_batch)
+        return (y.clamp(0, 1) * 255).round().to(torch.uint8)[0].permute(1, 2, 0).cpu().numpy()
+
+    def measure(fn):
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            out = fn()
+        torch.cuda.synchronize()
+        return {"ms_per_image": round((time.perf_counter() - t0) / args.steps * 1e3, 2),
+                "max_memory_allocated_MiB": round(torch.cuda.max_memory_allocated() / 2 ** 20, 1)}, out
+
+    side_a(), side_b()                                           # warm-up
+    runs = {"restore_image": [], "tiled_forward_route": []}
+    for _ in range(2):                                           # alternated, each side twice
+        ra, out_a = measure(side_a)
+        rb, out_b = measure(side_b)
+        runs["restore_image"].append(ra)
+        runs["tiled_forward_route"].append(rb)
+    diff = np.abs(out_a.astype(np.int16) - out_b.astype(np.int16))
+    timer = kernels.LaunchTimer()
+    kernels.set_timer(timer)
+    for _ in range(args.steps):
+        side_a()
+    per_kernel = {k: {f: round(v[f], 4) for f in ("launches", "mean_ms", "bytes_per_launch", "gbps")}
+                  for k, v in timer.summary().items() if k in ("tile_gather", "tile_scatter")}
+    kernels.set_timer(None)
+    n = 64 * 3 * 256 * 256
+    src, dst = torch.rand(n, device=dev), torch.empty(n, device=dev)
+    kernels.stream_copy(src, dst)
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    for _ in range(20):
+        kernels.stream_copy(src, dst)
+    e.record()
+    torch.cuda.synchronize()
+    copy_ms = s.elapsed_time(e) / 20
+    print(json.dumps({"metric": "whole-image restoration, ms per image", "value": runs["restore_image"][-1]["ms_per_image"],
+                      "unit": "ms", "n_gpus": 1,
+                      "config": {"workload": f"{args.size}^2 RGB uint8, {args.tile}^2 windows, halo {args.halo}, "
+                                             f"micro-batch {args.micro_batch}, G=32 F=3 S=10 image filter",
+                                 "weights": "trained fixture" if trained else "reference init", "steps": args.steps},
+                      "runs": runs, "outputs": {"levels_differing": int((diff > 0).sum()), "max_level_diff": int(diff.max())},
+                      "per_kernel": per_kernel,
+                      "float4_copy": {"floats": n, "mean_ms": round(copy_ms, 4),
+                                      "gbps": round(8 * n / (copy_ms * 1e-3) / 1e9, 1)}}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=2)
@@ -32,7 +110,11 @@ def main():
     ap.add_argument("--gather", action="store_true")
     ap.add_argument("--gpus", type=int, default=1, help="ranks (one process per GPU; spawned when not under torchrun)")
     ap.add_argument("--dry-run", action="store_true", help="launcher check: ranks report and exit (no HIP)")
+    ap.add_argument("--image-api", action="store_true",
+                    help="compare restore_image with the tiled_forward route on one uint8 image (one GPU)")
     args = ap.parse_args()
+    if args.image_api:
+        return image_api(args)
     import benchlib
     world, rank, local = benchlib.join_or_spawn(args.gpus, dry_run=args.dry_run)
     if args.dry_run:

@@ -160,6 +160,11 @@ SIGNATURES = {
     "grr_win_bwd_gather_fused": [P, P, P, P, I, I, I, P, P, P, P, I, I, I, I, I, P],
     "grr_win_bwd_edge_weights": [P, L, P, P, P, P, I, P, L, P, I, I, I, I, I, P],
     "grr_win_bwd_mix": [P, P, P, P, P, I, I, I, I, I, P],
+    # whole-image restoration I/O (restore.py)
+    "grr_image_io_supported": [I, I, I],
+    "grr_tile_gather": [P, I, I, I, I, P, I, I, I, P, P],
+    "grr_tile_scatter": [P, P, I, I, I, P, I, I, I, I, P],
+    "grr_u8_sse": [P, P, L, P, P],
 }
 _RESTYPES = {"grr_version": c_int, "grr_last_error": ctypes.c_char_p, "grr_lnb_workspace_bytes": c_int64,
              "grr_conv1x1_workspace_bytes": c_int64, "grr_wgrad_workspace_bytes": c_int64,

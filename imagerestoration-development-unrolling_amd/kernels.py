@@ -1710,3 +1710,86 @@ def win_bwd_mix(gout: Tensor, x: Tensor, score: Tensor) -> Tuple[Tensor, Tensor]
             gout.data_ptr(), x.data_ptr(), score.data_ptr(), gx.data_ptr(), gscore.data_ptr(), b, g, c, h, w,
             _stream(dev))
     return gx, gscore
+
+
+# ---------------------------------------------------------------------------
+# whole-image restoration I/O (image_ops.hip; restore.py is the caller)
+IMAGE_DTYPES = (torch.uint8, torch.float32)
+
+
+def image_io_ok(c: int, h: int, w: int) -> bool:
+    """grr_image_io_supported in plain Python (tests/test_restore_abi.py checks the two agree): an H x W x C
+    image, or a window batch as (C, n th, tw), the image entry points take."""
+    return 1 <= c <= 4 and h >= 1 and w >= 1 and h * w * c < (1 << 31)
+
+
+def _check_image(name: str, img: Tensor) -> Tuple[int, int, int]:
+    """(H, W, C) of an HWC uint8 / float32 device image; ValueError before any launch otherwise."""
+    if not isinstance(img, Tensor) or img.dim() != 3:
+        raise ValueError(f"{name}: expected an H x W x C tensor, got {tuple(getattr(img, 'shape', ()))}")
+    if img.dtype not in IMAGE_DTYPES:
+        raise ValueError(f"{name}: image dtype must be uint8 or float32, got {img.dtype}")
+    h, w, c = img.shape
+    if not image_io_ok(c, h, w):
+        raise ValueError(f"{name}: needs an H x W x C image with C <= 4 and below 2^31 elements, got {tuple(img.shape)}")
+    if not img.is_cuda:
+        raise RuntimeError(f"{name}: tensors must be on the GPU (got {img.device}); the HIP engine has no CPU path")
+    return h, w, c
+
+
+def _check_table(name: str, table: Tensor, dev) -> int:
+    if table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != 6 or table.shape[0] < 1:
+        raise ValueError(f"{name}: the window table is int32 [n, 6] (wr, wc, r0, r1, c0, c1)")
+    if table.device != dev or not table.is_contiguous():
+        raise ValueError(f"{name}: the window table must be contiguous and on the image's device")
+    return table.shape[0]
+
+
+def tile_gather(img: Tensor, table: Tensor, th: int, tw: int) -> Tensor:
+    """Windows [n, C, th, tw] (float32, the model's input) of the HWC uint8 / float32 image reflect-padded at
+    the bottom and right; table: int32 [n, 6] device rows (wr, wc, r0, r1, c0, c1) of tiling.Window.  uint8
+    becomes float(v) / 255; float32 is copied bit for bit.  A non-contiguous image is copied first."""
+    h, w, c = _check_image("tile_gather", img)
+    n = _check_table("tile_gather", table, img.device)
+    if th < 1 or tw < 1 or not image_io_ok(c, n * th, tw):
+        raise ValueError(f"tile_gather: window batch {n} x {c} x {th} x {tw} must have 1..2^31-1 elements")
+    img = img.contiguous()
+    out = torch.empty((n, c, th, tw), dtype=torch.float32, device=img.device)
+    _launch("tile_gather", out.numel() * (img.element_size() + 4), "grr_tile_gather", img.data_ptr(),
+            int(img.dtype == torch.float32), h, w, c, table.data_ptr(), n, th, tw, out.data_ptr(), _stream(img.device))
+    return out
+
+
+def tile_scatter(y: Tensor, table: Tensor, img: Tensor, core_px: Optional[int] = None) -> None:
+    """Write each window's core box of y [n, C, th, tw], cut to the image, into the contiguous HWC image
+    (uint8: img_as_ubyte(clip(y, 0, 1)), NaN -> 0; float32: copy).  core_px: pixels written, for the timer's
+    byte count (default: all n th tw)."""
+    h, w, c = _check_image("tile_scatter", img)
+    if not img.is_contiguous():
+        raise ValueError("tile_scatter: the output image must be contiguous")
+    n = _check_table("tile_scatter", table, img.device)
+    _check("tile_scatter", y)
+    if y.dim() != 4 or y.shape[0] != n or y.shape[1] != c or y.device != img.device:
+        raise ValueError(f"tile_scatter: y {tuple(y.shape)} does not match {n} windows of {c} channels")
+    th, tw = y.shape[2], y.shape[3]
+    if not image_io_ok(c, n * th, tw):
+        raise ValueError(f"tile_scatter: window batch {tuple(y.shape)} must have 1..2^31-1 elements")
+    px = n * th * tw if core_px is None else core_px
+    _launch("tile_scatter", px * c * (4 + img.element_size()), "grr_tile_scatter", y.data_ptr(), table.data_ptr(), n,
+            th, tw, img.data_ptr(), int(img.dtype == torch.float32), h, w, c, _stream(img.device))
+
+
+def u8_sse(a: Tensor, b: Tensor) -> int:
+    """sum (a - b)^2 over two uint8 device tensors of one shape, exact (a Python int; synchronises)."""
+    for t in (a, b):
+        if not isinstance(t, Tensor) or t.dtype != torch.uint8:
+            raise ValueError(f"u8_sse: expected uint8 tensors, got {getattr(t, 'dtype', type(t))}")
+    if a.shape != b.shape or a.numel() < 1 or not image_io_ok(1, 1, a.numel()):
+        raise ValueError(f"u8_sse: shapes {tuple(a.shape)} / {tuple(b.shape)} must match, 1..2^31-1 elements")
+    if not (a.is_cuda and b.is_cuda and a.device == b.device):
+        raise RuntimeError("u8_sse: tensors must be on one GPU; the HIP engine has no CPU path")
+    a, b = a.contiguous(), b.contiguous()
+    out = torch.empty(1, dtype=torch.int64, device=a.device)
+    _launch("u8_sse", 2 * a.numel(), "grr_u8_sse", a.data_ptr(), b.data_ptr(), a.numel(), out.data_ptr(),
+            _stream(a.device))
+    return int(out.item())

@@ -1,0 +1,189 @@
+"""Whole-image restoration: an H x W x C picture of any size in, the restored picture out.
+
+The semantics are the reference's test loop as ``training.validate`` restates it (scripts_v2/...sigma25.py
+:249-279): reflect-pad the bottom and right to a multiple of ``factor`` (only a side that is not one
+already), filter, crop, clamp to [0, 1], quantise like ``img_as_ubyte``.  When the padded image exceeds
+``tile`` on a side it runs in overlap-save windows (``tiling.tile_grid`` on the padded size).
+
+The data movement around the model is three libgrr kernels (csrc/image_ops.hip), not ATen: the image goes
+to the device once in its own dtype (uint8 stays uint8); ``kernels.tile_gather`` reads it through the
+reflect rule straight into the model's planar float32 window batch; ``kernels.tile_scatter`` writes each
+window's core, cropped, clamped and quantised, into the HWC output.  No float32 copy of the whole image,
+padded or not, exists on either side of the model, and no per-window ATen op is issued.
+
+Defaults: ``tile`` 512, ``halo`` 64, ``micro_batch`` 16 (as many pixels per launch as config C5's 64 windows
+of 256^2).  The halo is set by the deepest model behind this call: the two-scale S = 10 image filter
+reproduces the whole image to fp32 rounding at 32 pixels already (tests/test_gpu_tiling.py), but the
+four-level v1.0 model does not -- measured on the GPU: 6.6e-4 relative and up to 6 uint8
+levels at halo 32, 3e-5 and at most one level at halo 64.  A 512 tile keeps the window overhead of halo 64
+where 256 / 32 has it ((512 / 384)^2 = 1.78).  Callers of the image filter alone may pass tile=256, halo=32.
+
+Single process: several ranks are ``tiling.tiled_forward``'s business.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Callable, List, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import kernels, tiling
+
+TILE, HALO, MICRO_BATCH = 512, 64, 16
+
+
+@dataclass(frozen=True)
+class RestorePlan:
+    """Padded size, window size and the windows (tiling.Window rows, in padded-image coordinates)."""
+    h: int
+    w: int
+    hp: int
+    wp: int
+    th: int
+    tw: int
+    windows: Tuple[tiling.Window, ...]
+
+
+def _padded(n: int, factor: int) -> int:
+    return n if n % factor == 0 else (n // factor + 1) * factor
+
+
+def plan(h: int, w: int, factor: int = 16, tile: int = TILE, halo: int = HALO) -> RestorePlan:
+    """The windows of an h x w image (pure Python): each side grows to the next multiple of ``factor`` only
+    if it is not one already, as in ``validate``; ValueError where torch's reflect pad would raise (a pad
+    not smaller than its side) and where ``tiling.tile_grid`` does."""
+    if factor < 1 or h < 1 or w < 1:
+        raise ValueError(f"plan: h, w, factor must be positive (got {h}, {w}, {factor})")
+    hp, wp = _padded(h, factor), _padded(w, factor)
+    for n, p in ((h, hp), (w, wp)):
+        if p - n >= n:
+            raise ValueError(f"plan: reflect padding {p - n} must be smaller than the image side {n} (factor {factor})")
+    wins = tiling.tile_grid(hp, wp, tile, halo, align=factor)
+    return RestorePlan(h, w, hp, wp, min(tile, hp), min(tile, wp), tuple(wins))
+
+
+def _checked_image(image) -> Tuple[torch.Tensor, str]:
+    """The HWC image as a tensor where it is, shape and dtype checked, and what came in ("numpy", "cpu" or
+    "cuda")."""
+    kind = "numpy" if isinstance(image, np.ndarray) else None
+    if kind:
+        if image.dtype not in (np.uint8, np.float32):
+            raise ValueError(f"restore_image: image dtype must be uint8 or float32, got {image.dtype}")
+        t = torch.from_numpy(np.ascontiguousarray(image))
+    elif isinstance(image, torch.Tensor):
+        t = image
+        kind = "cuda" if t.is_cuda else "cpu"
+    else:
+        raise ValueError(f"restore_image: expected a numpy array or a torch tensor, got {type(image).__name__}")
+    if t.dim() != 3 or t.dtype not in kernels.IMAGE_DTYPES or not kernels.image_io_ok(t.shape[2], t.shape[0], t.shape[1]):
+        raise ValueError("restore_image: expected an H x W x C image (C <= 4, below 2^31 elements) of uint8 or "
+                         f"float32, got {tuple(t.shape)} {t.dtype}")
+    return t, kind
+
+
+def _to_device(t: torch.Tensor, device) -> torch.Tensor:
+    """One transfer, in the image's own dtype."""
+    return (t if t.is_cuda and device is None else t.to(device if device is not None else "cuda")).contiguous()
+
+
+def _model_device(model):
+    params = getattr(model, "parameters", None)
+    if callable(params):
+        for p in params():
+            return p.device if p.is_cuda else None
+    return None
+
+
+def _core_px(p: RestorePlan, wins: Sequence[tiling.Window]) -> int:
+    return sum(max(0, min(r1, p.h) - r0) * max(0, min(c1, p.w) - c0) for _, _, r0, r1, c0, c1 in wins)
+
+
+def _restore_device(model: Callable, img: torch.Tensor, p: RestorePlan, micro_batch: int, quantise: bool) -> torch.Tensor:
+    """gather -> model -> scatter per micro-batch; img is the checked device image, the result is on its device."""
+    if micro_batch < 1:
+        raise ValueError(f"restore_image: micro_batch must be positive (got {micro_batch})")
+    table = torch.tensor(p.windows, dtype=torch.int32).to(img.device)     # uploaded once per image
+    was_training = bool(getattr(model, "training", False))
+    if was_training:
+        model.eval()
+    out = None
+    try:
+        with torch.no_grad():
+            for i in range(0, len(p.windows), micro_batch):
+                rows = table[i:i + micro_batch]
+                y = model(kernels.tile_gather(img, rows, p.th, p.tw))
+                if y.dim() != 4 or y.shape[0] != rows.shape[0] or tuple(y.shape[2:]) != (p.th, p.tw):
+                    raise ValueError(f"restore_image: the model returned {tuple(y.shape)} for {rows.shape[0]} "
+                                     f"windows of {p.th} x {p.tw}")
+                if out is None:     # every pixel is written exactly once (the cores partition the image): no fill
+                    out = torch.empty((p.h, p.w, y.shape[1]), dtype=torch.uint8 if quantise else torch.float32,
+                                      device=img.device)
+                kernels.tile_scatter(y.float().contiguous(), rows, out, _core_px(p, p.windows[i:i + micro_batch]))
+    finally:
+        if was_training:
+            model.train()
+    return out
+
+
+def restore_image(model: Callable, image, *, factor: int = 16, tile: int = TILE, halo: int = HALO,
+                  micro_batch: int = MICRO_BATCH, quantise: bool = True, device=None):
+    """Restore one H x W x C image (numpy array or torch tensor, uint8 or float32 in [0, 1], host or device)
+    with ``model``, any callable from float32 [n, C, th, tw] to [n, Cout, th, tw].
+
+    Returns the H x W x Cout image of the input's kind (numpy in, numpy out; a tensor comes back on the
+    input's device): uint8 with ``quantise`` (clamp, x255 in float32, round half to even -- validate()'s
+    lines, bit for bit), else float32, unclamped.  If the padded image fits ``tile`` on both sides there is
+    one window and the result is the whole-image one.  Runs under no_grad with the model in eval mode (its
+    mode is restored).  ``device``: where to run when the image is on the host (default: the model's
+    parameters' device, else the current GPU)."""
+    if device is None and not (isinstance(image, torch.Tensor) and image.is_cuda):
+        device = _model_device(model)
+    img, kind = _checked_image(image)
+    p = plan(img.shape[0], img.shape[1], factor, tile, halo)
+    out = _restore_device(model, _to_device(img, device), p, micro_batch, quantise)
+    if kind == "numpy":
+        return out.cpu().numpy()
+    return out.cpu() if kind == "cpu" else out
+
+
+def _as_device_u8(x, device) -> torch.Tensor:
+    t = torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+        raise ValueError(f"psnr_u8: expected uint8 images, got {getattr(t, 'dtype', type(t).__name__)}")
+    return t if t.is_cuda and device is None else t.to(device if device is not None else "cuda")
+
+
+def psnr_u8(a, b) -> float:
+    """PSNR of two uint8 images of one shape: 10 log10(255^2 N / SSE) in float64 from the exact integer SSE
+    (kernels.u8_sse), so it does not depend on any summation order; inf for equal images."""
+    dev = next((t.device for t in (a, b) if isinstance(t, torch.Tensor) and t.is_cuda), None)
+    ta, tb = _as_device_u8(a, dev), _as_device_u8(b, dev)
+    if ta.shape != tb.shape:
+        raise ValueError(f"psnr_u8: shapes differ ({tuple(ta.shape)} vs {tuple(tb.shape)})")
+    sse = kernels.u8_sse(ta, tb.to(ta.device))
+    return float("inf") if sse == 0 else float(10.0 * np.log10(255.0 ** 2 * ta.numel() / sse))
+
+
+def evaluate(model: Callable, images, sigma: float = 25.0, factor: int = 16, seed: int = 2204,
+             **tiling_args) -> Tuple[float, List[float]]:
+    """``training.validate``'s loop on restore_image: per image, N(0, sigma/255) noise drawn on the host from
+    one RandomState(seed) stream in image order, the noisy float image restored, PSNR against
+    rint(clean x 255).  Returns (mean PSNR, per-image PSNRs).  tiling_args: tile, halo, micro_batch, device."""
+    device = tiling_args.pop("device", None) or _model_device(model)
+    tile, halo = tiling_args.pop("tile", TILE), tiling_args.pop("halo", HALO)
+    micro_batch = tiling_args.pop("micro_batch", MICRO_BATCH)
+    if tiling_args:
+        raise TypeError(f"evaluate: unexpected arguments {sorted(tiling_args)}")
+    rs = np.random.RandomState(seed=seed)
+    psnrs = []
+    for i in range(len(images)):
+        clean = np.asarray(images[i], dtype=np.float32)
+        noisy = clean.copy()
+        noisy += rs.normal(0, sigma / 255.0, clean.shape)      # float32 += float64 draws, as validate
+        img, _ = _checked_image(noisy)
+        p = plan(img.shape[0], img.shape[1], factor, tile, halo)
+        restored = _restore_device(model, _to_device(img, device), p, micro_batch, True)
+        clean_u8 = np.rint(clean.astype(np.float64) * 255.0).astype(np.uint8)
+        psnrs.append(psnr_u8(restored, torch.from_numpy(clean_u8).to(restored.device)))
+    return float(np.mean(psnrs)), psnrs

@@ -707,6 +707,32 @@ grr_status grr_win_bwd_edge_weights(const float* feat, int64_t feat_bstride, con
 grr_status grr_win_bwd_mix(const float* gout, const float* x, const float* score, float* gx, float* gscore, int B,
                            int G, int Fs, int H, int W, void* stream);
 
+/* ---- whole-image restoration I/O (no reference counterpart: the reference's test loop pads, crops, clamps
+ * and quantises one float image on the host, scripts_v2 ...sigma25.py:249-279).  The image is H x W x C,
+ * interleaved (HWC) and contiguous, uint8 (img_f32 = 0, any byte address) or float32 (img_f32 = 1, 4-byte
+ * aligned); windows are the model's planar float32 batch [n, C, th, tw].  table: int32 [n, 6] on the
+ * device, rows (wr, wc, r0, r1, c0, c1) = a window's origin and its core box in the coordinates of the
+ * image padded at the bottom and right (tiling.Window).  Every index taken from the table is clamped into
+ * the image and the window, so a bad table gives wrong pixels, never an access outside the buffers. */
+
+/* 1 where the image entry points take an H x W x C image (or a batch of n windows as C, n th, tw): 1 <= C <= 4,
+ * H, W >= 1 and H W C < 2^31. */
+int grr_image_io_supported(int C, int H, int W);
+/* out[i, c, y, x] = padded(wr_i + y, wc_i + x, c): a padded row r >= H reads row 2(H-1) - r, a padded column
+ * likewise (nn.functional.pad(..., "reflect") at the bottom / right; the pad must be smaller than the side).
+ * uint8 converts as float(v) / 255.0f, correctly rounded; float32 is copied bit for bit. */
+grr_status grr_tile_gather(const void* img, int img_f32, int H, int W, int C, const int32_t* table, int n, int th,
+                           int tw, float* out, void* stream);
+/* img[r, c, :] = y[i, :, r - wr_i, c - wc_i] for (r, c) in window i's core box cut to [0, H) x [0, W): with cores
+ * that partition the padded image each pixel is written exactly once.  uint8: clamp to [0, 1], multiply by
+ * 255 in float32, round half to even, clip to [0, 255], cast (skimage's img_as_ubyte of the clamped value,
+ * REF test loop :278-279); NaN writes 0.  float32: unclamped copy. */
+grr_status grr_tile_scatter(const float* y, const int32_t* table, int n, int th, int tw, void* img, int img_f32, int H,
+                            int W, int C, void* stream);
+/* *out = sum_i (a[i] - b[i])^2 over n < 2^31 bytes, exact (integer) and the same on every run; out: one
+ * 8-byte aligned uint64 on the device, overwritten. */
+grr_status grr_u8_sse(const uint8_t* a, const uint8_t* b, int64_t n, uint64_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
