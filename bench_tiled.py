@@ -13,6 +13,17 @@ compares, on one 8-bit size^2 RGB image and one GPU, (a) irdu_amd.restore_image 
 through host /255 + permute + upload, tiling.tiled_forward, clamp x255 round uint8 + permute + download:
 wall time per image and torch.cuda.max_memory_allocated, the sides alternated and each run twice, then the
 mean HIP-event time of the gather and scatter launches beside the float4 copy.  One JSON line.
+
+    python bench_tiled.py --image-list 68 [--image-list-size 321 481] [--yaml CONF.yaml] [--tile 256] [--halo 32]
+                          [--micro-batch 64]
+
+times, on one GPU, irdu_amd.evaluate over N synthetic 8-bit RGB images (half H x W, half W x H: CBSD68's two
+shapes by default) as the per-image loop (across_images=False) against shared window batches
+(across_images=True), same model, both sides synchronised, alternated, each twice.  The model is the image
+filter of the other modes, or --yaml's model: section with its initial weights.  One JSON line: seconds per
+list and images per second on each side, model calls on each side, whether restore_images' bytes equal the
+per-image restore_image's and whether the PSNRs are equal; and, since evaluate() draws its noise on the host
+inside the timed call, that draw's time and the two restore calls alone on the drawn images.
 """
 from __future__ import annotations
 
@@ -99,6 +110,96 @@ def image_api(args):
                                       "gbps": round(8 * n / (copy_ms * 1e-3) / 1e9, 1)}}), flush=True)
 
 
+def image_list(args):
+    """evaluate(across_images=False) against evaluate(across_images=True) on a list of images, see the module text."""
+    import numpy as np
+    import irdu_amd
+    from irdu_amd import training
+    from bench import TRAINED, build_model
+    if args.gpus != 1:
+        raise SystemExit("--image-list is a single-process comparison (--gpus 1)")
+    dev = torch.device("cuda:0")
+    irdu_amd.load_native()
+    if args.yaml:
+        torch.manual_seed(2204)
+        model = training.build_model(training.parse_options(args.yaml).get("model", {})).to(dev).eval()
+        what, weights = f"model: section of {os.path.basename(args.yaml)}", "initial"
+    else:
+        trained = os.path.exists(TRAINED)
+        model = build_model(dev, trained=trained)
+        what, weights = "G=32 F=3 S=10 image filter", "trained fixture" if trained else "reference init"
+    h, w = args.image_list_size
+    n = args.image_list
+    shapes = [(h, w) if i < (n + 1) // 2 else (w, h) for i in range(n)]
+    images = [training.synthetic_clean_patch(np.random.RandomState(68 * 7919 + i), sh, sw, 3)     # on the uint8 grid
+              for i, (sh, sw) in enumerate(shapes)]
+    tiling_args = dict(tile=args.tile, halo=args.halo, micro_batch=args.micro_batch)
+    calls = []
+    hook = model.register_forward_pre_hook(lambda mod, a: calls.append(int(a[0].shape[0])))
+
+    def run(across):
+        del calls[:]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        result = irdu_amd.evaluate(model, images, sigma=25.0, factor=16, seed=2204, across_images=across, **tiling_args)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, result, len(calls), max(calls)
+
+    # warm-up, and the byte comparison: the same noisy images through both calls.  evaluate() also draws the
+    # noise on the host, the same work on both sides: that time, and the two calls alone, are reported too
+    rs = np.random.RandomState(2204)
+    t0 = time.perf_counter()
+    noisy = []
+    for im in images:
+        x = im.copy()
+        x += rs.normal(0, 25.0 / 255.0, im.shape)
+        noisy.append(x)
+    noise_s = time.perf_counter() - t0
+
+    def restore_only(across):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        if across:
+            out = irdu_amd.restore_images(model, noisy, factor=16, **tiling_args)
+        else:
+            out = [irdu_amd.restore_image(model, x, factor=16, **tiling_args) for x in noisy]
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    _, one_by_one = restore_only(False)
+    _, together = restore_only(True)
+    byte_equal = all(np.array_equal(a, b) for a, b in zip(one_by_one, together))
+    differing = int(sum(int((a != b).sum()) for a, b in zip(one_by_one, together)))
+    restore_runs = {"loop": [], "across_images": []}
+    for _ in range(2):
+        restore_runs["loop"].append(round(restore_only(False)[0], 4))
+        restore_runs["across_images"].append(round(restore_only(True)[0], 4))
+    runs = {"loop": [], "across_images": []}
+    for _ in range(2):                                           # alternated, each side twice
+        t_loop, res_loop, calls_loop, max_loop = run(False)
+        t_across, res_across, calls_across, max_across = run(True)
+        runs["loop"].append(round(t_loop, 4))
+        runs["across_images"].append(round(t_across, 4))
+    hook.remove()
+    best = {k: min(v) for k, v in runs.items()}
+    print(json.dumps({"metric": "evaluate over an image list, seconds per list", "value": best["across_images"],
+                      "unit": "s", "n_gpus": 1,
+                      "config": {"workload": f"{n} RGB images, {(n + 1) // 2} of {h}x{w} and {n // 2} of {w}x{h}, sigma 25, "
+                                             f"tile {args.tile}, halo {args.halo}, micro-batch {args.micro_batch}",
+                                 "model": what, "weights": weights,
+                                 "native_convs": bool(irdu_amd.graph_filter.NATIVE_CONVS)},
+                      "seconds_per_list": runs,
+                      "images_per_s": {k: round(n / v, 2) for k, v in best.items()},
+                      "ms_per_image": {k: round(v / n * 1e3, 2) for k, v in best.items()},
+                      "host_noise_draw_s": round(noise_s, 4),
+                      "restore_only_seconds_per_list": restore_runs,
+                      "restore_only_ms_per_image": {k: round(min(v) / n * 1e3, 2) for k, v in restore_runs.items()},
+                      "model_calls": {"loop": calls_loop, "across_images": calls_across},
+                      "largest_batch": {"loop": max_loop, "across_images": max_across},
+                      "outputs_byte_equal": byte_equal, "bytes_differing": differing,
+                      "psnr_equal": res_loop == res_across, "mean_psnr": round(res_loop[0], 4)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=2)
@@ -112,9 +213,17 @@ def main():
     ap.add_argument("--dry-run", action="store_true", help="launcher check: ranks report and exit (no HIP)")
     ap.add_argument("--image-api", action="store_true",
                     help="compare restore_image with the tiled_forward route on one uint8 image (one GPU)")
+    ap.add_argument("--image-list", type=int, nargs="?", const=68, default=None, metavar="N",
+                    help="time evaluate() over N images as a per-image loop against shared window batches (one GPU)")
+    ap.add_argument("--image-list-size", type=int, nargs=2, default=[321, 481], metavar=("H", "W"))
+    ap.add_argument("--yaml", type=str, default=None, help="--image-list: build the model from this YAML's model: section")
     args = ap.parse_args()
     if args.image_api:
         return image_api(args)
+    if args.image_list is not None:
+        if args.image_list < 1:
+            raise SystemExit("--image-list needs at least one image")
+        return image_list(args)
     import benchlib
     world, rank, local = benchlib.join_or_spawn(args.gpus, dry_run=args.dry_run)
     if args.dry_run:

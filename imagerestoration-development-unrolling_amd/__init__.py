@@ -40,5 +40,6 @@ from . import window_graph_v1  # noqa: F401  (multiblock window denoiser of lib/
 from .training import miopen_training_defaults  # noqa: F401
 from . import restore  # noqa: F401  (whole-image restoration of 8-bit / float images of any size)
 from .restore import RestorePlan, evaluate, plan, psnr_u8, restore_image  # noqa: F401
+from .restore import ImagePack, pack_images, plan_images, restore_images  # noqa: F401  (lists of images)
 
 __version__ = "0.1.0"

@@ -165,6 +165,11 @@ SIGNATURES = {
     "grr_tile_gather": [P, I, I, I, I, P, I, I, I, P, P],
     "grr_tile_scatter": [P, P, I, I, I, P, I, I, I, I, P],
     "grr_u8_sse": [P, P, L, P, P],
+    # ... for a list of images in one arena (restore_images)
+    "grr_image_arena_supported": [I, I, L],
+    "grr_tiles_gather": [P, L, I, I, P, I, P, I, I, I, P, P],
+    "grr_tiles_scatter": [P, P, I, I, I, P, L, I, I, P, I, P],
+    "grr_u8_sse_segments": [P, P, L, P, I, P, P],
 }
 _RESTYPES = {"grr_version": c_int, "grr_last_error": ctypes.c_char_p, "grr_lnb_workspace_bytes": c_int64,
              "grr_conv1x1_workspace_bytes": c_int64, "grr_wgrad_workspace_bytes": c_int64,

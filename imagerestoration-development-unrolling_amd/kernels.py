@@ -7,7 +7,7 @@ tensor or a missing libgrr.so raises.
 """
 from __future__ import annotations
 
-from typing import Optional, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import os
 
@@ -1793,3 +1793,128 @@ def u8_sse(a: Tensor, b: Tensor) -> int:
     _launch("u8_sse", 2 * a.numel(), "grr_u8_sse", a.data_ptr(), b.data_ptr(), a.numel(), out.data_ptr(),
             _stream(a.device))
     return int(out.item())
+
+
+# ---------------------------------------------------------------------------
+# ... for a list of images in one arena (restore.restore_images).  ``pack`` is restore.ImagePack or anything
+# with its fields: ``arena`` (1-D uint8 / float32 device tensor, the HWC images back to back), ``table``
+# (device int64 [n_img, 3], rows (element offset, H, W)), ``host_table`` (the same rows as Python ints) and
+# ``c`` (channels, shared).  The kernels cannot trust device tables and clamp; the host copy is checked here.
+MAX_SSE_SEGMENTS = 65535      # grr_u8_sse_segments: one grid row per segment
+
+
+def image_arena_ok(c: int, n_img: int, arena_elems: int) -> bool:
+    """grr_image_arena_supported in plain Python (tests/test_restore_images_abi.py checks the two agree):
+    1 <= C <= 4, 1 <= n_img <= arena_elems < 2^62.  The arena may exceed 2^31 elements; each image may not
+    (image_io_ok, checked on the host table)."""
+    return 1 <= c <= 4 and 1 <= n_img <= arena_elems < (1 << 62)
+
+
+def _check_pack(name: str, pack) -> Tuple[int, int]:
+    """(n_img, C) of an image pack whose host table describes its arena; ValueError before any launch
+    otherwise, RuntimeError for CPU tensors."""
+    arena, table, host, c = (getattr(pack, f, None) for f in ("arena", "table", "host_table", "c"))
+    if not isinstance(arena, Tensor) or arena.dim() != 1 or arena.dtype not in IMAGE_DTYPES:
+        raise ValueError(f"{name}: the arena is a 1-D uint8 or float32 tensor, got "
+                         f"{tuple(getattr(arena, 'shape', ()))} {getattr(arena, 'dtype', type(arena).__name__)}")
+    if not isinstance(c, int) or host is None or not image_arena_ok(c, len(host), arena.numel()):
+        raise ValueError(f"{name}: needs C <= 4 and 1 <= images <= arena elements (got C {c}, "
+                         f"{0 if host is None else len(host)} images, {arena.numel()} elements)")
+    n_img = len(host)
+    if not isinstance(table, Tensor) or table.dtype != torch.int64 or tuple(table.shape) != (n_img, 3):
+        raise ValueError(f"{name}: the image table is int64 [{n_img}, 3] (element offset, H, W)")
+    end = 0
+    for i, row in enumerate(host):
+        off, h, w = (int(v) for v in row)
+        if not image_io_ok(c, h, w):
+            raise ValueError(f"{name}: image {i} needs H W C < 2^31 (got {h} x {w} x {c})")
+        if off < end:
+            raise ValueError(f"{name}: image {i} starts at element {off}, before image {i - 1} ends ({end}): offsets "
+                             "must be non-negative and increasing")
+        end = off + h * w * c
+        if end > arena.numel():
+            raise ValueError(f"{name}: image {i} ends at element {end} of an arena of {arena.numel()}")
+    if not arena.is_cuda:
+        raise RuntimeError(f"{name}: tensors must be on the GPU (got {arena.device}); the HIP engine has no CPU path")
+    if table.device != arena.device or not table.is_contiguous() or not arena.is_contiguous():
+        raise ValueError(f"{name}: the arena and the image table must be contiguous and on one device")
+    return n_img, c
+
+
+def _check_table7(name: str, table: Tensor, dev) -> int:
+    if not isinstance(table, Tensor) or table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != 7 \
+            or table.shape[0] < 1:
+        raise ValueError(f"{name}: the window table is int32 [n, 7] (img, wr, wc, r0, r1, c0, c1)")
+    if table.device != dev or not table.is_contiguous():
+        raise ValueError(f"{name}: the window table must be contiguous and on the arena's device")
+    return table.shape[0]
+
+
+def tiles_gather(pack, table: Tensor, th: int, tw: int) -> Tensor:
+    """Windows [n, C, th, tw] (float32) of the images of ``pack``: row i of the int32 [n, 7] device table
+    (img, wr, wc, r0, r1, c0, c1) is read from image img with that image's own H and W in the reflect rule.
+    Element conversion as tile_gather."""
+    n_img, c = _check_pack("tiles_gather", pack)
+    n = _check_table7("tiles_gather", table, pack.arena.device)
+    if th < 1 or tw < 1 or not image_io_ok(c, n * th, tw):
+        raise ValueError(f"tiles_gather: window batch {n} x {c} x {th} x {tw} must have 1..2^31-1 elements")
+    arena = pack.arena
+    out = torch.empty((n, c, th, tw), dtype=torch.float32, device=arena.device)
+    _launch("tiles_gather", out.numel() * (arena.element_size() + 4), "grr_tiles_gather", arena.data_ptr(),
+            arena.numel(), int(arena.dtype == torch.float32), c, pack.table.data_ptr(), n_img, table.data_ptr(), n, th,
+            tw, out.data_ptr(), _stream(arena.device))
+    return out
+
+
+def tiles_scatter(y: Tensor, table: Tensor, pack_out, core_px: Optional[int] = None) -> None:
+    """Write each window's core box of y [n, C, th, tw], cut to its own image, into that image's span of
+    ``pack_out.arena`` (quantisation as tile_scatter).  core_px: pixels written, for the timer's byte count."""
+    n_img, c = _check_pack("tiles_scatter", pack_out)
+    arena = pack_out.arena
+    n = _check_table7("tiles_scatter", table, arena.device)
+    if not isinstance(y, Tensor) or y.dim() != 4 or y.shape[0] != n or y.shape[1] != c:
+        raise ValueError(f"tiles_scatter: y {tuple(getattr(y, 'shape', ()))} does not match {n} windows of {c} channels")
+    _check("tiles_scatter", y)
+    if y.device != arena.device:
+        raise ValueError("tiles_scatter: y must be on the arena's device")
+    th, tw = y.shape[2], y.shape[3]
+    if not image_io_ok(c, n * th, tw):
+        raise ValueError(f"tiles_scatter: window batch {tuple(y.shape)} must have 1..2^31-1 elements")
+    px = n * th * tw if core_px is None else core_px
+    _launch("tiles_scatter", px * c * (4 + arena.element_size()), "grr_tiles_scatter", y.data_ptr(), table.data_ptr(),
+            n, th, tw, arena.data_ptr(), arena.numel(), int(arena.dtype == torch.float32), c, pack_out.table.data_ptr(),
+            n_img, _stream(arena.device))
+
+
+def u8_sse_segments(a: Tensor, b: Tensor, offsets) -> List[int]:
+    """[sum (a - b)^2 over [offsets[i], offsets[i + 1]) for each i]: two 1-D uint8 device tensors of one
+    length, all segments in one launch, exact Python ints; one device-to-host copy of the sums (synchronises).
+    offsets: n_seg + 1 non-decreasing ints in [0, len(a)] (checked here and uploaded), or a device int64
+    tensor (which the kernel clamps)."""
+    for t in (a, b):
+        if not isinstance(t, Tensor) or t.dtype != torch.uint8 or t.dim() != 1:
+            raise ValueError(f"u8_sse_segments: expected 1-D uint8 tensors, got {getattr(t, 'dtype', type(t))}")
+    if a.shape != b.shape or a.numel() < 1:
+        raise ValueError(f"u8_sse_segments: lengths {tuple(a.shape)} / {tuple(b.shape)} must match and not be 0")
+    on_device = isinstance(offsets, Tensor) and offsets.is_cuda
+    if on_device:
+        if offsets.dtype != torch.int64 or offsets.dim() != 1 or not offsets.is_contiguous():
+            raise ValueError("u8_sse_segments: device offsets are a contiguous 1-D int64 tensor")
+        n_seg = offsets.numel() - 1
+    else:
+        host = [int(v) for v in (offsets.tolist() if isinstance(offsets, Tensor) else offsets)]
+        n_seg = len(host) - 1
+        if any(y < x for x, y in zip([0] + host, host + [a.numel()])):
+            raise ValueError(f"u8_sse_segments: offsets must be non-decreasing within [0, {a.numel()}]")
+    if not 1 <= n_seg <= MAX_SSE_SEGMENTS:
+        raise ValueError(f"u8_sse_segments: 1..{MAX_SSE_SEGMENTS} segments per call (got {n_seg})")
+    if not (a.is_cuda and b.is_cuda and a.device == b.device):
+        raise RuntimeError("u8_sse_segments: tensors must be on one GPU; the HIP engine has no CPU path")
+    if on_device and offsets.device != a.device:
+        raise ValueError("u8_sse_segments: the offsets must be on the arrays' device")
+    a, b = a.contiguous(), b.contiguous()
+    offs = offsets if on_device else torch.tensor(host, dtype=torch.int64).to(a.device)
+    out = torch.empty(n_seg, dtype=torch.int64, device=a.device)
+    _launch("u8_sse_segments", 2 * a.numel(), "grr_u8_sse_segments", a.data_ptr(), b.data_ptr(), a.numel(),
+            offs.data_ptr(), n_seg, out.data_ptr(), _stream(a.device))
+    return [int(v) for v in out.tolist()]

@@ -18,6 +18,11 @@ four-level v1.0 model does not -- measured on the GPU: 6.6e-4 r
 levels at halo 32, 3e-5 and at most one level at halo 64.  A 512 tile keeps the window overhead of halo 64
 where 256 / 32 has it ((512 / 384)^2 = 1.78).  Callers of the image filter alone may pass tile=256, halo=32.
 
+A list of images (``restore_images``, ``evaluate(across_images=True)``) shares window batches: the images
+lie back to back in one arena (``pack_images``), ``plan_images`` groups the windows of all images by window
+shape into launches of one restore_image launch's pixel budget, and ``kernels.tiles_gather`` /
+``tiles_scatter`` / ``u8_sse_segments`` address each window's own image through a device image table.
+
 Single process: several ranks are ``tiling.tiled_forward``'s business.
 """
 from __future__ import annotations
@@ -147,6 +152,163 @@ def restore_image(model: Callable, image, *, factor: int = 16, tile: int = TILE,
     return out.cpu() if kind == "cpu" else out
 
 
+# ---------------------------------------------------------------------------
+# a list of images in shared window batches
+@dataclass(frozen=True)
+class ImagePack:
+    """The images of one call in one arena: ``arena`` is a 1-D tensor of the images' own dtype, the HWC images
+    back to back with no padding (a uint8 image may start at any byte); ``table`` the device int64 [n, 3] rows
+    (element offset, H, W) the kernels read; ``host_table`` the same rows as Python ints, which the wrappers
+    check before a launch; ``c`` the channels all images share; ``kinds`` what each image came in as ("numpy",
+    "cpu", or its GPU device)."""
+    arena: torch.Tensor
+    table: torch.Tensor
+    host_table: Tuple[Tuple[int, int, int], ...]
+    c: int
+    kinds: Tuple = ()
+
+    def __len__(self) -> int:
+        return len(self.host_table)
+
+    def shapes(self) -> List[Tuple[int, int]]:
+        return [(h, w) for _, h, w in self.host_table]
+
+    def image(self, i: int) -> torch.Tensor:
+        """Image i as an H x W x C view of the arena."""
+        off, h, w = self.host_table[i]
+        return self.arena[off:off + h * w * self.c].view(h, w, self.c)
+
+
+def _host_table(shapes: Sequence[Tuple[int, int]], c: int) -> Tuple[Tuple[Tuple[int, int, int], ...], int]:
+    rows, off = [], 0
+    for h, w in shapes:
+        rows.append((off, int(h), int(w)))
+        off += int(h) * int(w) * c
+    return tuple(rows), off
+
+
+def pack_images(images: Sequence, device=None) -> ImagePack:
+    """Pack H x W x C images (numpy arrays or tensors, possibly of different sizes; one dtype, uint8 or float32,
+    and one C) into one arena on ``device`` (default: the first device image's, else the current GPU).  Host
+    images are concatenated once on the host and sent in one transfer; device images are copied device to
+    device.  ValueError names the offending index."""
+    if len(images) < 1:
+        raise ValueError("pack_images: no images")
+    ts, kinds = [], []
+    for i, image in enumerate(images):
+        try:
+            t, kind = _checked_image(image)
+        except ValueError as e:
+            raise ValueError(f"pack_images: image {i}: {e}") from None
+        if ts and (t.dtype != ts[0].dtype or t.shape[2] != ts[0].shape[2]):
+            raise ValueError(f"pack_images: image {i} is {t.dtype} with {t.shape[2]} channel(s); image 0 is "
+                             f"{ts[0].dtype} with {ts[0].shape[2]}: one dtype and one C per call")
+        ts.append(t)
+        kinds.append(t.device if kind == "cuda" else kind)
+    if device is None:
+        device = next((t.device for t in ts if t.is_cuda), "cuda")
+    device = torch.device(device)
+    c = int(ts[0].shape[2])
+    host_table, total = _host_table([(t.shape[0], t.shape[1]) for t in ts], c)
+    on_host = [i for i, t in enumerate(ts) if not t.is_cuda]
+    staged = torch.cat([ts[i].reshape(-1) for i in on_host]).to(device) if on_host else None     # one transfer
+    if len(on_host) == len(ts):
+        arena = staged
+    else:
+        arena = torch.empty(total, dtype=ts[0].dtype, device=device)
+        at = 0
+        for i, t in enumerate(ts):
+            off, n = host_table[i][0], t.numel()
+            if t.is_cuda:
+                arena[off:off + n].view(t.shape).copy_(t)
+            else:
+                arena[off:off + n].copy_(staged[at:at + n])
+                at += n
+    table = torch.tensor(host_table, dtype=torch.int64).to(device)
+    return ImagePack(arena, table, host_table, c, tuple(kinds))
+
+
+def plan_images(shapes: Sequence[Tuple[int, int]], factor: int = 16, tile: int = TILE, halo: int = HALO,
+                micro_batch: int = MICRO_BATCH) -> List[Tuple[int, int, Tuple[Tuple[int, ...], ...]]]:
+    """The launches of a list of (h, w) images (pure Python): ``plan`` per image, all windows grouped by window
+    shape (th, tw) in (image, window) order, each group cut into launches of at most
+    max(1, micro_batch tile^2 // (th tw)) windows -- the pixels one restore_image launch has, so the peak
+    memory does not grow.  Returns [(th, tw, rows)], rows (img, wr, wc, r0, r1, c0, c1).  ValueError where
+    ``plan`` raises."""
+    if micro_batch < 1:
+        raise ValueError(f"plan_images: micro_batch must be positive (got {micro_batch})")
+    groups = {}
+    for i, shape in enumerate(shapes):
+        p = plan(int(shape[0]), int(shape[1]), factor, tile, halo)
+        groups.setdefault((p.th, p.tw), []).extend((i,) + tuple(w) for w in p.windows)
+    launches = []
+    for (th, tw), rows in groups.items():
+        cap = max(1, (micro_batch * tile * tile) // (th * tw))
+        launches.extend((th, tw, tuple(rows[k:k + cap])) for k in range(0, len(rows), cap))
+    return launches
+
+
+def _rows_core_px(rows, shapes) -> int:
+    return sum(max(0, min(r1, shapes[i][0]) - r0) * max(0, min(c1, shapes[i][1]) - c0)
+               for i, _, _, r0, r1, c0, c1 in rows)
+
+
+def _restore_pack(model: Callable, pack: ImagePack, launches, quantise: bool) -> ImagePack:
+    """gather -> model -> scatter per launch of plan_images; the result is a pack of the same image shapes."""
+    dev, shapes = pack.arena.device, pack.shapes()
+    table = torch.tensor([r for _, _, rows in launches for r in rows], dtype=torch.int32).to(dev)  # one upload
+    was_training = bool(getattr(model, "training", False))
+    if was_training:
+        model.eval()
+    out, at = None, 0
+    try:
+        with torch.no_grad():
+            for th, tw, launch_rows in launches:
+                rows = table[at:at + len(launch_rows)]
+                at += len(launch_rows)
+                y = model(kernels.tiles_gather(pack, rows, th, tw))
+                if y.dim() != 4 or y.shape[0] != rows.shape[0] or tuple(y.shape[2:]) != (th, tw) \
+                        or (out is not None and y.shape[1] != out.c):
+                    raise ValueError(f"restore_images: the model returned {tuple(y.shape)} for {rows.shape[0]} "
+                                     f"windows of {th} x {tw}")
+                if out is None:     # every pixel of every image is written exactly once: no fill
+                    cout = int(y.shape[1])
+                    host_table, total = (pack.host_table, pack.arena.numel()) if cout == pack.c \
+                        else _host_table(shapes, cout)
+                    out = ImagePack(torch.empty(total, dtype=torch.uint8 if quantise else torch.float32, device=dev),
+                                    pack.table if cout == pack.c else torch.tensor(host_table, dtype=torch.int64).to(dev),
+                                    host_table, cout, pack.kinds)
+                kernels.tiles_scatter(y.float().contiguous(), rows, out, _rows_core_px(launch_rows, shapes))
+    finally:
+        if was_training:
+            model.train()
+    return out
+
+
+def restore_images(model: Callable, images: Sequence, *, factor: int = 16, tile: int = TILE, halo: int = HALO,
+                   micro_batch: int = MICRO_BATCH, quantise: bool = True, device=None) -> list:
+    """restore_image for a list of images of possibly different sizes (one dtype, one C), with windows of
+    different images sharing the model's batches: the images go to the device in one arena (pack_images), each
+    launch of plan_images is one gather, one model call and one scatter, and the results come back from one
+    output arena in input order and of each input's kind.  Equal to
+    ``[restore_image(model, im, ...) for im in images]`` byte for byte whenever the model's result for a
+    window does not depend on what else is in the batch."""
+    if device is None and not any(isinstance(im, torch.Tensor) and im.is_cuda for im in images):
+        device = _model_device(model)
+    pack = pack_images(images, device)
+    out = _restore_pack(model, pack, plan_images(pack.shapes(), factor, tile, halo, micro_batch), quantise)
+    host = out.arena.cpu() if any(isinstance(k, str) for k in out.kinds) else None      # one transfer back
+    results = []
+    for i, kind in enumerate(out.kinds):
+        if isinstance(kind, str):
+            off, h, w = out.host_table[i]
+            t = host[off:off + h * w * out.c].view(h, w, out.c)
+            results.append(t.numpy() if kind == "numpy" else t)
+        else:
+            results.append(out.image(i).to(kind))
+    return results
+
+
 def _as_device_u8(x, device) -> torch.Tensor:
     t = torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x
     if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
@@ -166,16 +328,22 @@ def psnr_u8(a, b) -> float:
 
 
 def evaluate(model: Callable, images, sigma: float = 25.0, factor: int = 16, seed: int = 2204,
-             **tiling_args) -> Tuple[float, List[float]]:
+             across_images: bool = False, **tiling_args) -> Tuple[float, List[float]]:
     """``training.validate``'s loop on restore_image: per image, N(0, sigma/255) noise drawn on the host from
     one RandomState(seed) stream in image order, the noisy float image restored, PSNR against
-    rint(clean x 255).  Returns (mean PSNR, per-image PSNRs).  tiling_args: tile, halo, micro_batch, device."""
+    rint(clean x 255).  Returns (mean PSNR, per-image PSNRs).  tiling_args: tile, halo, micro_batch, device.
+
+    ``across_images``: draw the noise for all images first (the same stream, so the same draws), restore them
+    with restore_images in shared window batches and take every image's SSE in one launch; the same floats
+    for a batch-independent model."""
     device = tiling_args.pop("device", None) or _model_device(model)
     tile, halo = tiling_args.pop("tile", TILE), tiling_args.pop("halo", HALO)
     micro_batch = tiling_args.pop("micro_batch", MICRO_BATCH)
     if tiling_args:
         raise TypeError(f"evaluate: unexpected arguments {sorted(tiling_args)}")
     rs = np.random.RandomState(seed=seed)
+    if across_images:
+        return _evaluate_across(model, images, sigma, factor, rs, tile, halo, micro_batch, device)
     psnrs = []
     for i in range(len(images)):
         clean = np.asarray(images[i], dtype=np.float32)
@@ -186,4 +354,26 @@ def evaluate(model: Callable, images, sigma: float = 25.0, factor: int = 16, see
         restored = _restore_device(model, _to_device(img, device), p, micro_batch, True)
         clean_u8 = np.rint(clean.astype(np.float64) * 255.0).astype(np.uint8)
         psnrs.append(psnr_u8(restored, torch.from_numpy(clean_u8).to(restored.device)))
+    return float(np.mean(psnrs)), psnrs
+
+
+def _evaluate_across(model, images, sigma, factor, rs, tile, halo, micro_batch, device) -> Tuple[float, List[float]]:
+    """evaluate(across_images=True): the same draws, the same uint8 images and the same integer SSEs as the
+    per-image loop, with the windows of all images in shared batches and one SSE launch."""
+    cleans = [np.asarray(images[i], dtype=np.float32) for i in range(len(images))]
+    noisy = []
+    for clean in cleans:                                         # all draws first, in image order
+        x = clean.copy()
+        x += rs.normal(0, sigma / 255.0, clean.shape)
+        noisy.append(x)
+    pack = pack_images(noisy, device)
+    restored = _restore_pack(model, pack, plan_images(pack.shapes(), factor, tile, halo, micro_batch), True)
+    clean_u8 = pack_images([np.rint(c.astype(np.float64) * 255.0).astype(np.uint8) for c in cleans],
+                           restored.arena.device)
+    if clean_u8.host_table != restored.host_table:
+        raise ValueError(f"evaluate: the model returns {restored.c} channel(s) for {clean_u8.c}; no PSNR")
+    offsets = [off for off, _, _ in restored.host_table] + [restored.arena.numel()]
+    sses = kernels.u8_sse_segments(restored.arena, clean_u8.arena, offsets)
+    psnrs = [float("inf") if sse == 0 else float(10.0 * np.log10(255.0 ** 2 * (h * w * restored.c) / sse))
+             for sse, (_, h, w) in zip(sses, restored.host_table)]
     return float(np.mean(psnrs)), psnrs

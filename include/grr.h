@@ -733,6 +733,36 @@ grr_status grr_tile_scatter(const float* y, const int32_t* table, int n, int th,
  * 8-byte aligned uint64 on the device, overwritten. */
 grr_status grr_u8_sse(const uint8_t* a, const uint8_t* b, int64_t n, uint64_t* out, void* stream);
 
+/* ---- the same for a list of images that share window batches (restore_images).  The images of one call lie in
+ * one arena: a contiguous device buffer of arena_elems elements of their own dtype (uint8, any byte address, or
+ * float32, 4-byte aligned), HWC each, packed back to back with no padding, so a uint8 image may start at any
+ * byte.  img_table: int64 [n_img, 3] on the device, 8-byte aligned, rows (element offset, H, W); all images of a
+ * call share C.  table: int32 [n, 7] on the device, rows (img, wr, wc, r0, r1, c0, c1): the image's index, then
+ * the window row of the single-image calls in that image's padded coordinates.  Both tables are device data the
+ * host cannot see: the image index is clamped into [0, n_img), H and W into [1, 2^31), and every element index
+ * derived from them is kept inside [0, arena_elems) -- reads are clamped, writes outside are dropped -- so bad
+ * tables give wrong pixels, never an access outside the arena and the window batch. */
+
+/* 1 where the arena entry points take the call: 1 <= C <= 4, 1 <= n_img <= arena_elems (an image has at least
+ * one element) and arena_elems < 2^62 (64-bit offsets: the arena may exceed 2^31 elements).  Per image,
+ * H W C < 2^31 (grr_image_io_supported) is the caller's to keep: it is device data here.  The window batch is
+ * bounded as in the single-image calls (n th tw C < 2^31). */
+int grr_image_arena_supported(int C, int n_img, int64_t arena_elems);
+/* grr_tile_gather for window i of image table[i][0]: that image's own H and W in the reflect rule, the same
+ * element conversion. */
+grr_status grr_tiles_gather(const void* arena, int64_t arena_elems, int img_f32, int C, const int64_t* img_table,
+                            int n_img, const int32_t* table, int n, int th, int tw, float* out, void* stream);
+/* grr_tile_scatter of each window's core box, cut to its own image's H x W, into that image's span of the
+ * arena; the same quantisation. */
+grr_status grr_tiles_scatter(const float* y, const int32_t* table, int n, int th, int tw, void* arena, int64_t arena_elems,
+                             int img_f32, int C, const int64_t* img_table, int n_img, void* stream);
+/* out[i] = sum (a[j] - b[j])^2 over j in [offsets[i], offsets[i + 1]), i < n_seg, in one launch: exact 64-bit
+ * integers, the same on every run.  offsets: int64 [n_seg + 1] on the device, 8-byte aligned, clamped into
+ * [0, total] and made monotone by the kernel; segments may start at any byte.  out: n_seg 8-byte aligned
+ * uint64 on the device, overwritten.  n_seg <= 65535 (one grid row per segment), else GRR_ERR_UNSUPPORTED. */
+grr_status grr_u8_sse_segments(const uint8_t* a, const uint8_t* b, int64_t total, const int64_t* offsets, int n_seg,
+                               uint64_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,14 +1,17 @@
 """Restore image files with a trained model (irdu_amd.restore; single process, one GPU).
 
     python restore.py -yaml_path CONF.yaml --ckpt CHECKPOINT.pt --input FILE_OR_DIR --output DIR \\
-           [--sigma S --seed N] [--tile T --halo H --factor F]
+           [--sigma S --seed N] [--tile T --halo H --factor F] [--batch-images]
 
 The model is ``training.build_model(conf["model"])``; the checkpoint is the training loop's dict (its
 "model" entry).  Without --ckpt the initial weights run, and the tool says so.  Images of any size are read
 and written with PIL.  With --sigma each input is taken as clean: N(0, sigma/255) noise is drawn on the host
 from one RandomState(seed) stream in file order (as ``irdu_amd.evaluate`` and ``training.validate`` do), the
 noisy image is restored and its PSNR against the input printed, with the mean at the end.  Without --sigma
-the input is restored as it is.
+the input is restored as it is.  With --batch-images all inputs are read first and restored by
+``irdu_amd.restore_images``, windows of different files sharing the model's batches (files of one mode, all
+RGB or all grey); the noise is still drawn in file order, and the lines printed and the files written are
+the same.
 """
 import argparse
 import os
@@ -41,6 +44,8 @@ def main(argv=None) -> None:
     ap.add_argument("--tile", type=int, default=None)
     ap.add_argument("--halo", type=int, default=None)
     ap.add_argument("--factor", type=int, default=16)
+    ap.add_argument("--batch-images", action="store_true",
+                    help="read all inputs first and restore them in shared window batches (restore_images)")
     args = ap.parse_args(argv)
 
     import numpy as np
@@ -66,26 +71,44 @@ def main(argv=None) -> None:
     os.makedirs(args.output, exist_ok=True)
     rs = np.random.RandomState(seed=args.seed)
     psnrs = []
-    for path in files:
+
+    def read(path):
         img = np.array(Image.open(path))
         if img.dtype != np.uint8:
             raise SystemExit(f"{path}: only 8-bit images are supported (got {img.dtype})")
-        gray = img.ndim == 2
-        if gray:
-            img = img[:, :, None]
+        return img[:, :, None] if img.ndim == 2 else img
+
+    def noisy_of(img):
+        noisy = img.astype(np.float32) / 255.0
+        noisy += rs.normal(0, args.sigma / 255.0, noisy.shape)
+        return noisy
+
+    def finish(path, img, out):
         out_path = os.path.join(args.output, os.path.splitext(os.path.basename(path))[0] + ".png")
         if args.sigma is None:
-            out = irdu_amd.restore_image(model, img, factor=args.factor, tile=tile, halo=halo)
             print(f"{path} -> {out_path}  {img.shape[0]}x{img.shape[1]}x{img.shape[2]}")
         else:
-            noisy = img.astype(np.float32) / 255.0
-            noisy += rs.normal(0, args.sigma / 255.0, noisy.shape)
-            out = irdu_amd.restore_image(model, noisy, factor=args.factor, tile=tile, halo=halo)
             if out.shape != img.shape:
                 raise SystemExit(f"{path}: the model returns {out.shape[2]} channels for {img.shape[2]}; no PSNR")
             psnrs.append(irdu_amd.psnr_u8(out, img))
             print(f"{path} -> {out_path}  sigma {args.sigma:g}  PSNR {psnrs[-1]:.4f} dB")
         Image.fromarray(out[:, :, 0] if out.shape[2] == 1 else out).save(out_path)
+
+    if args.batch_images:
+        imgs = [read(path) for path in files]
+        inputs = imgs if args.sigma is None else [noisy_of(img) for img in imgs]       # draws in file order
+        try:
+            outs = irdu_amd.restore_images(model, inputs, factor=args.factor, tile=tile, halo=halo)
+        except ValueError as e:
+            raise SystemExit(f"--batch-images: {e}")
+        for path, img, out in zip(files, imgs, outs):
+            finish(path, img, out)
+    else:
+        for path in files:
+            img = read(path)
+            out = irdu_amd.restore_image(model, img if args.sigma is None else noisy_of(img), factor=args.factor,
+                                         tile=tile, halo=halo)
+            finish(path, img, out)
     if psnrs:
         print(f"mean PSNR over {len(psnrs)} image(s): {float(np.mean(psnrs)):.4f} dB")
 
