@@ -1737,12 +1737,43 @@ def _check_image(name: str, img: Tensor) -> Tuple[int, int, int]:
     return h, w, c
 
 
-def _check_table(name: str, table: Tensor, dev) -> int:
-    if table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != 6 or table.shape[0] < 1:
-        raise ValueError(f"{name}: the window table is int32 [n, 6] (wr, wc, r0, r1, c0, c1)")
+_TABLE_ROWS = {6: "(wr, wc, r0, r1, c0, c1)", 7: "(img, wr, wc, r0, r1, c0, c1)"}
+
+
+def _check_table(name: str, table: Tensor, dev, cols: int, owner: str) -> int:
+    if not isinstance(table, Tensor) or table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != cols \
+            or table.shape[0] < 1:
+        raise ValueError(f"{name}: the window table is int32 [n, {cols}] {_TABLE_ROWS[cols]}")
     if table.device != dev or not table.is_contiguous():
-        raise ValueError(f"{name}: the window table must be contiguous and on the image's device")
+        raise ValueError(f"{name}: the window table must be contiguous and on the {owner}'s device")
     return table.shape[0]
+
+
+def _check_batch(name: str, n: int, c: int, th: int, tw: int) -> None:
+    """The window-batch bound of the four gather / scatter entry points: 1 <= n th tw C < 2^31."""
+    if th < 1 or tw < 1 or not image_io_ok(c, n * th, tw):
+        raise ValueError(f"{name}: window batch {n} x {c} x {th} x {tw} must have 1..2^31-1 elements")
+
+
+def _gather(kind: str, buf: Tensor, src_args: tuple, c: int, table: Tensor, th: int, tw: int) -> Tensor:
+    """tile_gather / tiles_gather after their own checks: ``buf`` is the image or the arena, ``src_args`` what
+    grr_<kind> takes in front of (table, n, th, tw, out, stream)."""
+    n = table.shape[0]
+    _check_batch(kind, n, c, th, tw)
+    out = torch.empty((n, c, th, tw), dtype=torch.float32, device=buf.device)
+    _launch(kind, out.numel() * (buf.element_size() + 4), "grr_" + kind, *src_args, table.data_ptr(), n, th, tw,
+            out.data_ptr(), _stream(buf.device))
+    return out
+
+
+def _scatter(kind: str, y: Tensor, table: Tensor, buf: Tensor, src_args: tuple, core_px: Optional[int]) -> None:
+    """tile_scatter / tiles_scatter after their own checks: ``src_args`` is what grr_<kind> takes between
+    (y, table, n, th, tw) and the stream."""
+    n, c, th, tw = y.shape
+    _check_batch(kind, n, c, th, tw)
+    px = n * th * tw if core_px is None else core_px
+    _launch(kind, px * c * (4 + buf.element_size()), "grr_" + kind, y.data_ptr(), table.data_ptr(), n, th, tw,
+            *src_args, _stream(buf.device))
 
 
 def tile_gather(img: Tensor, table: Tensor, th: int, tw: int) -> Tensor:
@@ -1750,14 +1781,9 @@ def tile_gather(img: Tensor, table: Tensor, th: int, tw: int) -> Tensor:
     the bottom and right; table: int32 [n, 6] device rows (wr, wc, r0, r1, c0, c1) of tiling.Window.  uint8
     becomes float(v) / 255; float32 is copied bit for bit.  A non-contiguous image is copied first."""
     h, w, c = _check_image("tile_gather", img)
-    n = _check_table("tile_gather", table, img.device)
-    if th < 1 or tw < 1 or not image_io_ok(c, n * th, tw):
-        raise ValueError(f"tile_gather: window batch {n} x {c} x {th} x {tw} must have 1..2^31-1 elements")
+    _check_table("tile_gather", table, img.device, 6, "image")
     img = img.contiguous()
-    out = torch.empty((n, c, th, tw), dtype=torch.float32, device=img.device)
-    _launch("tile_gather", out.numel() * (img.element_size() + 4), "grr_tile_gather", img.data_ptr(),
-            int(img.dtype == torch.float32), h, w, c, table.data_ptr(), n, th, tw, out.data_ptr(), _stream(img.device))
-    return out
+    return _gather("tile_gather", img, (img.data_ptr(), int(img.dtype == torch.float32), h, w, c), c, table, th, tw)
 
 
 def tile_scatter(y: Tensor, table: Tensor, img: Tensor, core_px: Optional[int] = None) -> None:
@@ -1767,16 +1793,11 @@ def tile_scatter(y: Tensor, table: Tensor, img: Tensor, core_px: Optional[int] =
     h, w, c = _check_image("tile_scatter", img)
     if not img.is_contiguous():
         raise ValueError("tile_scatter: the output image must be contiguous")
-    n = _check_table("tile_scatter", table, img.device)
+    n = _check_table("tile_scatter", table, img.device, 6, "image")
     _check("tile_scatter", y)
     if y.dim() != 4 or y.shape[0] != n or y.shape[1] != c or y.device != img.device:
         raise ValueError(f"tile_scatter: y {tuple(y.shape)} does not match {n} windows of {c} channels")
-    th, tw = y.shape[2], y.shape[3]
-    if not image_io_ok(c, n * th, tw):
-        raise ValueError(f"tile_scatter: window batch {tuple(y.shape)} must have 1..2^31-1 elements")
-    px = n * th * tw if core_px is None else core_px
-    _launch("tile_scatter", px * c * (4 + img.element_size()), "grr_tile_scatter", y.data_ptr(), table.data_ptr(), n,
-            th, tw, img.data_ptr(), int(img.dtype == torch.float32), h, w, c, _stream(img.device))
+    _scatter("tile_scatter", y, table, img, (img.data_ptr(), int(img.dtype == torch.float32), h, w, c), core_px)
 
 
 def u8_sse(a: Tensor, b: Tensor) -> int:
@@ -1841,13 +1862,9 @@ def _check_pack(name: str, pack) -> Tuple[int, int]:
     return n_img, c
 
 
-def _check_table7(name: str, table: Tensor, dev) -> int:
-    if not isinstance(table, Tensor) or table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != 7 \
-            or table.shape[0] < 1:
-        raise ValueError(f"{name}: the window table is int32 [n, 7] (img, wr, wc, r0, r1, c0, c1)")
-    if table.device != dev or not table.is_contiguous():
-        raise ValueError(f"{name}: the window table must be contiguous and on the arena's device")
-    return table.shape[0]
+def _arena_args(pack, n_img: int, c: int) -> tuple:
+    arena = pack.arena
+    return (arena.data_ptr(), arena.numel(), int(arena.dtype == torch.float32), c, pack.table.data_ptr(), n_img)
 
 
 def tiles_gather(pack, table: Tensor, th: int, tw: int) -> Tensor:
@@ -1855,15 +1872,8 @@ def tiles_gather(pack, table: Tensor, th: int, tw: int) -> Tensor:
     (img, wr, wc, r0, r1, c0, c1) is read from image img with that image's own H and W in the reflect rule.
     Element conversion as tile_gather."""
     n_img, c = _check_pack("tiles_gather", pack)
-    n = _check_table7("tiles_gather", table, pack.arena.device)
-    if th < 1 or tw < 1 or not image_io_ok(c, n * th, tw):
-        raise ValueError(f"tiles_gather: window batch {n} x {c} x {th} x {tw} must have 1..2^31-1 elements")
-    arena = pack.arena
-    out = torch.empty((n, c, th, tw), dtype=torch.float32, device=arena.device)
-    _launch("tiles_gather", out.numel() * (arena.element_size() + 4), "grr_tiles_gather", arena.data_ptr(),
-            arena.numel(), int(arena.dtype == torch.float32), c, pack.table.data_ptr(), n_img, table.data_ptr(), n, th,
-            tw, out.data_ptr(), _stream(arena.device))
-    return out
+    _check_table("tiles_gather", table, pack.arena.device, 7, "arena")
+    return _gather("tiles_gather", pack.arena, _arena_args(pack, n_img, c), c, table, th, tw)
 
 
 def tiles_scatter(y: Tensor, table: Tensor, pack_out, core_px: Optional[int] = None) -> None:
@@ -1871,19 +1881,13 @@ def tiles_scatter(y: Tensor, table: Tensor, pack_out, core_px: Optional[int] = N
     ``pack_out.arena`` (quantisation as tile_scatter).  core_px: pixels written, for the timer's byte count."""
     n_img, c = _check_pack("tiles_scatter", pack_out)
     arena = pack_out.arena
-    n = _check_table7("tiles_scatter", table, arena.device)
+    n = _check_table("tiles_scatter", table, arena.device, 7, "arena")
     if not isinstance(y, Tensor) or y.dim() != 4 or y.shape[0] != n or y.shape[1] != c:
         raise ValueError(f"tiles_scatter: y {tuple(getattr(y, 'shape', ()))} does not match {n} windows of {c} channels")
     _check("tiles_scatter", y)
     if y.device != arena.device:
         raise ValueError("tiles_scatter: y must be on the arena's device")
-    th, tw = y.shape[2], y.shape[3]
-    if not image_io_ok(c, n * th, tw):
-        raise ValueError(f"tiles_scatter: window batch {tuple(y.shape)} must have 1..2^31-1 elements")
-    px = n * th * tw if core_px is None else core_px
-    _launch("tiles_scatter", px * c * (4 + arena.element_size()), "grr_tiles_scatter", y.data_ptr(), table.data_ptr(),
-            n, th, tw, arena.data_ptr(), arena.numel(), int(arena.dtype == torch.float32), c, pack_out.table.data_ptr(),
-            n_img, _stream(arena.device))
+    _scatter("tiles_scatter", y, table, arena, _arena_args(pack_out, n_img, c), core_px)
 
 
 def u8_sse_segments(a: Tensor, b: Tensor, offsets) -> List[int]:

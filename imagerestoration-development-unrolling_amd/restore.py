@@ -28,6 +28,7 @@ Single process: several ranks are ``tiling.tiled_forward``'s business.
 from __future__ import annotations
 
 from dataclasses import dataclass
+from functools import partial
 from typing import Callable, List, Sequence, Tuple
 
 import numpy as np
@@ -100,35 +101,55 @@ def _model_device(model):
     return None
 
 
-def _core_px(p: RestorePlan, wins: Sequence[tiling.Window]) -> int:
-    return sum(max(0, min(r1, p.h) - r0) * max(0, min(c1, p.w) - c0) for _, _, r0, r1, c0, c1 in wins)
+def _core_px(rows, shapes) -> int:
+    """Pixels the rows (img, wr, wc, r0, r1, c0, c1) write into images of these (h, w): the timer's byte count."""
+    return sum(max(0, min(r1, shapes[i][0]) - r0) * max(0, min(c1, shapes[i][1]) - c0)
+               for i, _, _, r0, r1, c0, c1 in rows)
 
 
-def _restore_device(model: Callable, img: torch.Tensor, p: RestorePlan, micro_batch: int, quantise: bool) -> torch.Tensor:
-    """gather -> model -> scatter per micro-batch; img is the checked device image, the result is on its device."""
-    if micro_batch < 1:
-        raise ValueError(f"restore_image: micro_batch must be positive (got {micro_batch})")
-    table = torch.tensor(p.windows, dtype=torch.int32).to(img.device)     # uploaded once per image
+def _run_launches(who: str, model: Callable, launches, quantise: bool, gather, alloc, scatter):
+    """The one loop that calls the model: gather -> model -> scatter per launch, under no_grad with the model in
+    eval mode (its mode is restored).  launches yields (rows, th, tw, core_px), rows a slice of the uploaded
+    window table; gather(rows, th, tw) is the model's input, alloc(cout, dtype) the output for the first result's
+    channels (uint8 with quantise, else float32) and scatter(y, rows, out, core_px) writes into it.  Returns
+    what alloc did."""
     was_training = bool(getattr(model, "training", False))
     if was_training:
         model.eval()
-    out = None
+    out = cout = None
     try:
         with torch.no_grad():
-            for i in range(0, len(p.windows), micro_batch):
-                rows = table[i:i + micro_batch]
-                y = model(kernels.tile_gather(img, rows, p.th, p.tw))
-                if y.dim() != 4 or y.shape[0] != rows.shape[0] or tuple(y.shape[2:]) != (p.th, p.tw):
-                    raise ValueError(f"restore_image: the model returned {tuple(y.shape)} for {rows.shape[0]} "
-                                     f"windows of {p.th} x {p.tw}")
-                if out is None:     # every pixel is written exactly once (the cores partition the image): no fill
-                    out = torch.empty((p.h, p.w, y.shape[1]), dtype=torch.uint8 if quantise else torch.float32,
-                                      device=img.device)
-                kernels.tile_scatter(y.float().contiguous(), rows, out, _core_px(p, p.windows[i:i + micro_batch]))
+            for rows, th, tw, core_px in launches:
+                y = model(gather(rows, th, tw))
+                if y.dim() != 4 or y.shape[0] != rows.shape[0] or tuple(y.shape[2:]) != (th, tw) \
+                        or (out is not None and y.shape[1] != cout):
+                    raise ValueError(f"{who}: the model returned {tuple(y.shape)} for {rows.shape[0]} "
+                                     f"windows of {th} x {tw}")
+                if out is None:     # every pixel of every image is written exactly once (the cores partition it): no fill
+                    cout = int(y.shape[1])
+                    out = alloc(cout, torch.uint8 if quantise else torch.float32)
+                scatter(y.float().contiguous(), rows, out, core_px)
     finally:
         if was_training:
             model.train()
     return out
+
+
+def _restore_device(model: Callable, img: torch.Tensor, device, factor: int, tile: int, halo: int, micro_batch: int,
+                    quantise: bool) -> torch.Tensor:
+    """restore_image on the checked image, sent to the device as it is: micro_batch windows per launch whatever
+    the window shape; the result is on that device."""
+    p = plan(img.shape[0], img.shape[1], factor, tile, halo)
+    img = _to_device(img, device)
+    if micro_batch < 1:
+        raise ValueError(f"restore_image: micro_batch must be positive (got {micro_batch})")
+    table = torch.tensor(p.windows, dtype=torch.int32).to(img.device)     # uploaded once per image
+    launches = ((table[i:i + micro_batch], p.th, p.tw,
+                 _core_px([(0,) + tuple(w) for w in p.windows[i:i + micro_batch]], [(p.h, p.w)]))
+                for i in range(0, len(p.windows), micro_batch))
+    return _run_launches("restore_image", model, launches, quantise, partial(kernels.tile_gather, img),
+                         lambda cout, dtype: torch.empty((p.h, p.w, cout), dtype=dtype, device=img.device),
+                         kernels.tile_scatter)
 
 
 def restore_image(model: Callable, image, *, factor: int = 16, tile: int = TILE, halo: int = HALO,
@@ -145,8 +166,7 @@ def restore_image(model: Callable, image, *, factor: int = 16, tile: int = TILE,
     if device is None and not (isinstance(image, torch.Tensor) and image.is_cuda):
         device = _model_device(model)
     img, kind = _checked_image(image)
-    p = plan(img.shape[0], img.shape[1], factor, tile, halo)
-    out = _restore_device(model, _to_device(img, device), p, micro_batch, quantise)
+    out = _restore_device(model, img, device, factor, tile, halo, micro_batch, quantise)
     if kind == "numpy":
         return out.cpu().numpy()
     return out.cpu() if kind == "cpu" else out
@@ -248,41 +268,27 @@ def plan_images(shapes: Sequence[Tuple[int, int]], factor: int = 16, tile: int =
     return launches
 
 
-def _rows_core_px(rows, shapes) -> int:
-    return sum(max(0, min(r1, shapes[i][0]) - r0) * max(0, min(c1, shapes[i][1]) - c0)
-               for i, _, _, r0, r1, c0, c1 in rows)
-
-
 def _restore_pack(model: Callable, pack: ImagePack, launches, quantise: bool) -> ImagePack:
-    """gather -> model -> scatter per launch of plan_images; the result is a pack of the same image shapes."""
+    """restore_images on a pack: one launch per launch of plan_images; the result is a pack of the same image
+    shapes."""
     dev, shapes = pack.arena.device, pack.shapes()
     table = torch.tensor([r for _, _, rows in launches for r in rows], dtype=torch.int32).to(dev)  # one upload
-    was_training = bool(getattr(model, "training", False))
-    if was_training:
-        model.eval()
-    out, at = None, 0
-    try:
-        with torch.no_grad():
-            for th, tw, launch_rows in launches:
-                rows = table[at:at + len(launch_rows)]
-                at += len(launch_rows)
-                y = model(kernels.tiles_gather(pack, rows, th, tw))
-                if y.dim() != 4 or y.shape[0] != rows.shape[0] or tuple(y.shape[2:]) != (th, tw) \
-                        or (out is not None and y.shape[1] != out.c):
-                    raise ValueError(f"restore_images: the model returned {tuple(y.shape)} for {rows.shape[0]} "
-                                     f"windows of {th} x {tw}")
-                if out is None:     # every pixel of every image is written exactly once: no fill
-                    cout = int(y.shape[1])
-                    host_table, total = (pack.host_table, pack.arena.numel()) if cout == pack.c \
-                        else _host_table(shapes, cout)
-                    out = ImagePack(torch.empty(total, dtype=torch.uint8 if quantise else torch.float32, device=dev),
-                                    pack.table if cout == pack.c else torch.tensor(host_table, dtype=torch.int64).to(dev),
-                                    host_table, cout, pack.kinds)
-                kernels.tiles_scatter(y.float().contiguous(), rows, out, _rows_core_px(launch_rows, shapes))
-    finally:
-        if was_training:
-            model.train()
-    return out
+
+    def sliced():
+        at = 0
+        for th, tw, rows in launches:
+            yield table[at:at + len(rows)], th, tw, _core_px(rows, shapes)
+            at += len(rows)
+
+    def alloc(cout: int, dtype) -> ImagePack:
+        same = cout == pack.c
+        host_table, total = (pack.host_table, pack.arena.numel()) if same else _host_table(shapes, cout)
+        return ImagePack(torch.empty(total, dtype=dtype, device=dev),
+                         pack.table if same else torch.tensor(host_table, dtype=torch.int64).to(dev),
+                         host_table, cout, pack.kinds)
+
+    return _run_launches("restore_images", model, sliced(), quantise, partial(kernels.tiles_gather, pack), alloc,
+                         kernels.tiles_scatter)
 
 
 def restore_images(model: Callable, images: Sequence, *, factor: int = 16, tile: int = TILE, halo: int = HALO,
@@ -316,6 +322,21 @@ def _as_device_u8(x, device) -> torch.Tensor:
     return t if t.is_cuda and device is None else t.to(device if device is not None else "cuda")
 
 
+def _psnr(sse: int, n: int) -> float:
+    """10 log10(255^2 n / sse) in float64 from an exact integer SSE over n bytes; inf for sse == 0."""
+    return float("inf") if sse == 0 else float(10.0 * np.log10(255.0 ** 2 * n / sse))
+
+
+def _noisy(clean: np.ndarray, sigma: float, rs) -> np.ndarray:
+    noisy = clean.copy()
+    noisy += rs.normal(0, sigma / 255.0, clean.shape)      # float32 += float64 draws, as validate
+    return noisy
+
+
+def _clean_u8(clean: np.ndarray) -> np.ndarray:
+    return np.rint(clean.astype(np.float64) * 255.0).astype(np.uint8)
+
+
 def psnr_u8(a, b) -> float:
     """PSNR of two uint8 images of one shape: 10 log10(255^2 N / SSE) in float64 from the exact integer SSE
     (kernels.u8_sse), so it does not depend on any summation order; inf for equal images."""
@@ -323,8 +344,7 @@ def psnr_u8(a, b) -> float:
     ta, tb = _as_device_u8(a, dev), _as_device_u8(b, dev)
     if ta.shape != tb.shape:
         raise ValueError(f"psnr_u8: shapes differ ({tuple(ta.shape)} vs {tuple(tb.shape)})")
-    sse = kernels.u8_sse(ta, tb.to(ta.device))
-    return float("inf") if sse == 0 else float(10.0 * np.log10(255.0 ** 2 * ta.numel() / sse))
+    return _psnr(kernels.u8_sse(ta, tb.to(ta.device)), ta.numel())
 
 
 def evaluate(model: Callable, images, sigma: float = 25.0, factor: int = 16, seed: int = 2204,
@@ -347,13 +367,9 @@ def evaluate(model: Callable, images, sigma: float = 25.0, factor: int = 16, see
     psnrs = []
     for i in range(len(images)):
         clean = np.asarray(images[i], dtype=np.float32)
-        noisy = clean.copy()
-        noisy += rs.normal(0, sigma / 255.0, clean.shape)      # float32 += float64 draws, as validate
-        img, _ = _checked_image(noisy)
-        p = plan(img.shape[0], img.shape[1], factor, tile, halo)
-        restored = _restore_device(model, _to_device(img, device), p, micro_batch, True)
-        clean_u8 = np.rint(clean.astype(np.float64) * 255.0).astype(np.uint8)
-        psnrs.append(psnr_u8(restored, torch.from_numpy(clean_u8).to(restored.device)))
+        img, _ = _checked_image(_noisy(clean, sigma, rs))
+        restored = _restore_device(model, img, device, factor, tile, halo, micro_batch, True)
+        psnrs.append(psnr_u8(restored, torch.from_numpy(_clean_u8(clean)).to(restored.device)))
     return float(np.mean(psnrs)), psnrs
 
 
@@ -361,19 +377,12 @@ def _evaluate_across(model, images, sigma, factor, rs, tile, halo, micro_batch, 
     """evaluate(across_images=True): the same draws, the same uint8 images and the same integer SSEs as the
     per-image loop, with the windows of all images in shared batches and one SSE launch."""
     cleans = [np.asarray(images[i], dtype=np.float32) for i in range(len(images))]
-    noisy = []
-    for clean in cleans:                                         # all draws first, in image order
-        x = clean.copy()
-        x += rs.normal(0, sigma / 255.0, clean.shape)
-        noisy.append(x)
-    pack = pack_images(noisy, device)
+    pack = pack_images([_noisy(clean, sigma, rs) for clean in cleans], device)     # all draws first, in image order
     restored = _restore_pack(model, pack, plan_images(pack.shapes(), factor, tile, halo, micro_batch), True)
-    clean_u8 = pack_images([np.rint(c.astype(np.float64) * 255.0).astype(np.uint8) for c in cleans],
-                           restored.arena.device)
+    clean_u8 = pack_images([_clean_u8(c) for c in cleans], restored.arena.device)
     if clean_u8.host_table != restored.host_table:
         raise ValueError(f"evaluate: the model returns {restored.c} channel(s) for {clean_u8.c}; no PSNR")
     offsets = [off for off, _, _ in restored.host_table] + [restored.arena.numel()]
     sses = kernels.u8_sse_segments(restored.arena, clean_u8.arena, offsets)
-    psnrs = [float("inf") if sse == 0 else float(10.0 * np.log10(255.0 ** 2 * (h * w * restored.c) / sse))
-             for sse, (_, h, w) in zip(sses, restored.host_table)]
+    psnrs = [_psnr(sse, h * w * restored.c) for sse, (_, h, w) in zip(sses, restored.host_table)]
     return float(np.mean(psnrs)), psnrs
