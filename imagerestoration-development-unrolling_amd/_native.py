@@ -170,6 +170,11 @@ SIGNATURES = {
     "grr_tiles_gather": [P, L, I, I, P, I, P, I, I, I, P, P],
     "grr_tiles_scatter": [P, P, I, I, I, P, L, I, I, P, I, P],
     "grr_u8_sse_segments": [P, P, L, P, I, P, P],
+    # ... under the 8 flips and quarter turns (restore_image(ensemble=...)); the mode lists are host arrays
+    "grr_tile_gather_d8": [P, I, I, I, I, P, I, P, I, I, I, P, P],
+    "grr_tile_scatter_mean": [P, P, P, I, P, I, I, I, I, I, P, I, I, I, I, P],
+    "grr_tiles_gather_d8": [P, L, I, I, P, I, P, I, P, I, I, I, P, P],
+    "grr_tiles_scatter_mean": [P, P, P, I, P, I, I, I, I, I, P, L, I, I, P, I, P],
 }
 _RESTYPES = {"grr_version": c_int, "grr_last_error": ctypes.c_char_p, "grr_lnb_workspace_bytes": c_int64,
              "grr_conv1x1_workspace_bytes": c_int64, "grr_wgrad_workspace_bytes": c_int64,

@@ -11,6 +11,11 @@
 // carry their image's index in front:
 //   grr_tiles_gather / grr_tiles_scatter / grr_u8_sse_segments
 //
+// and, for the geometric self-ensemble (restore_image(ensemble=...)), the gather under up to 4 of the 8 flips
+// and quarter turns of a window at once and the scatter of the fixed-order mean of the members turned back:
+//   grr_tile_gather_d8 / grr_tile_scatter_mean / grr_tiles_gather_d8 / grr_tiles_scatter_mean
+// one gather body and one scatter body again, block per (window, tile), the odd quarter turns through LDS.
+//
 // Both families are instances of one gather body, one scatter body and one SSE kernel.  gather_kernel and
 // scatter_kernel are written against an image source (OneImage or Arena below), which says where a window's
 // image is, how wide coordinates and table rows are, and which element indices may be touched.
@@ -222,6 +227,222 @@ __global__ __launch_bounds__(kIoThreads) void scatter_kernel(Src src, WinArgs a)
   }
 }
 
+// ---------------------------------------------------------------------------
+// The 8 flips and quarter turns of a window (geometric self-ensemble), m = 2k + f: np.rot90(a, k), then
+// np.flipud if f.  Pixel (i, j) of a th x tw window with i' = flip_i ? th-1-i : i, j' = flip_j ? tw-1-j : j
+// lands at (i', j') of T_m (th x tw) for even k and at (j', i') of T_m (tw x th) for odd k:
+//   m        0  1  2  3  4  5  6  7
+//   flip_i   .  x  .  .  x  .  x  x     0xD2
+//   flip_j   .  .  x  .  x  x  .  x     0xB4
+//   odd k    .  .  x  x  .  .  x  x     bit 1 of m
+// A mode list travels in the kernel arguments, 4 bits a member (at most 8 members), not in a device table.
+constexpr int kTileI = 32;       // window rows of a block's tile: a transposed run of 32 floats is 128 bytes
+constexpr int kMeanTileJ = 32;   // window columns of a scatter_mean tile
+
+__device__ __forceinline__ int d8_mode(uint32_t modes, int j) { return (int)((modes >> (4 * j)) & 7u); }
+__device__ __forceinline__ bool d8_flip_i(int m) { return (0xD2u >> m) & 1u; }
+__device__ __forceinline__ bool d8_flip_j(int m) { return (0xB4u >> m) & 1u; }
+__device__ __forceinline__ bool d8_odd(int m) { return (m & 2) != 0; }
+
+// window columns of a gather_d8 tile: an image row of the tile is at least 128 bytes (uint8 C = 1: 128 pixels)
+template <typename T, int C>
+constexpr int d8_tile_j() { return sizeof(T) * C >= 2 ? 64 : 128; }
+
+struct D8Args {
+  float* win;            // [n M, C, th, tw] (even k) or [n M, C, tw, th] (odd k), window-major
+  const int32_t* table;  // as WinArgs
+  int n, th, tw;         // th x tw: the window in the picture's frame
+  int tiles_i, tiles_j;  // tiles of kTileI x d8_tile_j per window
+  int M;                 // modes of this call, all of one orientation
+  uint32_t modes;
+};
+
+// One block per (window, tile).  A lane reads one pixel (all C channels, adjacent lanes adjacent elements of an
+// image row) through the reflect rule.  Even k: the value goes straight to (i', j') of each mode's plane, a row
+// walk, forward or reversed.  Odd k: the tile goes through LDS with a row stride of TJ + 1 floats; it is read
+// back down its columns (lanes 32 rows apart in steps of TJ + 1 words: 32 distinct banks), so the planar side
+// is written in runs of 32 consecutive floats along the transformed row.
+template <typename T, int C, typename Src, bool Odd>
+__device__ __forceinline__ void gather_d8_body(const Src& src, const D8Args& a) {
+  typedef typename Src::idx I;
+  constexpr int TJ = d8_tile_j<T, C>();
+  constexpr int PX = kTileI * TJ / kIoThreads;
+  __shared__ float tile[Odd ? C * kTileI * (TJ + 1) : 1];
+  const uint32_t b = blockIdx.x;
+  const int tj = (int)(b % (uint32_t)a.tiles_j);
+  const uint32_t t = b / (uint32_t)a.tiles_j;
+  const int ti = (int)(t % (uint32_t)a.tiles_i), win = (int)(t / (uint32_t)a.tiles_i);
+  const int i0 = ti * kTileI, j0 = tj * TJ;
+  const int32_t* e = a.table + (I)win * Src::cols;
+  const Image<I> im = src.image(e);
+  const int32_t* w = e + (Src::cols - 6);
+  const T* img = static_cast<const T*>(src.base);
+  const int64_t plane = (int64_t)a.th * a.tw;
+  float* out = a.win + (int64_t)win * a.M * C * plane;
+#pragma unroll
+  for (int k = 0; k < PX; ++k) {
+    const int px = (int)threadIdx.x + k * kIoThreads;
+    const int il = px / TJ, jl = px % TJ, i = i0 + il, j = j0 + jl;
+    if (i >= a.th || j >= a.tw) continue;
+    const I sr = reflect_hi((I)w[0] + i, im.H), sc = reflect_hi((I)w[1] + j, im.W);
+    const int64_t base = src.elem(im, (int64_t)sr * im.W + sc, C);
+    float v[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) v[c] = load_px(img + src.clamped(base + c));
+    if (Odd) {
+#pragma unroll
+      for (int c = 0; c < C; ++c) tile[(c * kTileI + il) * (TJ + 1) + jl] = v[c];
+    } else {
+      for (int m = 0; m < a.M; ++m) {
+        const int mode = d8_mode(a.modes, m);
+        const int p = d8_flip_i(mode) ? a.th - 1 - i : i, q = d8_flip_j(mode) ? a.tw - 1 - j : j;
+        float* o = out + (int64_t)m * C * plane + (int64_t)p * a.tw + q;
+#pragma unroll
+        for (int c = 0; c < C; ++c) o[c * plane] = v[c];
+      }
+    }
+  }
+  if (!Odd) return;
+  __syncthreads();
+  for (int m = 0; m < a.M; ++m) {
+    const int mode = d8_mode(a.modes, m);
+    const bool fi = d8_flip_i(mode), fj = d8_flip_j(mode);
+    float* o = out + (int64_t)m * C * plane;
+#pragma unroll
+    for (int k = 0; k < PX; ++k) {
+      const int px = (int)threadIdx.x + k * kIoThreads;
+      const int il = px % kTileI, jl = px / kTileI, i = i0 + il, j = j0 + jl;
+      if (i >= a.th || j >= a.tw) continue;
+      const int64_t at = (int64_t)(fj ? a.tw - 1 - j : j) * a.th + (fi ? a.th - 1 - i : i);   // plane is tw x th
+#pragma unroll
+      for (int c = 0; c < C; ++c) o[c * plane + at] = tile[(c * kTileI + il) * (TJ + 1) + jl];
+    }
+  }
+}
+
+template <typename T, int C, typename Src>
+__global__ __launch_bounds__(kIoThreads) void gather_d8_even_kernel(Src src, D8Args a) {
+  gather_d8_body<T, C, Src, false>(src, a);
+}
+template <typename T, int C, typename Src>
+__global__ __launch_bounds__(kIoThreads) void gather_d8_odd_kernel(Src src, D8Args a) {
+  gather_d8_body<T, C, Src, true>(src, a);
+}
+
+struct MeanArgs {
+  const float* y0;       // [n M0, C, th, tw]: the even-k members, window-major; unused when M0 == 0
+  const float* y1;       // [n M1, C, tw, th]: the odd-k members
+  const int32_t* table;
+  int n, th, tw, tiles_i, tiles_j;
+  int M, M0, M1;         // M = M0 + M1 members, in the listed (ascending) order in modes
+  uint32_t modes;
+};
+
+// float32 pairwise tree over z[0 .. cnt) in the listed order, the odd one carried: [z0+z1, z2+z3, ...] until
+// one is left.  Static indices only, so z stays in registers; slots at and past cnt are never read into a sum.
+__device__ __forceinline__ float tree_sum8(float (&z)[8], int cnt) {
+#pragma unroll
+  for (int width = 4; width >= 1; width >>= 1) {
+#pragma unroll
+    for (int k = 0; k < width; ++k) z[k] = 2 * k + 1 < cnt ? z[2 * k] + z[2 * k + 1] : z[2 * k];
+    cnt = (cnt + 1) >> 1;
+  }
+  return z[0];
+}
+
+// One block per (window, tile of kTileI x kMeanTileJ); a tile outside the window's core box ends at once.  Per
+// channel: the odd-k members' tile is read from y1 along their own rows (runs of 32 floats) into LDS, row
+// stride kMeanTileJ + 1 words (the transposing write meets 32 distinct banks), and read back along the
+// picture's rows; the even-k members are read from y0 along their rows, forward or reversed.  A lane owns
+// PX pixels of the tile for all channels: it forms the tree mean of the M members in registers and writes the
+// pixel's C elements once (adjacent lanes adjacent elements).  No atomics, no canvas, no second pass.
+template <typename T, int C, typename Src>
+__global__ __launch_bounds__(kIoThreads) void scatter_mean_kernel(Src src, MeanArgs a) {
+  typedef typename Src::idx I;
+  constexpr int TJ = kMeanTileJ;
+  constexpr int PX = kTileI * TJ / kIoThreads;
+  constexpr int kSlot = kTileI * (TJ + 1);
+  __shared__ float tile[4 * kSlot];
+  const uint32_t b = blockIdx.x;
+  const int tj = (int)(b % (uint32_t)a.tiles_j);
+  const uint32_t t = b / (uint32_t)a.tiles_j;
+  const int ti = (int)(t % (uint32_t)a.tiles_i), win = (int)(t / (uint32_t)a.tiles_i);
+  const int i0 = ti * kTileI, j0 = tj * TJ;
+  const int32_t* e = a.table + (I)win * Src::cols;
+  const Image<I> im = src.image(e);
+  const int32_t* w = e + (Src::cols - 6);
+  const I wr = w[0], wc = w[1];
+  // the core box, cut to the window and to the window's own unpadded image
+  const I r0 = max(max((I)w[2], wr), (I)0), r1 = min(min((I)w[3], wr + a.th), im.H);
+  const I c0 = max(max((I)w[4], wc), (I)0), c1 = min(min((I)w[5], wc + a.tw), im.W);
+  if (wr + i0 >= r1 || wr + i0 + kTileI <= r0 || wc + j0 >= c1 || wc + j0 + TJ <= c0) return;   // the whole block
+  const int64_t plane = (int64_t)a.th * a.tw;
+  const float* y0 = a.y0 + (int64_t)win * a.M0 * C * plane;
+  const float* y1 = a.y1 + (int64_t)win * a.M1 * C * plane;
+  const float scale = (float)a.M;
+  float res[C][PX];
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    if (a.M1 > 0) {
+      if (c > 0) __syncthreads();       // the previous channel has been read
+      int slot = 0;
+#pragma unroll
+      for (int m = 0; m < 8; ++m) {
+        const int mode = d8_mode(a.modes, m);
+        if (m >= a.M || !d8_odd(mode)) continue;
+        const bool fi = d8_flip_i(mode), fj = d8_flip_j(mode);
+        const float* y = y1 + ((int64_t)slot * C + c) * plane;
+#pragma unroll
+        for (int k = 0; k < PX; ++k) {
+          const int px = (int)threadIdx.x + k * kIoThreads;
+          const int il = px % kTileI, jl = px / kTileI, i = i0 + il, j = j0 + jl;
+          if (i < a.th && j < a.tw)
+            tile[slot * kSlot + il * (TJ + 1) + jl] = y[(int64_t)(fj ? a.tw - 1 - j : j) * a.th + (fi ? a.th - 1 - i : i)];
+        }
+        ++slot;
+      }
+      __syncthreads();
+    }
+#pragma unroll
+    for (int k = 0; k < PX; ++k) {
+      const int px = (int)threadIdx.x + k * kIoThreads;
+      const int il = px / TJ, jl = px % TJ, i = i0 + il, j = j0 + jl;
+      float z[8];
+      int even = 0, odd = 0;
+#pragma unroll
+      for (int m = 0; m < 8; ++m) {
+        z[m] = 0.0f;
+        if (m >= a.M || i >= a.th || j >= a.tw) continue;
+        const int mode = d8_mode(a.modes, m);
+        if (d8_odd(mode)) {
+          z[m] = tile[odd * kSlot + il * (TJ + 1) + jl];
+          ++odd;
+        } else {
+          const int p = d8_flip_i(mode) ? a.th - 1 - i : i, q = d8_flip_j(mode) ? a.tw - 1 - j : j;
+          z[m] = y0[((int64_t)even * C + c) * plane + (int64_t)p * a.tw + q];
+          ++even;
+        }
+      }
+      res[c][k] = __fdiv_rn(tree_sum8(z, a.M), scale);
+    }
+  }
+  T* img = static_cast<T*>(src.base);
+#pragma unroll
+  for (int k = 0; k < PX; ++k) {
+    const int px = (int)threadIdx.x + k * kIoThreads;
+    const int i = i0 + px / TJ, j = j0 + px % TJ;
+    if (i >= a.th || j >= a.tw) continue;
+    const I r = wr + i, col = wc + j;
+    if (r < r0 || r >= r1 || col < c0 || col >= c1) continue;
+    const int64_t at = (int64_t)r * im.W + col;     // 0 <= r < H and 0 <= col < W
+    if (!src.has_px(at)) continue;
+    const int64_t base = src.elem(im, at, C);
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+      if (src.inside(base + c, 1)) store_px(img + base + c, res[c][k]);
+  }
+}
+
 __device__ __forceinline__ uint32_t sq_diff(uint32_t x, uint32_t y) {
   const int d = (int)x - (int)y;
   return (uint32_t)(d * d);
@@ -332,6 +553,96 @@ grr_status arena_args(const char* what, const void* arena, int64_t arena_elems, 
   return GRR_OK;
 }
 
+// A host mode list, checked: 1..8 modes of 0..7, strictly ascending.  packed as D8Args / MeanArgs carry it.
+struct ModeList {
+  uint32_t packed;
+  int M, M0, M1;      // all, even-k, odd-k
+};
+
+grr_status mode_list(const char* what, const int32_t* modes, int n_modes, ModeList* l) {
+  GRR_REQUIRE(modes, GRR_ERR_INVALID_ARG, "%s: bad args", what);
+  GRR_REQUIRE(n_modes >= 1 && n_modes <= 8, GRR_ERR_INVALID_ARG, "%s: needs 1..8 modes (got %d)", what, n_modes);
+  *l = ModeList{0u, n_modes, 0, 0};
+  for (int j = 0; j < n_modes; ++j) {
+    const int m = modes[j];
+    GRR_REQUIRE(m >= 0 && m <= 7, GRR_ERR_INVALID_ARG, "%s: mode %d is outside 0..7", what, m);
+    GRR_REQUIRE(j == 0 || m > modes[j - 1], GRR_ERR_INVALID_ARG, "%s: modes must be strictly ascending (%d after %d)",
+                what, m, j ? modes[j - 1] : 0);
+    l->packed |= (uint32_t)m << (4 * j);
+    ++(m & 2 ? l->M1 : l->M0);
+  }
+  return GRR_OK;
+}
+
+// The mode checks of the two gathers: one orientation.  rows: n M, the rows of the batch, or n where n <= 0.
+grr_status gather_d8_modes(const char* what, const int32_t* modes, int n_modes, int n, ModeList* l, int* rows) {
+  grr_status st = mode_list(what, modes, n_modes, l);
+  if (st != GRR_OK) return st;
+  GRR_REQUIRE(l->M0 == 0 || l->M1 == 0, GRR_ERR_INVALID_ARG,
+              "%s: the modes of one call share an orientation (got %d of even k and %d of odd k)", what, l->M0, l->M1);
+  const int64_t r = n > 0 ? (int64_t)n * l->M : n;
+  GRR_REQUIRE(r < (1ll << 31), GRR_ERR_UNSUPPORTED, "%s: window batch n M must be below 2^31 (got %d x %d)", what, n, l->M);
+  *rows = (int)r;
+  return GRR_OK;
+}
+
+D8Args d8_args(const WinArgs& wa, const ModeList& l, int n, int bh, int bw, int tile_j) {
+  D8Args a{};
+  a.win = wa.win;
+  a.table = wa.table;
+  a.n = n;
+  a.th = l.M1 ? bw : bh;      // odd k: the batch holds the window turned
+  a.tw = l.M1 ? bh : bw;
+  a.tiles_i = (a.th + kTileI - 1) / kTileI;
+  a.tiles_j = (a.tw + tile_j - 1) / tile_j;
+  a.M = l.M;
+  a.modes = l.packed;
+  return a;
+}
+
+int gather_tile_j(int img_f32, int C) { return img_f32 || C >= 2 ? 64 : 128; }   // d8_tile_j<T, C>()
+
+// The mode and operand checks of the two scatter_means, before image_args / arena_args: fills l; *y and *rows
+// are the larger of the two batches, which those check (NULL, alignment, the 2^31 bound).
+grr_status mean_modes(const char* what, const float* y0, const float* y1, const int32_t* modes, int n_modes, int n_even,
+                      int n_odd, int n, ModeList* l, const float** y, int* rows) {
+  grr_status st = mode_list(what, modes, n_modes, l);
+  if (st != GRR_OK) return st;
+  GRR_REQUIRE(n_even + n_odd == n_modes && n_even == l->M0 && n_odd == l->M1, GRR_ERR_INVALID_ARG,
+              "%s: M0 + M1 must be the list's %d modes, %d of even k and %d of odd k (got %d and %d)", what, l->M, l->M0,
+              l->M1, n_even, n_odd);
+  GRR_REQUIRE((l->M0 == 0 || y0) && (l->M1 == 0 || y1), GRR_ERR_INVALID_ARG, "%s: bad args", what);
+  GRR_REQUIRE((uintptr_t)y0 % 4 == 0 && (uintptr_t)y1 % 4 == 0, GRR_ERR_INVALID_ARG,
+              "%s: float32 and int32 operands must be 4-byte aligned", what);
+  const int most = std::max(l->M0, l->M1);
+  const int64_t r = n > 0 ? (int64_t)n * most : n;
+  GRR_REQUIRE(r < (1ll << 31), GRR_ERR_UNSUPPORTED, "%s: window batch n M must be below 2^31 (got %d x %d)", what, n, most);
+  *y = l->M0 >= l->M1 ? y0 : y1;
+  *rows = (int)r;
+  return GRR_OK;
+}
+
+MeanArgs mean_args(const float* y0, const float* y1, const WinArgs& wa, const ModeList& l, int n, int th, int tw) {
+  MeanArgs a{};
+  a.y0 = y0;
+  a.y1 = y1;
+  a.table = wa.table;
+  a.n = n;
+  a.th = th;
+  a.tw = tw;
+  a.tiles_i = (th + kTileI - 1) / kTileI;
+  a.tiles_j = (tw + kMeanTileJ - 1) / kMeanTileJ;
+  a.M = l.M;
+  a.M0 = l.M0;
+  a.M1 = l.M1;
+  a.modes = l.packed;
+  return a;
+}
+
+// n tiles_i tiles_j <= n th tw < 2^31
+template <typename A>
+dim3 tile_grid(const A& a) { return dim3((uint32_t)((int64_t)a.n * a.tiles_i * a.tiles_j)); }
+
 }  // namespace
 }  // namespace grr
 
@@ -424,6 +735,83 @@ grr_status grr_u8_sse_segments(const uint8_t* a, const uint8_t* b, int64_t total
   hipLaunchKernelGGL(u8_sse_kernel, dim3(bx, n_seg), dim3(kIoThreads), 0, s, a, b, total, offsets, vec,
                      reinterpret_cast<unsigned long long*>(out));
   return launch_status("grr_u8_sse_segments");
+}
+
+grr_status grr_tile_gather_d8(const void* img, int img_f32, int H, int W, int C, const int32_t* table, int n,
+                              const int32_t* modes, int n_modes, int bh, int bw, float* out, void* stream) {
+  clear_error();
+  ModeList l{};
+  int rows = 0;
+  grr_status st = gather_d8_modes("grr_tile_gather_d8", modes, n_modes, n, &l, &rows);
+  if (st != GRR_OK) return st;
+  OneImage src{};
+  WinArgs wa{};
+  st = image_args("grr_tile_gather_d8", img, img_f32, H, W, C, table, rows, bh, bw, out, &src, &wa);
+  if (st != GRR_OK) return st;
+  const D8Args a = d8_args(wa, l, n, bh, bw, gather_tile_j(img_f32, C));
+  if (l.M1)
+    GRR_IO_DISPATCH(gather_d8_odd_kernel, OneImage, img_f32, C, tile_grid(a), (hipStream_t)stream, src, a);
+  else
+    GRR_IO_DISPATCH(gather_d8_even_kernel, OneImage, img_f32, C, tile_grid(a), (hipStream_t)stream, src, a);
+  return launch_status("grr_tile_gather_d8");
+}
+
+grr_status grr_tile_scatter_mean(const float* y0, const float* y1, const int32_t* table, int n, const int32_t* modes,
+                                 int n_modes, int n_even, int n_odd, int th, int tw, void* img, int img_f32, int H, int W,
+                                 int C, void* stream) {
+  clear_error();
+  ModeList l{};
+  const float* y = nullptr;
+  int rows = 0;
+  grr_status st = mean_modes("grr_tile_scatter_mean", y0, y1, modes, n_modes, n_even, n_odd, n, &l, &y, &rows);
+  if (st != GRR_OK) return st;
+  OneImage src{};
+  WinArgs wa{};
+  st = image_args("grr_tile_scatter_mean", img, img_f32, H, W, C, table, rows, th, tw, y, &src, &wa);
+  if (st != GRR_OK) return st;
+  const MeanArgs a = mean_args(y0, y1, wa, l, n, th, tw);
+  GRR_IO_DISPATCH(scatter_mean_kernel, OneImage, img_f32, C, tile_grid(a), (hipStream_t)stream, src, a);
+  return launch_status("grr_tile_scatter_mean");
+}
+
+grr_status grr_tiles_gather_d8(const void* arena, int64_t arena_elems, int img_f32, int C, const int64_t* img_table,
+                               int n_img, const int32_t* table, int n, const int32_t* modes, int n_modes, int bh, int bw,
+                               float* out, void* stream) {
+  clear_error();
+  ModeList l{};
+  int rows = 0;
+  grr_status st = gather_d8_modes("grr_tiles_gather_d8", modes, n_modes, n, &l, &rows);
+  if (st != GRR_OK) return st;
+  Arena src{};
+  WinArgs wa{};
+  st = arena_args("grr_tiles_gather_d8", arena, arena_elems, img_f32, C, img_table, n_img, table, rows, bh, bw, out, &src,
+                  &wa);
+  if (st != GRR_OK) return st;
+  const D8Args a = d8_args(wa, l, n, bh, bw, gather_tile_j(img_f32, C));
+  if (l.M1)
+    GRR_IO_DISPATCH(gather_d8_odd_kernel, Arena, img_f32, C, tile_grid(a), (hipStream_t)stream, src, a);
+  else
+    GRR_IO_DISPATCH(gather_d8_even_kernel, Arena, img_f32, C, tile_grid(a), (hipStream_t)stream, src, a);
+  return launch_status("grr_tiles_gather_d8");
+}
+
+grr_status grr_tiles_scatter_mean(const float* y0, const float* y1, const int32_t* table, int n, const int32_t* modes,
+                                  int n_modes, int n_even, int n_odd, int th, int tw, void* arena, int64_t arena_elems,
+                                  int img_f32, int C, const int64_t* img_table, int n_img, void* stream) {
+  clear_error();
+  ModeList l{};
+  const float* y = nullptr;
+  int rows = 0;
+  grr_status st = mean_modes("grr_tiles_scatter_mean", y0, y1, modes, n_modes, n_even, n_odd, n, &l, &y, &rows);
+  if (st != GRR_OK) return st;
+  Arena src{};
+  WinArgs wa{};
+  st = arena_args("grr_tiles_scatter_mean", arena, arena_elems, img_f32, C, img_table, n_img, table, rows, th, tw, y, &src,
+                  &wa);
+  if (st != GRR_OK) return st;
+  const MeanArgs a = mean_args(y0, y1, wa, l, n, th, tw);
+  GRR_IO_DISPATCH(scatter_mean_kernel, Arena, img_f32, C, tile_grid(a), (hipStream_t)stream, src, a);
+  return launch_status("grr_tiles_scatter_mean");
 }
 
 }  // extern "C"

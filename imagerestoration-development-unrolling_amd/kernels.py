@@ -9,6 +9,7 @@ from __future__ import annotations
 
 from typing import List, Optional, Sequence, Tuple
 
+import ctypes
 import os
 
 import torch
@@ -1888,6 +1889,122 @@ def tiles_scatter(y: Tensor, table: Tensor, pack_out, core_px: Optional[int] = N
     if y.device != arena.device:
         raise ValueError("tiles_scatter: y must be on the arena's device")
     _scatter("tiles_scatter", y, table, arena, _arena_args(pack_out, n_img, c), core_px)
+
+
+# ---------------------------------------------------------------------------
+# ... under the 8 flips and quarter turns of a window (restore_image(ensemble=...)).  Mode m = 2k + f:
+# np.rot90(a, k), then np.flipud if f -- the numbering of the reference's data_augmentation.
+def dihedral_index(m: int, th: int, tw: int, i: int, j: int) -> Tuple[int, int]:
+    """Where pixel (i, j) of a th x tw window lands in T_m, in plain Python: k = m // 2 quarter turns
+    counter-clockwise, (i, j, th, tw) <- (tw - 1 - j, i, tw, th) each, then i <- th - 1 - i if m is odd.  T_m is
+    th x tw for even k and tw x th for odd k."""
+    if not 0 <= m <= 7:
+        raise ValueError(f"dihedral_index: mode {m} is outside 0..7")
+    for _ in range(m // 2):
+        i, j, th, tw = tw - 1 - j, i, tw, th
+    return (th - 1 - i if m % 2 else i), j
+
+
+def _check_modes(name: str, modes) -> Tuple[int, ...]:
+    try:
+        ms = tuple(int(m) for m in modes)
+    except TypeError:
+        ms = ()
+    if not 1 <= len(ms) <= 8 or any(not 0 <= m <= 7 for m in ms) or any(b <= a for a, b in zip(ms, ms[1:])):
+        raise ValueError(f"{name}: modes are 1..8 strictly ascending ints of 0..7, got {modes!r}")
+    return ms
+
+
+def _mode_array(ms: Tuple[int, ...]):
+    return (ctypes.c_int32 * len(ms))(*ms)
+
+
+def _check_gather_modes(name: str, modes) -> Tuple[int, ...]:
+    ms = _check_modes(name, modes)
+    if len({m // 2 % 2 for m in ms}) != 1:
+        raise ValueError(f"{name}: the modes of one call share an orientation (0, 1, 4, 5 or 2, 3, 6, 7), got {ms}")
+    return ms
+
+
+def _gather_d8(kind: str, buf: Tensor, src_args: tuple, c: int, table: Tensor, ms: Tuple[int, ...], bh: int,
+               bw: int) -> Tensor:
+    """tile_gather_d8 / tiles_gather_d8 after their own checks (as _gather); ms: the checked modes."""
+    n = table.shape[0]
+    _check_batch(kind, n * len(ms), c, bh, bw)
+    out = torch.empty((n * len(ms), c, bh, bw), dtype=torch.float32, device=buf.device)
+    _launch(kind, n * c * bh * bw * (buf.element_size() + 4 * len(ms)), "grr_" + kind, *src_args, table.data_ptr(), n,
+            _mode_array(ms), len(ms), bh, bw, out.data_ptr(), _stream(buf.device))
+    return out
+
+
+def _scatter_mean(kind: str, y0: Optional[Tensor], y1: Optional[Tensor], table: Tensor, ms: Tuple[int, ...], th: int,
+                  tw: int, c: int, buf: Tensor, src_args: tuple, core_px: Optional[int]) -> None:
+    """tile_scatter_mean / tiles_scatter_mean after their own checks (as _scatter): y0 [n M0, C, th, tw] holds
+    the even-k members, y1 [n M1, C, tw, th] the odd-k ones; ms: the checked modes."""
+    n = table.shape[0]
+    m1 = sum(m // 2 % 2 for m in ms)
+    counts = (len(ms) - m1, m1)
+    for y, cnt, shape in ((y0, counts[0], (th, tw)), (y1, counts[1], (tw, th))):
+        if cnt == 0:
+            if y is not None:
+                raise ValueError(f"{kind}: a batch was given for an orientation that has no mode in {ms}")
+            continue
+        if not isinstance(y, Tensor) or y.dim() != 4 or tuple(y.shape) != (n * cnt, c) + shape:
+            raise ValueError(f"{kind}: expected a batch {(n * cnt, c) + shape} for {n} windows and modes {ms}, got "
+                             f"{tuple(getattr(y, 'shape', ()))}")
+        _check(kind, y)
+        if y.device != buf.device:
+            raise ValueError(f"{kind}: the batches must be on the output's device")
+    _check_batch(kind, n * max(counts), c, th, tw)
+    px = n * th * tw if core_px is None else core_px
+    _launch(kind, px * c * (4 * len(ms) + buf.element_size()), "grr_" + kind, y0.data_ptr() if counts[0] else None,
+            y1.data_ptr() if counts[1] else None, table.data_ptr(), n, _mode_array(ms), len(ms), counts[0], counts[1],
+            th, tw, *src_args, _stream(buf.device))
+
+
+def tile_gather_d8(img: Tensor, table: Tensor, modes, bh: int, bw: int) -> Tensor:
+    """tile_gather under the modes of one orientation (all of 0, 1, 4, 5 or all of 2, 3, 6, 7, ascending): out
+    [n M, C, bh, bw], row w M + j = T_modes[j] of window w, which is bh x bw in the picture for even k and
+    bw x bh for odd k.  Element conversion as tile_gather."""
+    ms = _check_gather_modes("tile_gather_d8", modes)
+    h, w, c = _check_image("tile_gather_d8", img)
+    _check_table("tile_gather_d8", table, img.device, 6, "image")
+    img = img.contiguous()
+    return _gather_d8("tile_gather_d8", img, (img.data_ptr(), int(img.dtype == torch.float32), h, w, c), c, table,
+                      ms, bh, bw)
+
+
+def tile_scatter_mean(y0: Optional[Tensor], y1: Optional[Tensor], table: Tensor, modes, th: int, tw: int, img: Tensor,
+                      core_px: Optional[int] = None) -> None:
+    """The float32 pairwise-tree mean, in the listed (ascending) order, of the members T_m^-1(y) of each th x tw
+    window -- y0 [n M0, C, th, tw] the even-k members, y1 [n M1, C, tw, th] the odd-k ones, window-major as
+    tile_gather_d8 lays them out, None where an orientation has no mode -- then tile_scatter's steps into the
+    contiguous HWC image."""
+    ms = _check_modes("tile_scatter_mean", modes)
+    h, w, c = _check_image("tile_scatter_mean", img)
+    if not img.is_contiguous():
+        raise ValueError("tile_scatter_mean: the output image must be contiguous")
+    _check_table("tile_scatter_mean", table, img.device, 6, "image")
+    _scatter_mean("tile_scatter_mean", y0, y1, table, ms, th, tw, c, img,
+                  (img.data_ptr(), int(img.dtype == torch.float32), h, w, c), core_px)
+
+
+def tiles_gather_d8(pack, table: Tensor, modes, bh: int, bw: int) -> Tensor:
+    """tile_gather_d8 for the images of ``pack`` (table rows [n, 7], as tiles_gather)."""
+    ms = _check_gather_modes("tiles_gather_d8", modes)
+    n_img, c = _check_pack("tiles_gather_d8", pack)
+    _check_table("tiles_gather_d8", table, pack.arena.device, 7, "arena")
+    return _gather_d8("tiles_gather_d8", pack.arena, _arena_args(pack, n_img, c), c, table, ms, bh, bw)
+
+
+def tiles_scatter_mean(y0: Optional[Tensor], y1: Optional[Tensor], table: Tensor, modes, th: int, tw: int, pack_out,
+                       core_px: Optional[int] = None) -> None:
+    """tile_scatter_mean into each window's own image of ``pack_out.arena``."""
+    ms = _check_modes("tiles_scatter_mean", modes)
+    n_img, c = _check_pack("tiles_scatter_mean", pack_out)
+    _check_table("tiles_scatter_mean", table, pack_out.arena.device, 7, "arena")
+    _scatter_mean("tiles_scatter_mean", y0, y1, table, ms, th, tw, c, pack_out.arena,
+                  _arena_args(pack_out, n_img, c), core_px)
 
 
 def u8_sse_segments(a: Tensor, b: Tensor, offsets) -> List[int]:

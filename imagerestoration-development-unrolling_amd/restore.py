@@ -23,6 +23,24 @@ lie back to back in one arena (``pack_images``), ``plan_images`` groups the wind
 shape into launches of one restore_image launch's pixel budget, and ``kernels.tiles_gather`` /
 ``tiles_scatter`` / ``u8_sse_segments`` address each window's own image through a device image table.
 
+Geometric self-ensemble (``ensemble=8`` or a list of modes on restore_image, restore_images and evaluate): the
+picture is restored under the flips and quarter turns T_m, m = 2k + f = np.rot90(a, k) then np.flipud if f (the
+numbering of the reference's ``data_augmentation``), each result is turned back and the M estimates are
+averaged.  The transforms act on the model's window, after the reflect rule, so the padding, the window grid,
+the cores and the crop are the plain call's for every mode, and a one-window call on a picture that needs no
+padding equals transforming the picture itself.  Member j is z_j = T_mj^-1(model(T_mj(window))); the result is
+the float32 pairwise tree over the ascending mode list -- [z0 + z1, z2 + z3, ..., the odd one carried] until
+one is left, for M = 8 ((z0+z1)+(z2+z3)) + ((z4+z5)+(z6+z7)) -- divided by float32(M), then the plain call's
+crop, clamp and quantisation.  With a model that commutes with the transforms the tree gives the plain call's
+result bit for bit for M = 2, 4 and 8 (sums of equal values are exact; a left-to-right sum rounds at 3v).
+Per group of windows a launch runs ``kernels.tile_gather_d8`` for the even-k modes (0, 1, 4, 5), the model,
+``tile_gather_d8`` for the odd-k modes (2, 3, 6, 7: windows of tw x th), the model again, and
+``kernels.tile_scatter_mean``: two model calls per group, one per orientation, for square windows too.  No
+transformed copy of the picture, no per-mode canvas and no ATen op per mode exists.  A group is
+max(1, micro_batch // Mo) windows, Mo the larger number of modes of one orientation, so no model call is larger
+than a plain call's -- except where micro_batch < Mo, when a call holds the Mo rows of one window.  The peak
+memory grows by one output batch: the even-k results are alive while the odd-k ones are computed.
+
 Single process: several ranks are ``tiling.tiled_forward``'s business.
 """
 from __future__ import annotations
@@ -69,6 +87,32 @@ def plan(h: int, w: int, factor: int = 16, tile: int = TILE, halo: int = HALO) -
     return RestorePlan(h, w, hp, wp, min(tile, hp), min(tile, wp), tuple(wins))
 
 
+def _ensemble_modes(who: str, ensemble) -> Tuple[int, ...]:
+    """The ascending mode list of an ``ensemble`` argument: 1 or None -> (0,), 8 -> all of 0..7, else a strictly
+    ascending sequence of modes of 0..7.  (0,) is the plain path.  ValueError otherwise."""
+    if ensemble is None or (isinstance(ensemble, int) and not isinstance(ensemble, bool) and ensemble == 1):
+        return (0,)
+    if isinstance(ensemble, int) and not isinstance(ensemble, bool) and ensemble == 8:
+        return tuple(range(8))
+    ms = None
+    if isinstance(ensemble, (tuple, list, range)) and all(isinstance(m, (int, np.integer)) and not isinstance(m, bool)
+                                                          for m in ensemble):
+        ms = tuple(int(m) for m in ensemble)
+    if not ms or any(not 0 <= m <= 7 for m in ms) or any(b <= a for a, b in zip(ms, ms[1:])):
+        raise ValueError(f"{who}: ensemble is 1, 8 or a strictly ascending sequence of modes of 0..7, got {ensemble!r}")
+    return ms
+
+
+def _split_modes(modes: Tuple[int, ...]) -> Tuple[Tuple[int, ...], Tuple[int, ...]]:
+    """(even-k modes, odd-k modes): T_m keeps the window's shape for 0, 1, 4, 5 and turns it for 2, 3, 6, 7."""
+    return tuple(m for m in modes if m // 2 % 2 == 0), tuple(m for m in modes if m // 2 % 2 == 1)
+
+
+def _most_modes(modes: Tuple[int, ...]) -> int:
+    """Mo: the rows one window has in the larger of a launch's two model calls."""
+    return max(len(ms) for ms in _split_modes(modes))
+
+
 def _checked_image(image) -> Tuple[torch.Tensor, str]:
     """The HWC image as a tensor where it is, shape and dtype checked, and what came in ("numpy", "cpu" or
     "cuda")."""
@@ -107,11 +151,14 @@ def _core_px(rows, shapes) -> int:
                for i, _, _, r0, r1, c0, c1 in rows)
 
 
-def _run_launches(who: str, model: Callable, launches, quantise: bool, gather, alloc, scatter):
-    """The one loop that calls the model: gather -> model -> scatter per launch, under no_grad with the model in
-    eval mode (its mode is restored).  launches yields (rows, th, tw, core_px), rows a slice of the uploaded
-    window table; gather(rows, th, tw) is the model's input, alloc(cout, dtype) the output for the first result's
-    channels (uint8 with quantise, else float32) and scatter(y, rows, out, core_px) writes into it.  Returns
+def _run_launches(who: str, model: Callable, launches, quantise: bool, gather, alloc, scatter, modes=(0,)):
+    """The one loop that calls the model: per launch gather -> model once per orientation of ``modes``, then one
+    scatter, under no_grad with the model in eval mode (its mode is restored).  launches yields
+    (rows, th, tw, core_px), rows a slice of the uploaded window table; gather(rows, ms, bh, bw) is the model's
+    input for one orientation's modes ms (bh x bw = th x tw for the even-k ones, tw x th for the odd-k ones),
+    alloc(cout, dtype) the output for the first result's channels (uint8 with quantise, else float32) and
+    scatter(y0, y1, rows, modes, th, tw, out, core_px) writes both results into it (None where an orientation has
+    no mode).  The plain call is modes (0,): one th x tw call per launch (_plain_io adapts its kernels).  Returns
     what alloc did."""
     was_training = bool(getattr(model, "training", False))
     if was_training:
@@ -120,40 +167,57 @@ def _run_launches(who: str, model: Callable, launches, quantise: bool, gather, a
     try:
         with torch.no_grad():
             for rows, th, tw, core_px in launches:
-                y = model(gather(rows, th, tw))
-                if y.dim() != 4 or y.shape[0] != rows.shape[0] or tuple(y.shape[2:]) != (th, tw) \
-                        or (out is not None and y.shape[1] != cout):
-                    raise ValueError(f"{who}: the model returned {tuple(y.shape)} for {rows.shape[0]} "
-                                     f"windows of {th} x {tw}")
-                if out is None:     # every pixel of every image is written exactly once (the cores partition it): no fill
-                    cout = int(y.shape[1])
-                    out = alloc(cout, torch.uint8 if quantise else torch.float32)
-                scatter(y.float().contiguous(), rows, out, core_px)
+                ys = []
+                for ms, bh, bw in zip(_split_modes(modes), (th, tw), (tw, th)):
+                    if not ms:
+                        ys.append(None)
+                        continue
+                    n = rows.shape[0] * len(ms)
+                    y = model(gather(rows, ms, bh, bw))
+                    if y.dim() != 4 or y.shape[0] != n or tuple(y.shape[2:]) != (bh, bw) \
+                            or (out is not None and y.shape[1] != cout):
+                        raise ValueError(f"{who}: the model returned {tuple(y.shape)} for {n} "
+                                         f"windows of {bh} x {bw}")
+                    if out is None:     # every pixel of every image is written exactly once (the cores partition it): no fill
+                        cout = int(y.shape[1])
+                        out = alloc(cout, torch.uint8 if quantise else torch.float32)
+                    ys.append(y.float().contiguous())
+                scatter(ys[0], ys[1], rows, modes, th, tw, out, core_px)
     finally:
         if was_training:
             model.train()
     return out
 
 
+def _plain_io(gather, scatter):
+    """The plain call's gather(rows, th, tw) and scatter(y, rows, out, core_px) as _run_launches calls them with
+    modes (0,): today's kernels, no transform, no mean."""
+    return (lambda rows, ms, bh, bw: gather(rows, bh, bw),
+            lambda y0, y1, rows, modes, th, tw, out, core_px: scatter(y0, rows, out, core_px))
+
+
 def _restore_device(model: Callable, img: torch.Tensor, device, factor: int, tile: int, halo: int, micro_batch: int,
-                    quantise: bool) -> torch.Tensor:
+                    quantise: bool, modes: Tuple[int, ...] = (0,)) -> torch.Tensor:
     """restore_image on the checked image, sent to the device as it is: micro_batch windows per launch whatever
-    the window shape; the result is on that device."""
+    the window shape (max(1, micro_batch // Mo) with modes); the result is on that device."""
     p = plan(img.shape[0], img.shape[1], factor, tile, halo)
     img = _to_device(img, device)
     if micro_batch < 1:
         raise ValueError(f"restore_image: micro_batch must be positive (got {micro_batch})")
     table = torch.tensor(p.windows, dtype=torch.int32).to(img.device)     # uploaded once per image
-    launches = ((table[i:i + micro_batch], p.th, p.tw,
-                 _core_px([(0,) + tuple(w) for w in p.windows[i:i + micro_batch]], [(p.h, p.w)]))
-                for i in range(0, len(p.windows), micro_batch))
-    return _run_launches("restore_image", model, launches, quantise, partial(kernels.tile_gather, img),
-                         lambda cout, dtype: torch.empty((p.h, p.w, cout), dtype=dtype, device=img.device),
-                         kernels.tile_scatter)
+    plain = modes == (0,)
+    group = micro_batch if plain else max(1, micro_batch // _most_modes(modes))
+    launches = ((table[i:i + group], p.th, p.tw,
+                 _core_px([(0,) + tuple(w) for w in p.windows[i:i + group]], [(p.h, p.w)]))
+                for i in range(0, len(p.windows), group))
+    gather, scatter = _plain_io(partial(kernels.tile_gather, img), kernels.tile_scatter) if plain else \
+        (partial(kernels.tile_gather_d8, img), kernels.tile_scatter_mean)
+    return _run_launches("restore_image", model, launches, quantise, gather,
+                         lambda cout, dtype: torch.empty((p.h, p.w, cout), dtype=dtype, device=img.device), scatter, modes)
 
 
 def restore_image(model: Callable, image, *, factor: int = 16, tile: int = TILE, halo: int = HALO,
-                  micro_batch: int = MICRO_BATCH, quantise: bool = True, device=None):
+                  micro_batch: int = MICRO_BATCH, quantise: bool = True, device=None, ensemble=1):
     """Restore one H x W x C image (numpy array or torch tensor, uint8 or float32 in [0, 1], host or device)
     with ``model``, any callable from float32 [n, C, th, tw] to [n, Cout, th, tw].
 
@@ -162,11 +226,19 @@ def restore_image(model: Callable, image, *, factor: int = 16, tile: int = TILE,
     lines, bit for bit), else float32, unclamped.  If the padded image fits ``tile`` on both sides there is
     one window and the result is the whole-image one.  Runs under no_grad with the model in eval mode (its
     mode is restored).  ``device``: where to run when the image is on the host (default: the model's
-    parameters' device, else the current GPU)."""
+    parameters' device, else the current GPU).
+
+    ``ensemble``: 1 (default) restores once; 8 restores under all 8 flips and quarter turns of each window and
+    averages the results turned back (the module docstring has the definition, the mode numbering and the
+    fixed summation order); a strictly ascending sequence of modes of 0..7 takes that subset.  A launch is then
+    max(1, micro_batch // Mo) windows and two model calls, one of th x tw and one of tw x th windows, so the
+    model must take both; the peak memory grows by one output batch.  ``ensemble=1`` and ``(0,)`` run the plain
+    path.  Anything else is a ValueError before any launch."""
+    modes = _ensemble_modes("restore_image", ensemble)
     if device is None and not (isinstance(image, torch.Tensor) and image.is_cuda):
         device = _model_device(model)
     img, kind = _checked_image(image)
-    out = _restore_device(model, img, device, factor, tile, halo, micro_batch, quantise)
+    out = _restore_device(model, img, device, factor, tile, halo, micro_batch, quantise, modes)
     if kind == "numpy":
         return out.cpu().numpy()
     return out.cpu() if kind == "cpu" else out
@@ -249,12 +321,15 @@ def pack_images(images: Sequence, device=None) -> ImagePack:
 
 
 def plan_images(shapes: Sequence[Tuple[int, int]], factor: int = 16, tile: int = TILE, halo: int = HALO,
-                micro_batch: int = MICRO_BATCH) -> List[Tuple[int, int, Tuple[Tuple[int, ...], ...]]]:
+                micro_batch: int = MICRO_BATCH, modes=None) -> List[Tuple[int, int, Tuple[Tuple[int, ...], ...]]]:
     """The launches of a list of (h, w) images (pure Python): ``plan`` per image, all windows grouped by window
     shape (th, tw) in (image, window) order, each group cut into launches of at most
     max(1, micro_batch tile^2 // (th tw)) windows -- the pixels one restore_image launch has, so the peak
-    memory does not grow.  Returns [(th, tw, rows)], rows (img, wr, wc, r0, r1, c0, c1).  ValueError where
-    ``plan`` raises."""
+    memory does not grow.  ``modes`` (what ``ensemble`` takes; default: the plain call): a launch is then two
+    model calls, one per orientation, and holds at most max(1, micro_batch tile^2 // (th tw Mo)) windows, Mo the
+    larger number of modes of one orientation.  Returns [(th, tw, rows)], rows (img, wr, wc, r0, r1, c0, c1).
+    ValueError where ``plan`` raises and for bad modes."""
+    most = _most_modes(_ensemble_modes("plan_images", modes))
     if micro_batch < 1:
         raise ValueError(f"plan_images: micro_batch must be positive (got {micro_batch})")
     groups = {}
@@ -263,14 +338,14 @@ def plan_images(shapes: Sequence[Tuple[int, int]], factor: int = 16, tile: int =
         groups.setdefault((p.th, p.tw), []).extend((i,) + tuple(w) for w in p.windows)
     launches = []
     for (th, tw), rows in groups.items():
-        cap = max(1, (micro_batch * tile * tile) // (th * tw))
+        cap = max(1, (micro_batch * tile * tile) // (th * tw * most))
         launches.extend((th, tw, tuple(rows[k:k + cap])) for k in range(0, len(rows), cap))
     return launches
 
 
-def _restore_pack(model: Callable, pack: ImagePack, launches, quantise: bool) -> ImagePack:
-    """restore_images on a pack: one launch per launch of plan_images; the result is a pack of the same image
-    shapes."""
+def _restore_pack(model: Callable, pack: ImagePack, launches, quantise: bool, modes: Tuple[int, ...] = (0,)) -> ImagePack:
+    """restore_images on a pack: one launch per launch of plan_images (planned with the same modes); the result
+    is a pack of the same image shapes."""
     dev, shapes = pack.arena.device, pack.shapes()
     table = torch.tensor([r for _, _, rows in launches for r in rows], dtype=torch.int32).to(dev)  # one upload
 
@@ -287,22 +362,27 @@ def _restore_pack(model: Callable, pack: ImagePack, launches, quantise: bool) ->
                          pack.table if same else torch.tensor(host_table, dtype=torch.int64).to(dev),
                          host_table, cout, pack.kinds)
 
-    return _run_launches("restore_images", model, sliced(), quantise, partial(kernels.tiles_gather, pack), alloc,
-                         kernels.tiles_scatter)
+    gather, scatter = _plain_io(partial(kernels.tiles_gather, pack), kernels.tiles_scatter) if modes == (0,) else \
+        (partial(kernels.tiles_gather_d8, pack), kernels.tiles_scatter_mean)
+    return _run_launches("restore_images", model, sliced(), quantise, gather, alloc, scatter, modes)
 
 
 def restore_images(model: Callable, images: Sequence, *, factor: int = 16, tile: int = TILE, halo: int = HALO,
-                   micro_batch: int = MICRO_BATCH, quantise: bool = True, device=None) -> list:
+                   micro_batch: int = MICRO_BATCH, quantise: bool = True, device=None, ensemble=1) -> list:
     """restore_image for a list of images of possibly different sizes (one dtype, one C), with windows of
     different images sharing the model's batches: the images go to the device in one arena (pack_images), each
     launch of plan_images is one gather, one model call and one scatter, and the results come back from one
     output arena in input order and of each input's kind.  Equal to
     ``[restore_image(model, im, ...) for im in images]`` byte for byte whenever the model's result for a
-    window does not depend on what else is in the batch."""
+    window does not depend on what else is in the batch.  ``ensemble`` as in restore_image: windows of different
+    images keep sharing launches by window shape (th, tw), and each launch is one even-k and one odd-k model
+    call."""
+    modes = _ensemble_modes("restore_images", ensemble)
     if device is None and not any(isinstance(im, torch.Tensor) and im.is_cuda for im in images):
         device = _model_device(model)
     pack = pack_images(images, device)
-    out = _restore_pack(model, pack, plan_images(pack.shapes(), factor, tile, halo, micro_batch), quantise)
+    out = _restore_pack(model, pack, plan_images(pack.shapes(), factor, tile, halo, micro_batch, modes), quantise,
+                        modes)
     host = out.arena.cpu() if any(isinstance(k, str) for k in out.kinds) else None      # one transfer back
     results = []
     for i, kind in enumerate(out.kinds):
@@ -348,14 +428,15 @@ def psnr_u8(a, b) -> float:
 
 
 def evaluate(model: Callable, images, sigma: float = 25.0, factor: int = 16, seed: int = 2204,
-             across_images: bool = False, **tiling_args) -> Tuple[float, List[float]]:
+             across_images: bool = False, ensemble=1, **tiling_args) -> Tuple[float, List[float]]:
     """``training.validate``'s loop on restore_image: per image, N(0, sigma/255) noise drawn on the host from
     one RandomState(seed) stream in image order, the noisy float image restored, PSNR against
     rint(clean x 255).  Returns (mean PSNR, per-image PSNRs).  tiling_args: tile, halo, micro_batch, device.
 
     ``across_images``: draw the noise for all images first (the same stream, so the same draws), restore them
     with restore_images in shared window batches and take every image's SSE in one launch; the same floats
-    for a batch-independent model."""
+    for a batch-independent model.  ``ensemble`` as in restore_image, on either branch."""
+    modes = _ensemble_modes("evaluate", ensemble)
     device = tiling_args.pop("device", None) or _model_device(model)
     tile, halo = tiling_args.pop("tile", TILE), tiling_args.pop("halo", HALO)
     micro_batch = tiling_args.pop("micro_batch", MICRO_BATCH)
@@ -363,22 +444,24 @@ def evaluate(model: Callable, images, sigma: float = 25.0, factor: int = 16, see
         raise TypeError(f"evaluate: unexpected arguments {sorted(tiling_args)}")
     rs = np.random.RandomState(seed=seed)
     if across_images:
-        return _evaluate_across(model, images, sigma, factor, rs, tile, halo, micro_batch, device)
+        return _evaluate_across(model, images, sigma, factor, rs, tile, halo, micro_batch, device, modes)
     psnrs = []
     for i in range(len(images)):
         clean = np.asarray(images[i], dtype=np.float32)
         img, _ = _checked_image(_noisy(clean, sigma, rs))
-        restored = _restore_device(model, img, device, factor, tile, halo, micro_batch, True)
+        restored = _restore_device(model, img, device, factor, tile, halo, micro_batch, True, modes)
         psnrs.append(psnr_u8(restored, torch.from_numpy(_clean_u8(clean)).to(restored.device)))
     return float(np.mean(psnrs)), psnrs
 
 
-def _evaluate_across(model, images, sigma, factor, rs, tile, halo, micro_batch, device) -> Tuple[float, List[float]]:
+def _evaluate_across(model, images, sigma, factor, rs, tile, halo, micro_batch, device,
+                     modes=(0,)) -> Tuple[float, List[float]]:
     """evaluate(across_images=True): the same draws, the same uint8 images and the same integer SSEs as the
     per-image loop, with the windows of all images in shared batches and one SSE launch."""
     cleans = [np.asarray(images[i], dtype=np.float32) for i in range(len(images))]
     pack = pack_images([_noisy(clean, sigma, rs) for clean in cleans], device)     # all draws first, in image order
-    restored = _restore_pack(model, pack, plan_images(pack.shapes(), factor, tile, halo, micro_batch), True)
+    restored = _restore_pack(model, pack, plan_images(pack.shapes(), factor, tile, halo, micro_batch, modes), True,
+                             modes)
     clean_u8 = pack_images([_clean_u8(c) for c in cleans], restored.arena.device)
     if clean_u8.host_table != restored.host_table:
         raise ValueError(f"evaluate: the model returns {restored.c} channel(s) for {clean_u8.c}; no PSNR")

@@ -763,6 +763,39 @@ grr_status grr_tiles_scatter(const float* y, const int32_t* table, int n, int th
 grr_status grr_u8_sse_segments(const uint8_t* a, const uint8_t* b, int64_t total, const int64_t* offsets, int n_seg,
                                uint64_t* out, void* stream);
 
+/* ---- 8-way geometric self-ensemble of the two families above (restore_image(ensemble=...)).  Mode m = 2k + f
+ * of 0..7 is T_m(a) = np.rot90(a, k) (k quarter turns counter-clockwise), then np.flipud if f = 1 -- the
+ * numbering of the reference's data_augmentation (lib/dataloader*.py).  Pixel (i, j) of a th x tw window lands
+ * where k applications of (i, j, th, tw) <- (tw - 1 - j, i, tw, th), then i <- th - 1 - i if f, put it: T_m is
+ * th x tw for even k (modes 0, 1, 4, 5) and tw x th for odd k (2, 3, 6, 7).  The transforms act on the model's
+ * window, after the reflect rule: the window tables, the padding, the cores and the crop are those of the plain
+ * entry points.  modes: n_modes ints on the HOST, strictly ascending, each in 0..7; they are copied into the
+ * kernel arguments.  A bad list is GRR_ERR_INVALID_ARG before any launch; image, arena and batch checks as in
+ * the plain entry points, with n times the modes of an orientation as the batch's rows. */
+
+/* out[w n_modes + j] = T_modes[j](window w as grr_tile_gather reads it), out: [n n_modes, C, bh, bw].  The modes
+ * of one call share an orientation: all of even k, window w is bh x bw in the picture, or all of odd k, it is
+ * bw x bh.  Element conversion as grr_tile_gather. */
+grr_status grr_tile_gather_d8(const void* img, int img_f32, int H, int W, int C, const int32_t* table, int n,
+                              const int32_t* modes, int n_modes, int bh, int bw, float* out, void* stream);
+/* The mean of the n_modes members z_j = T_modes[j]^-1(model's result) of each th x tw window, then the steps of
+ * grr_tile_scatter (core box, crop, quantisation).  y0: [n n_even, C, th, tw], the even-k members in list order,
+ * window-major as grr_tile_gather_d8 lays them out; y1: [n n_odd, C, tw, th], the odd-k members; either is
+ * ignored (may be NULL) when its count is 0; n_even + n_odd = n_modes and both must be the list's counts.  The
+ * mean is a float32 pairwise tree over the listed order -- [z0 + z1, z2 + z3, ..., the odd one carried], until
+ * one is left -- divided by float(n_modes), correctly rounded.  Each core pixel is written once; no atomics. */
+grr_status grr_tile_scatter_mean(const float* y0, const float* y1, const int32_t* table, int n, const int32_t* modes,
+                                 int n_modes, int n_even, int n_odd, int th, int tw, void* img, int img_f32, int H, int W,
+                                 int C, void* stream);
+/* grr_tile_gather_d8 for window i of image table[i][0] of the arena (table rows [n, 7]). */
+grr_status grr_tiles_gather_d8(const void* arena, int64_t arena_elems, int img_f32, int C, const int64_t* img_table,
+                               int n_img, const int32_t* table, int n, const int32_t* modes, int n_modes, int bh, int bw,
+                               float* out, void* stream);
+/* grr_tile_scatter_mean into each window's own image of the arena. */
+grr_status grr_tiles_scatter_mean(const float* y0, const float* y1, const int32_t* table, int n, const int32_t* modes,
+                                  int n_modes, int n_even, int n_odd, int th, int tw, void* arena, int64_t arena_elems,
+                                  int img_f32, int C, const int64_t* img_table, int n_img, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

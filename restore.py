@@ -2,6 +2,7 @@
 
     python restore.py -yaml_path CONF.yaml --ckpt CHECKPOINT.pt --input FILE_OR_DIR --output DIR \\
            [--sigma S --seed N] [--tile T --halo H --factor F] [--batch-images]
+           [--self-ensemble | --ensemble-modes 0,1,4,5]
 
 The model is ``training.build_model(conf["model"])``; the checkpoint is the training loop's dict (its
 "model" entry).  Without --ckpt the initial weights run, and the tool says so.  Images of any size are read
@@ -11,7 +12,10 @@ noisy image is restored and its PSNR against the input printed, with the mean at
 the input is restored as it is.  With --batch-images all inputs are read first and restored by
 ``irdu_amd.restore_images``, windows of different files sharing the model's batches (files of one mode, all
 RGB or all grey); the noise is still drawn in file order, and the lines printed and the files written are
-the same.
+the same.  With --self-ensemble every window is restored under all 8 flips and quarter turns and the results,
+turned back, are averaged (``ensemble=8``; about 8 times the work); --ensemble-modes takes a subset of the modes
+0..7 (m = 2k + f: k quarter turns counter-clockwise, then an upside-down flip if f), ascending and separated by
+commas.  Both work with --batch-images; the lines printed and the files written keep their formats.
 """
 import argparse
 import os
@@ -46,7 +50,18 @@ def main(argv=None) -> None:
     ap.add_argument("--factor", type=int, default=16)
     ap.add_argument("--batch-images", action="store_true",
                     help="read all inputs first and restore them in shared window batches (restore_images)")
+    group = ap.add_mutually_exclusive_group()
+    group.add_argument("--self-ensemble", action="store_true",
+                       help="average the restorations under all 8 flips and quarter turns (ensemble=8)")
+    group.add_argument("--ensemble-modes", type=str, default=None, metavar="M,M,...",
+                       help="average over these modes of 0..7 only, ascending (e.g. 0,1,4,5)")
     args = ap.parse_args(argv)
+    ensemble = 8 if args.self_ensemble else 1
+    if args.ensemble_modes is not None:
+        try:
+            ensemble = tuple(int(m) for m in args.ensemble_modes.split(","))
+        except ValueError:
+            ap.error(f"--ensemble-modes: expected integers separated by commas, got {args.ensemble_modes!r}")
 
     import numpy as np
     import torch
@@ -54,6 +69,10 @@ def main(argv=None) -> None:
     import irdu_amd
     from irdu_amd import restore, training
 
+    try:
+        restore._ensemble_modes("--ensemble-modes", ensemble)
+    except ValueError as e:
+        raise SystemExit(str(e))
     files = input_files(args.input)
     conf = training.parse_options(args.yaml_path)
     if not torch.cuda.is_available():
@@ -98,7 +117,7 @@ def main(argv=None) -> None:
         imgs = [read(path) for path in files]
         inputs = imgs if args.sigma is None else [noisy_of(img) for img in imgs]       # draws in file order
         try:
-            outs = irdu_amd.restore_images(model, inputs, factor=args.factor, tile=tile, halo=halo)
+            outs = irdu_amd.restore_images(model, inputs, factor=args.factor, tile=tile, halo=halo, ensemble=ensemble)
         except ValueError as e:
             raise SystemExit(f"--batch-images: {e}")
         for path, img, out in zip(files, imgs, outs):
@@ -107,7 +126,7 @@ def main(argv=None) -> None:
         for path in files:
             img = read(path)
             out = irdu_amd.restore_image(model, img if args.sigma is None else noisy_of(img), factor=args.factor,
-                                         tile=tile, halo=halo)
+                                         tile=tile, halo=halo, ensemble=ensemble)
             finish(path, img, out)
     if psnrs:
         print(f"mean PSNR over {len(psnrs)} image(s): {float(np.mean(psnrs)):.4f} dB")
