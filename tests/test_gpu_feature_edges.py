@@ -63,6 +63,43 @@ def test_feature_edges_vs_two_pass_and_float64(K, b, g, h, w):
     assert torch.equal(wG8, wG) and torch.equal(cG8, cG) and torch.equal(wL8, wL)
 
 
+def _segment_rows(b, h, w):
+    """grr_feature_edges' rows per segment (csrc/feature_edge.hip: the sseg loop)."""
+    sseg, strips = h, b * -(-w // 32)
+    while sseg > 32 and strips * -(-h // sseg) < 1024:
+        sseg = (sseg + 1) // 2
+    return sseg
+
+
+def test_one_workgroup_streams_a_long_unsegmented_strip(K):
+    """grr_feature_edges halves its row segments while B ceil(W / 32) nsegs < 1024.  At B = 512, W = 40 (two strips
+    per image, the second 8 columns wide) the launch has 1024 strips already: one workgroup streams all 75 rows
+    of a strip (nine 8-row halo batches through the 11-row ring, then 3 rows), where the shapes above stop at
+    35-row segments.  Against float64 at the tolerances above, bitwise against the same images run 8 at a
+    time (16 strips: 19-row segments; a pixel's arithmetic does not depend on its segment), and the blocked
+    input bitwise."""
+    b, g, h, w = 512, 2, 75, 40
+    c = 3 * g
+    assert _segment_rows(b, h, w) == h and _segment_rows(8, h, w) == 19
+    torch.manual_seed(7540)
+    x = (torch.randn(b, c, h, w) * torch.rand(b, 1, h, w) * 3).to(DEV)
+    wt = (torch.randn(2 * c, c, 1, 1) * 0.2).to(DEV)
+    mG = (0.5 + torch.rand(g, 3)).to(DEV)
+    mL = (0.5 + torch.rand(g, 3)).to(DEV)
+    wG, cG, wL = K.feature_edges(x, False, wt, g, 3, mG, mL)
+    f64 = torch.nn.functional.conv2d(x.double().cpu(), wt.double().cpu())
+    for slab, (got_w, mm) in enumerate(((wG, mG), (wL, mL))):
+        w64, c64 = _edges64(f64[:, slab * c:(slab + 1) * c].reshape(b, g, 3, h, w), mm.double().cpu())
+        assert (got_w.double().cpu() - w64).abs().max().item() < 2e-5, slab
+        if slab == 0:
+            assert (cG.double().cpu() - c64).abs().max().item() < 4e-5
+    for i in range(0, b, 8):
+        pG, pc, pL = K.feature_edges(x[i:i + 8].contiguous(), False, wt, g, 3, mG, mL)
+        assert torch.equal(pG, wG[i:i + 8]) and torch.equal(pc, cG[i:i + 8]) and torch.equal(pL, wL[i:i + 8]), i
+    wG8, cG8, wL8 = K.feature_edges(K.to_c8(x), True, wt, g, 3, mG, mL)
+    assert torch.equal(wG8, wG) and torch.equal(cG8, cG) and torch.equal(wL8, wL)
+
+
 def test_image_filter_fused_edges_close_to_two_pass(K):
     import irdu_amd
     from irdu_amd import graph_filter as GF
