@@ -1548,9 +1548,10 @@ def win_mix(x: Tensor, score: Tensor, dc: Optional[Tensor] = None) -> Tensor:
 
 def win_apply(x: Tensor, edge_delta, n_graphs: int, n_sig: int, *, wL: Optional[Tensor] = None,
               tapsL: Optional[Tensor] = None, mu: Optional[Tensor] = None, wG: Optional[Tensor] = None,
-              tapsG: Optional[Tensor] = None, ro: Optional[Tensor] = None) -> Tensor:
+              tapsG: Optional[Tensor] = None, ro: Optional[Tensor] = None, pair: bool = False) -> Tensor:
     """mu S_L^T (I - W_L) S_L x [wL] + ro S_G^T C^T C S_G x [wG] (grr_win_solver mode 3; the
-    GLRFast / GTVFast.forward of REF7:503-511, :776-782).  x [B,G,Fs,H,W]."""
+    GLRFast / GTVFast.forward of REF7:503-511, :776-782).  x [B,G,Fs,H,W].
+    pair: wG holds win_pair_weights(w_G) (mode 7: the same GTV term from K weights per position)."""
     dev = _check("win_apply", x, wL, tapsL, mu, wG, tapsG, ro)
     delta, k = _delta_arg(edge_delta)
     b, g, c, h, w = x.shape
@@ -1562,9 +1563,11 @@ def win_apply(x: Tensor, edge_delta, n_graphs: int, n_sig: int, *, wL: Optional[
     _check_win_scalars(n_graphs, tapsG=tapsG, tapsL=tapsL, ro=ro, mu=mu)
     out = torch.empty_like(x)
     nbytes = 4 * h * w * (2 * x.numel() // (h * w) + k * b * n_graphs * (int(wL is not None) + int(wG is not None)))
-    _launch("win_solver", nbytes, "grr_win_solver", 3, x.data_ptr(), 0, None, None, _ptr(wL), _ptr(wG), _ptr(tapsL),
-            _ptr(tapsG), _ptr(mu), _ptr(ro), None, None, None, delta, k, out.data_ptr(), None, b, n_graphs, n_sig, h, w,
-            _stream(dev))
+    if pair and wG is None:
+        raise ValueError("win_apply: pair needs the pair weights in wG")
+    _launch("win_solver", nbytes, "grr_win_solver", 7 if pair else 3, x.data_ptr(), 0, None, None, _ptr(wL), _ptr(wG),
+            _ptr(tapsL), _ptr(tapsG), _ptr(mu), _ptr(ro), None, None, None, delta, k, out.data_ptr(), None, b, n_graphs,
+            n_sig, h, w, _stream(dev))
     return out
 
 

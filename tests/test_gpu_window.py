@@ -223,5 +223,8 @@ def test_window_pair_weights_and_pair_solver(wg, name):
     raw1, _ = K.win_solver(1, x, y1, wgt, taps, ro, delta, g, fs)
     got1, _ = K.win_solver(1, x, y1, c, taps, ro, delta, g, fs, pair=True)
     assert rel_err(got1, raw1) <= 1e-5
+    raw3 = K.win_apply(x, delta, g, fs, wL=wl, tapsL=taps, mu=mu, wG=wgt, tapsG=taps, ro=ro)
+    got3 = K.win_apply(x, delta, g, fs, wL=wl, tapsL=taps, mu=mu, wG=c, tapsG=taps, ro=ro, pair=True)
+    assert rel_err(got3, raw3) <= 1e-5
     with pytest.raises(ValueError):
         K.win_solver(2, x, y1, c, taps, ro, delta, g, fs, log_gamma=torch.zeros(g, device=DEV), pair=True)

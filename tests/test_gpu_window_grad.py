@@ -24,6 +24,16 @@ WINDOWS = {"ring3": np.array([1, 1, 1, 1, 0, 1, 1, 1, 1]).reshape(3, 3),
            "diamond5": np.array([0, 0, 1, 0, 0, 0, 1, 1, 1, 0, 1, 1, 0, 1, 1, 0, 1, 1, 1, 0, 0, 0, 1, 0, 0])
            .reshape(5, 5),
            "full5": np.array([1] * 12 + [0] + [1] * 12).reshape(5, 5)}
+# windows no reference model uses, through the runtime-K paths (tests/window_ref.py: K = 4, K = 8 at reach 2, K = 20)
+EXTRA = ("cross4", "plus8", "round20")
+EXTRA_CASES = [(n, fs, (5, 7)) for n in EXTRA for fs in (1, 2)] + [("round20", 2, (2, 3))]
+
+
+def _cw(name):
+    if name in WINDOWS:
+        return WINDOWS[name]
+    from tests.window_ref import WINDOWS as more
+    return more[name]
 
 
 @pytest.fixture(scope="module")
@@ -67,11 +77,22 @@ def _dev(t):
 @pytest.mark.parametrize("term", ["glr", "gtv", "prox"])
 def test_window_term_reverse_vs_oracle(wg, name, term, hw):
     """One operator term  coef * scale[g] * T(Z(P x)): x-gradient, weight, tap and scalar gradients."""
+    _term_reverse(wg, name, term, hw, 3)
+
+
+@pytest.mark.parametrize("name,fs,hw", EXTRA_CASES)
+@pytest.mark.parametrize("term", ["glr", "gtv", "prox"])
+def test_window_term_reverse_vs_oracle_other_windows(wg, name, term, fs, hw):
+    """The same on windows of K = 4, 8 (reach 2) and 20 with one and two signal channels (planes [B,G,Fs])."""
+    _term_reverse(wg, name, term, hw, fs)
+
+
+def _term_reverse(wg, name, term, hw, fs):
     WG = wg[0]
-    cw = WINDOWS[name]
+    cw = _cw(name)
     delta = O.window_edges(cw)
     dl = tuple((int(a), int(c)) for a, c in delta)
-    b, g, fs = 2, 3, 3
+    b, g = 2, 3
     h, w = hw
     gen = torch.Generator().manual_seed(77 + len(delta) + len(term))
     k = len(delta)
@@ -119,10 +140,20 @@ def test_window_term_reverse_vs_oracle(wg, name, term, hw):
 @pytest.mark.parametrize("hw", [(19, 33), (2, 5)])
 @pytest.mark.parametrize("name", sorted(WINDOWS))
 def test_window_edge_weight_reverse_vs_oracle(wg, name, hw):
+    _edge_weight_reverse(wg, name, hw, 5)
+
+
+@pytest.mark.parametrize("name,f,hw", [("ring3", 13, (19, 33)), ("diamond5", 24, (2, 5)), ("full5", 24, (19, 33))])
+def test_window_edge_weight_reverse_vs_oracle_wide_features(wg, name, f, hw):
+    """F > 12: win_edge_weights_kernel<24> and win_feat_bwd_kernel<24>, just past the boundary and at the maximum."""
+    _edge_weight_reverse(wg, name, hw, f)
+
+
+def _edge_weight_reverse(wg, name, hw, f):
     WG = wg[0]
-    delta = O.window_edges(WINDOWS[name])
+    delta = O.window_edges(_cw(name))
     dl = tuple((int(a), int(c)) for a, c in delta)
-    b, g, f = 2, 3, 5
+    b, g = 2, 3
     h, w = hw
     gen = torch.Generator().manual_seed(91 + len(delta))
     feat = torch.randn((b, g * f + 4, h, w), generator=gen, dtype=torch.float64)
@@ -335,10 +366,21 @@ def test_window_fused_gather_equals_planes(wg, name, term, hw):
     """grr_win_bwd_gather_fused (the E / PW terms recomputed where they are gathered; pass 1 writes no
     planes) against pass 1 writing E / PW + grr_win_bwd_gather: l or o, gs, and the weight / scalar
     gradients pass 1 accumulates, to fp32 rounding (the same expressions in two kernels)."""
+    _fused_gather(wg, name, term, hw, 3)
+
+
+@pytest.mark.parametrize("name,fs,hw", EXTRA_CASES)
+@pytest.mark.parametrize("term", ["glr", "gtv", "prox", "prox_tiny"])
+def test_window_fused_gather_equals_planes_other_windows(wg, name, term, fs, hw):
+    """The same on windows of K = 4, 8 (reach 2) and 20 with one and two signal channels."""
+    _fused_gather(wg, name, term, hw, fs)
+
+
+def _fused_gather(wg, name, term, hw, fs):
     K = wg[0].K
-    delta = O.window_edges(WINDOWS[name])
+    delta = O.window_edges(_cw(name))
     dl = tuple((int(a), int(c)) for a, c in delta)
-    b, g, fs = 2, 3, 3
+    b, g = 2, 3
     h, w = hw
     k = len(delta)
     gen = torch.Generator().manual_seed(501 + k + len(term) + h)
