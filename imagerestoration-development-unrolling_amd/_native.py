@@ -175,6 +175,10 @@ SIGNATURES = {
     "grr_tile_scatter_mean": [P, P, P, I, P, I, I, I, I, I, P, I, I, I, I, P],
     "grr_tiles_gather_d8": [P, L, I, I, P, I, P, I, P, I, I, I, P, P],
     "grr_tiles_scatter_mean": [P, P, P, I, P, I, I, I, I, I, P, L, I, I, P, I, P],
+    # SSIM of uint8 images (metric_ops.hip)
+    "grr_u8_ssim_supported": [I, I, I],
+    "grr_u8_ssim": [P, P, I, I, I, P, P],
+    "grr_u8_ssim_images": [P, P, L, I, P, I, I, I, P, P],
 }
 _RESTYPES = {"grr_version": c_int, "grr_last_error": ctypes.c_char_p, "grr_lnb_workspace_bytes": c_int64,
              "grr_conv1x1_workspace_bytes": c_int64, "grr_wgrad_workspace_bytes": c_int64,

@@ -1,0 +1,256 @@
+// Image metrics beside the PSNR's grr_u8_sse (image_ops.hip), gfx950.
+//
+//   grr_u8_ssim         sum over the valid pixels and channels of rint(2^32 s), s the Gaussian-window SSIM of
+//                       two uint8 H x W x C images, as an exact signed 64-bit integer
+//   grr_u8_ssim_images  the same for every image of two arenas that share one image table, in one launch
+//
+// Definition (Wang et al.; skimage's structural_similarity with gaussian_weights, sigma 1.5,
+// use_sample_covariance=False, data_range 255): an 11 x 11 separable Gaussian window, taps
+// g[k] = exp(-(k - 5)^2 / 4.5) / sum; per channel the five filtered moments mx, my, E[x^2], E[y^2], E[xy] at the
+// (H - 10) x (W - 10) pixels whose window lies inside the image; vx = E[x^2] - mx^2, vy likewise,
+// vxy = E[xy] - mx my; s = (2 mx my + C1)(2 vxy + C2) / ((mx^2 + my^2 + C1)(vx + vy + C2)), C1 = 6.5025,
+// C2 = 58.5225.  SSIM is the mean of s over the N = (H - 10)(W - 10) C values: sum / (2^32 N).
+//
+// Every s is float64 from the bytes, in one fixed order -- the horizontal taps k = 0..10 ascending (fma), then
+// the vertical taps ascending (fma), then the formula above with every product and sum rounded on its own (no
+// contraction in this file) -- so a pixel's value does not depend on the tile, the lane or the image's place in
+// an arena.  It is quantised to q = rint(2^32 s) and the q are added as integers (lane, wave, one 64-bit vector
+// atomic per wave): the sum is the same whatever order the atomics land in and whatever the grid is.  |s| <= 1,
+// so |q| <= 2^32 and N < 2^31 values stay below 2^63.  Equal images give num == den bit for bit, s = 1 and
+// q = 2^32 at every pixel.
+//
+// An image is H rows of W C interleaved bytes; output byte column j < (W - 10) C of output row i reads the bytes
+// j + k C, k = 0..10, of the rows i..i + 10.  A 256-thread workgroup owns kSsimCols = 256 output byte columns by
+// kSsimRows = 32 output rows.  Per input row it stages the 256 + 10 C bytes of a and of b as float64 in LDS (one
+// conversion per byte, two buffers, one barrier per row; the next row's bytes are in flight meanwhile), each lane
+// forms its five horizontal sums and keeps the last 11 rows of them in a register ring whose slots are
+// compile-time (the row loop is unrolled by 11), and from the 11th row of the tile on it emits one output row per
+// input row.  Both images are read (32 + 10) / 32 times.  Images start at any byte: all global reads are single
+// bytes, adjacent lanes adjacent bytes.
+//
+// The arena's image table is device data: the offset is clamped into [0, arena_elems), H and W into
+// [1, max_h] x [1, max_w], and every byte index into [0, arena_elems), so a bad table gives a wrong number,
+// never an access outside the arenas.  An image with a side below 11 contributes nothing.
+#include <algorithm>
+
+#include "grr_common.h"
+
+#pragma clang fp contract(off)
+
+namespace grr {
+namespace {
+
+constexpr int kSsimThreads = 256;
+constexpr int kSsimCols = 256;      // output byte columns of a tile (one per lane); kernels.SSIM_TILE[1]
+constexpr int kSsimRows = 32;       // output rows of a tile; kernels.SSIM_TILE[0]
+constexpr int kSsimTaps = 11;
+constexpr int kSsimMaxImages = 65535;   // one grid row (blockIdx.y) per image
+constexpr double kSsimC1 = 6.5025, kSsimC2 = 58.5225;   // (0.01 x 255)^2, (0.03 x 255)^2
+
+// g[k] = exp(-(k - 5)^2 / (2 x 1.5^2)) / sum in float64, as literals so that every host builds the same taps
+struct SsimTaps {
+  double g[kSsimTaps];
+};
+constexpr SsimTaps kTaps = {{0x1.0d956b52a1d70p-10, 0x1.f1fe01ae5a5b8p-8, 0x1.26eb175d83f67p-5, 0x1.bff0fe8e98418p-4,
+                             0x1.b43c3f52b19f2p-3, 0x1.106560aa892c0p-2, 0x1.b43c3f52b19f2p-3, 0x1.bff0fe8e98418p-4,
+                             0x1.26eb175d83f67p-5, 0x1.f1fe01ae5a5b8p-8, 0x1.0d956b52a1d70p-10}};
+
+struct SsimImage {
+  int64_t off;   // first byte of the image in a and in b
+  int H, W;
+};
+
+// grr_u8_ssim: one H x W image at a and b; the caller sized both from (H, W, C).
+struct SsimOne {
+  int H, W;
+  __device__ __forceinline__ SsimImage image(int) const { return SsimImage{0, H, W}; }
+  __device__ __forceinline__ int64_t clamped(int64_t e) const { return e; }
+};
+
+// grr_u8_ssim_images: image blockIdx.y of the device image table [n_img, 3] (element offset, H, W), clamped.
+struct SsimArena {
+  const int64_t* img_table;
+  int64_t elems;
+  int max_h, max_w;
+  __device__ __forceinline__ SsimImage image(int i) const {
+    const int64_t* it = img_table + (int64_t)i * 3;
+    const int64_t off = it[0], h = it[1], w = it[2];
+    return SsimImage{off < 0 ? 0 : (off > elems - 1 ? elems - 1 : off), (int)(h < 1 ? 1 : (h > max_h ? max_h : h)),
+                     (int)(w < 1 ? 1 : (w > max_w ? max_w : w))};
+  }
+  __device__ __forceinline__ int64_t clamped(int64_t e) const { return e < elems - 1 ? e : elems - 1; }   // e >= 0
+};
+
+// byte col of a row that starts at byte row0 and is rowlen long; 0 beyond the row (no valid column reads it)
+template <typename Src>
+__device__ __forceinline__ uint32_t ssim_byte(const uint8_t* __restrict__ p, const Src& src, int64_t row0, int64_t col,
+                                              int64_t rowlen) {
+  return col < rowlen ? (uint32_t)p[src.clamped(row0 + col)] : 0u;
+}
+
+template <int C, typename Src>
+__global__ __launch_bounds__(kSsimThreads) void u8_ssim_kernel(const uint8_t* __restrict__ a,
+                                                               const uint8_t* __restrict__ b, Src src, SsimTaps taps,
+                                                               unsigned long long* out) {
+  constexpr int kExtra = (kSsimTaps - 1) * C;             // bytes a tile's row needs beyond its 256 columns
+  __shared__ double lds[2][2][kSsimCols + kExtra];        // [buffer][a, b][byte column of the tile]
+  const SsimImage im = src.image(blockIdx.y);
+  if (im.H < kSsimTaps || im.W < kSsimTaps) return;       // whole block: before any barrier
+  const int64_t rowlen = (int64_t)im.W * C, vcols = rowlen - kExtra;
+  const int vrows = im.H - (kSsimTaps - 1);
+  const int64_t tcols = (vcols + kSsimCols - 1) / kSsimCols, trows = (vrows + kSsimRows - 1) / kSsimRows;
+  if ((int64_t)blockIdx.x >= tcols * trows) return;       // the grid is the largest image's
+  const int64_t j0 = ((int64_t)blockIdx.x % tcols) * kSsimCols;
+  const int r0 = (int)((int64_t)blockIdx.x / tcols) * kSsimRows;
+  const int rin_end = min(r0 + kSsimRows, vrows) + (kSsimTaps - 1);   // input rows [r0, rin_end), rin_end <= H
+  const int t = threadIdx.x;
+  const bool active = j0 + t < vcols;
+  const bool extra = t < kExtra;
+
+  // the bytes this lane stages for the row in flight: column j0 + t and, for the first 10 C lanes, j0 + 256 + t
+  uint32_t pa0, pb0, pa1 = 0, pb1 = 0;
+  {
+    const int64_t row0 = im.off + (int64_t)r0 * rowlen;
+    pa0 = ssim_byte(a, src, row0, j0 + t, rowlen);
+    pb0 = ssim_byte(b, src, row0, j0 + t, rowlen);
+    if (extra) {
+      pa1 = ssim_byte(a, src, row0, j0 + kSsimCols + t, rowlen);
+      pb1 = ssim_byte(b, src, row0, j0 + kSsimCols + t, rowlen);
+    }
+  }
+
+  double ring[kSsimTaps][5];     // horizontal sums (x, y, x^2, y^2, xy) of the last 11 input rows; slot = (r - r0) % 11
+#pragma unroll
+  for (int p = 0; p < kSsimTaps; ++p)
+#pragma unroll
+    for (int m = 0; m < 5; ++m) ring[p][m] = 0.0;
+  long long acc = 0;
+
+  for (int base = r0; base < rin_end; base += kSsimTaps) {
+#pragma unroll
+    for (int p = 0; p < kSsimTaps; ++p) {
+      const int r = base + p;                  // input row; block-uniform
+      if (r < rin_end) {
+        double* la = lds[(r - r0) & 1][0];
+        double* lb = lds[(r - r0) & 1][1];
+        la[t] = (double)pa0;
+        lb[t] = (double)pb0;
+        if (extra) {
+          la[kSsimCols + t] = (double)pa1;
+          lb[kSsimCols + t] = (double)pb1;
+        }
+        if (r + 1 < rin_end) {
+          const int64_t row0 = im.off + (int64_t)(r + 1) * rowlen;
+          pa0 = ssim_byte(a, src, row0, j0 + t, rowlen);
+          pb0 = ssim_byte(b, src, row0, j0 + t, rowlen);
+          if (extra) {
+            pa1 = ssim_byte(a, src, row0, j0 + kSsimCols + t, rowlen);
+            pb1 = ssim_byte(b, src, row0, j0 + kSsimCols + t, rowlen);
+          }
+        }
+        // this buffer was last read two rows ago, before the previous row's barrier
+        __syncthreads();
+        double hx = 0.0, hy = 0.0, hxx = 0.0, hyy = 0.0, hxy = 0.0;
+#pragma unroll
+        for (int k = 0; k < kSsimTaps; ++k) {
+          const double x = la[t + k * C], y = lb[t + k * C], g = taps.g[k];
+          hx = __builtin_fma(g, x, hx);
+          hy = __builtin_fma(g, y, hy);
+          hxx = __builtin_fma(g, x * x, hxx);      // the products of two bytes are exact
+          hyy = __builtin_fma(g, y * y, hyy);
+          hxy = __builtin_fma(g, x * y, hxy);
+        }
+        ring[p][0] = hx;
+        ring[p][1] = hy;
+        ring[p][2] = hxx;
+        ring[p][3] = hyy;
+        ring[p][4] = hxy;
+        if (r - r0 >= kSsimTaps - 1) {           // output row r - 10: input rows r - 10..r = slots p + 1..p + 11
+          double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+          for (int k = 0; k < kSsimTaps; ++k)
+#pragma unroll
+            for (int m = 0; m < 5; ++m) v[m] = __builtin_fma(taps.g[k], ring[(p + 1 + k) % kSsimTaps][m], v[m]);
+          const double mx = v[0], my = v[1];
+          const double mxx = mx * mx, myy = my * my, mxy = mx * my;
+          const double vx = v[2] - mxx, vy = v[3] - myy, vxy = v[4] - mxy;
+          const double num = (2.0 * mxy + kSsimC1) * (2.0 * vxy + kSsimC2);
+          const double den = (mxx + myy + kSsimC1) * (vx + vy + kSsimC2);
+          const double s = num / den;
+          if (active) acc += __double2ll_rn(s * 4294967296.0);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) acc += __shfl_down(acc, off, kWave);
+  if ((threadIdx.x & (kWave - 1)) == 0 && acc) atomicAdd(out + blockIdx.y, (unsigned long long)acc);
+}
+
+template <typename Src>
+void ssim_launch(int C, dim3 grid, hipStream_t s, const uint8_t* a, const uint8_t* b, const Src& src,
+                 unsigned long long* out) {
+  switch (C) {
+    case 1: hipLaunchKernelGGL((u8_ssim_kernel<1, Src>), grid, dim3(kSsimThreads), 0, s, a, b, src, kTaps, out); break;
+    case 2: hipLaunchKernelGGL((u8_ssim_kernel<2, Src>), grid, dim3(kSsimThreads), 0, s, a, b, src, kTaps, out); break;
+    case 3: hipLaunchKernelGGL((u8_ssim_kernel<3, Src>), grid, dim3(kSsimThreads), 0, s, a, b, src, kTaps, out); break;
+    default: hipLaunchKernelGGL((u8_ssim_kernel<4, Src>), grid, dim3(kSsimThreads), 0, s, a, b, src, kTaps, out); break;
+  }
+}
+
+// tiles of an h x w image with both sides >= 11
+int64_t ssim_tiles(int h, int w, int C) {
+  const int64_t vcols = (int64_t)(w - (kSsimTaps - 1)) * C, vrows = h - (kSsimTaps - 1);
+  return ((vcols + kSsimCols - 1) / kSsimCols) * ((vrows + kSsimRows - 1) / kSsimRows);
+}
+
+}  // namespace
+}  // namespace grr
+
+using namespace grr;
+
+extern "C" {
+
+int grr_u8_ssim_supported(int C, int H, int W) {
+  return C >= 1 && C <= 4 && H >= kSsimTaps && W >= kSsimTaps && (int64_t)H * W * C < (1ll << 31) ? 1 : 0;
+}
+
+grr_status grr_u8_ssim(const uint8_t* a, const uint8_t* b, int H, int W, int C, int64_t* out, void* stream) {
+  clear_error();
+  GRR_REQUIRE(a && b && out && H > 0 && W > 0 && C > 0 && (uintptr_t)out % 8 == 0, GRR_ERR_INVALID_ARG,
+              "grr_u8_ssim: bad args");
+  GRR_REQUIRE(grr_u8_ssim_supported(C, H, W), GRR_ERR_UNSUPPORTED,
+              "grr_u8_ssim: needs C <= 4, H and W >= 11 and H W C < 2^31 (got %d x %d x %d)", H, W, C);
+  hipStream_t s = (hipStream_t)stream;
+  GRR_REQUIRE(hipMemsetAsync(out, 0, sizeof(int64_t), s) == hipSuccess, GRR_ERR_HIP, "grr_u8_ssim: zeroing the sum failed");
+  // tiles <= H W C < 2^31
+  ssim_launch(C, dim3((uint32_t)ssim_tiles(H, W, C)), s, a, b, SsimOne{H, W}, reinterpret_cast<unsigned long long*>(out));
+  return launch_status("grr_u8_ssim");
+}
+
+grr_status grr_u8_ssim_images(const uint8_t* a, const uint8_t* b, int64_t arena_elems, int C, const int64_t* img_table,
+                              int n_img, int max_h, int max_w, int64_t* out, void* stream) {
+  clear_error();
+  GRR_REQUIRE(a && b && img_table && out && arena_elems > 0 && C > 0 && n_img > 0 && max_h > 0 && max_w > 0 &&
+                  (uintptr_t)out % 8 == 0 && (uintptr_t)img_table % 8 == 0,
+              GRR_ERR_INVALID_ARG, "grr_u8_ssim_images: bad args");
+  GRR_REQUIRE(grr_image_arena_supported(C, n_img, arena_elems), GRR_ERR_UNSUPPORTED,
+              "grr_u8_ssim_images: needs C <= 4, n_img <= arena_elems < 2^62 (got C %d, %d images, %lld elements)", C,
+              n_img, (long long)arena_elems);
+  GRR_REQUIRE(n_img <= kSsimMaxImages, GRR_ERR_UNSUPPORTED,
+              "grr_u8_ssim_images: at most %d images per call, one grid row each (got %d)", kSsimMaxImages, n_img);
+  const bool any = max_h >= kSsimTaps && max_w >= kSsimTaps;      // else no image has a valid pixel: all sums are 0
+  const int64_t tiles = any ? ssim_tiles(max_h, max_w, C) : 0;
+  GRR_REQUIRE(tiles < (1ll << 31), GRR_ERR_UNSUPPORTED,
+              "grr_u8_ssim_images: max_h x max_w x C must be below 2^31 tiles of %d x %d (got %d x %d x %d)", kSsimRows,
+              kSsimCols, max_h, max_w, C);
+  hipStream_t s = (hipStream_t)stream;
+  GRR_REQUIRE(hipMemsetAsync(out, 0, sizeof(int64_t) * n_img, s) == hipSuccess, GRR_ERR_HIP,
+              "grr_u8_ssim_images: zeroing the sums failed");
+  if (!any) return GRR_OK;
+  ssim_launch(C, dim3((uint32_t)tiles, (uint32_t)n_img), s, a, b, SsimArena{img_table, arena_elems, max_h, max_w},
+              reinterpret_cast<unsigned long long*>(out));
+  return launch_status("grr_u8_ssim_images");
+}
+
+}  // extern "C"

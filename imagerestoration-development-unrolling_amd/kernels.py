@@ -1835,9 +1835,9 @@ def image_arena_ok(c: int, n_img: int, arena_elems: int) -> bool:
     return 1 <= c <= 4 and 1 <= n_img <= arena_elems < (1 << 62)
 
 
-def _check_pack(name: str, pack) -> Tuple[int, int]:
+def _check_pack(name: str, pack, placed: bool = True) -> Tuple[int, int]:
     """(n_img, C) of an image pack whose host table describes its arena; ValueError before any launch
-    otherwise, RuntimeError for CPU tensors."""
+    otherwise, RuntimeError for CPU tensors (placed=False leaves where the tensors are to _check_placed)."""
     arena, table, host, c = (getattr(pack, f, None) for f in ("arena", "table", "host_table", "c"))
     if not isinstance(arena, Tensor) or arena.dim() != 1 or arena.dtype not in IMAGE_DTYPES:
         raise ValueError(f"{name}: the arena is a 1-D uint8 or float32 tensor, got "
@@ -1859,11 +1859,17 @@ def _check_pack(name: str, pack) -> Tuple[int, int]:
         end = off + h * w * c
         if end > arena.numel():
             raise ValueError(f"{name}: image {i} ends at element {end} of an arena of {arena.numel()}")
+    if placed:
+        _check_placed(name, pack)
+    return n_img, c
+
+
+def _check_placed(name: str, pack) -> None:
+    arena, table = pack.arena, pack.table
     if not arena.is_cuda:
         raise RuntimeError(f"{name}: tensors must be on the GPU (got {arena.device}); the HIP engine has no CPU path")
     if table.device != arena.device or not table.is_contiguous() or not arena.is_contiguous():
         raise ValueError(f"{name}: the arena and the image table must be contiguous and on one device")
-    return n_img, c
 
 
 def _arena_args(pack, n_img: int, c: int) -> tuple:
@@ -2041,4 +2047,78 @@ def u8_sse_segments(a: Tensor, b: Tensor, offsets) -> List[int]:
     out = torch.empty(n_seg, dtype=torch.int64, device=a.device)
     _launch("u8_sse_segments", 2 * a.numel(), "grr_u8_sse_segments", a.data_ptr(), b.data_ptr(), a.numel(),
             offs.data_ptr(), n_seg, out.data_ptr(), _stream(a.device))
+    return [int(v) for v in out.tolist()]
+
+
+# ---------------------------------------------------------------------------
+# SSIM of uint8 images (csrc/metric_ops.hip; include/grr.h has the definition).  Both calls return sum q, the exact
+# integer sum of q = rint(2^32 s) over the N = (H - 10)(W - 10) C valid values; SSIM = sum q / (2^32 N)
+# (restore.ssim_u8 divides).
+SSIM_WINDOW = 11              # the Gaussian window's side: an image side below it has no SSIM
+SSIM_TILE = (32, 256)         # a workgroup's output rows and interleaved output byte columns ((W - 10) C per row)
+SSIM_ONE = 1 << 32            # q of s = 1
+MAX_SSIM_IMAGES = 65535       # grr_u8_ssim_images: one grid row per image
+
+
+def ssim_ok(c: int, h: int, w: int) -> bool:
+    """grr_u8_ssim_supported in plain Python (tests/test_ssim_abi.py checks the two agree): 1 <= C <= 4, both
+    sides at least 11, H W C < 2^31."""
+    return 1 <= c <= 4 and h >= SSIM_WINDOW and w >= SSIM_WINDOW and h * w * c < (1 << 31)
+
+
+def ssim_count(c: int, h: int, w: int) -> int:
+    """N: the values the SSIM of an H x W x C image is the mean of."""
+    return (h - SSIM_WINDOW + 1) * (w - SSIM_WINDOW + 1) * c
+
+
+def _ssim_flops(n: int) -> int:
+    return 2 * 110 * n      # 55 horizontal and 55 vertical float64 FMAs per value
+
+
+def u8_ssim(a: Tensor, b: Tensor) -> int:
+    """sum of rint(2^32 s) over the valid pixels and channels of two H x W x C uint8 device images, exact (a
+    Python int; synchronises).  Equal images give ssim_count(C, H, W) << 32."""
+    for t in (a, b):
+        if not isinstance(t, Tensor) or t.dtype != torch.uint8 or t.dim() != 3:
+            raise ValueError("u8_ssim: expected H x W x C uint8 tensors, got "
+                             f"{tuple(getattr(t, 'shape', ()))} {getattr(t, 'dtype', type(t))}")
+    h, w, c = a.shape
+    if a.shape != b.shape or not ssim_ok(c, h, w):
+        raise ValueError(f"u8_ssim: shapes {tuple(a.shape)} / {tuple(b.shape)} must match, with C <= 4, both sides at "
+                         f"least {SSIM_WINDOW} and below 2^31 elements")
+    if not (a.is_cuda and b.is_cuda and a.device == b.device):
+        raise RuntimeError("u8_ssim: tensors must be on one GPU; the HIP engine has no CPU path")
+    a, b = a.contiguous(), b.contiguous()
+    out = torch.empty(1, dtype=torch.int64, device=a.device)
+    _launch("u8_ssim", 2 * a.numel(), "grr_u8_ssim", a.data_ptr(), b.data_ptr(), h, w, c, out.data_ptr(),
+            _stream(a.device), flops=_ssim_flops(ssim_count(c, h, w)))
+    return int(out.item())
+
+
+def u8_ssim_images(a_pack, b_pack) -> List[int]:
+    """[u8_ssim of image i of the two packs for each i] in one launch: exact Python ints, one device-to-host copy
+    of the sums (synchronises).  The packs (restore.ImagePack: uint8 arenas) describe the same images: equal host
+    tables, one device; every image has both sides at least 11."""
+    n_img, c = _check_pack("u8_ssim_images", a_pack, placed=False)
+    _check_pack("u8_ssim_images", b_pack, placed=False)
+    a, b = a_pack.arena, b_pack.arena
+    if a.dtype != torch.uint8 or b.dtype != torch.uint8:
+        raise ValueError(f"u8_ssim_images: expected uint8 arenas, got {a.dtype} and {b.dtype}")
+    host = tuple(tuple(int(v) for v in row) for row in a_pack.host_table)
+    if host != tuple(tuple(int(v) for v in row) for row in b_pack.host_table) or b_pack.c != c or a.numel() != b.numel():
+        raise ValueError("u8_ssim_images: the two packs must hold the same images (equal host tables, C and arena "
+                         "lengths)")
+    for i, (_, h, w) in enumerate(host):
+        if not ssim_ok(c, h, w):
+            raise ValueError(f"u8_ssim_images: image {i} needs both sides at least {SSIM_WINDOW} (got {h} x {w} x {c})")
+    if n_img > MAX_SSIM_IMAGES:
+        raise ValueError(f"u8_ssim_images: 1..{MAX_SSIM_IMAGES} images per call (got {n_img})")
+    _check_placed("u8_ssim_images", a_pack)
+    _check_placed("u8_ssim_images", b_pack)
+    if a.device != b.device:
+        raise ValueError("u8_ssim_images: the two packs must be on one device")
+    out = torch.empty(n_img, dtype=torch.int64, device=a.device)
+    _launch("u8_ssim_images", 2 * a.numel(), "grr_u8_ssim_images", a.data_ptr(), b.data_ptr(), a.numel(), c,
+            a_pack.table.data_ptr(), n_img, max(h for _, h, _ in host), max(w for _, _, w in host), out.data_ptr(),
+            _stream(a.device), flops=_ssim_flops(sum(ssim_count(c, h, w) for _, h, w in host)))
     return [int(v) for v in out.tolist()]

@@ -41,6 +41,11 @@ max(1, micro_batch // Mo) windows, Mo the larger number of modes of one orientat
 than a plain call's -- except where micro_batch < Mo, when a call holds the Mo rows of one window.  The peak
 memory grows by one output batch: the even-k results are alive while the odd-k ones are computed.
 
+Metrics: ``psnr_u8`` from the exact integer SSE (``kernels.u8_sse``) and ``ssim_u8``, the 11 x 11 Gaussian-window
+SSIM, from the exact integer sum of the per-pixel values quantised to 2^-32 (``kernels.u8_ssim``; float64 per
+pixel on the device).  ``evaluate`` returns the PSNRs, ``evaluate_metrics`` both, from one body; with
+``across_images`` each metric of all images is one launch on the restored and the clean arena.
+
 Single process: several ranks are ``tiling.tiled_forward``'s business.
 """
 from __future__ import annotations
@@ -395,10 +400,10 @@ def restore_images(model: Callable, images: Sequence, *, factor: int = 16, tile:
     return results
 
 
-def _as_device_u8(x, device) -> torch.Tensor:
+def _as_device_u8(x, device, who: str = "psnr_u8") -> torch.Tensor:
     t = torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x
     if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
-        raise ValueError(f"psnr_u8: expected uint8 images, got {getattr(t, 'dtype', type(t).__name__)}")
+        raise ValueError(f"{who}: expected uint8 images, got {getattr(t, 'dtype', type(t).__name__)}")
     return t if t.is_cuda and device is None else t.to(device if device is not None else "cuda")
 
 
@@ -417,14 +422,80 @@ def _clean_u8(clean: np.ndarray) -> np.ndarray:
     return np.rint(clean.astype(np.float64) * 255.0).astype(np.uint8)
 
 
+def _u8_pair(who: str, a, b) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Two uint8 images of one shape (numpy or tensor, host or device) as tensors on one GPU."""
+    dev = next((t.device for t in (a, b) if isinstance(t, torch.Tensor) and t.is_cuda), None)
+    ta, tb = _as_device_u8(a, dev, who), _as_device_u8(b, dev, who)
+    if ta.shape != tb.shape:
+        raise ValueError(f"{who}: shapes differ ({tuple(ta.shape)} vs {tuple(tb.shape)})")
+    return ta, tb.to(ta.device)
+
+
 def psnr_u8(a, b) -> float:
     """PSNR of two uint8 images of one shape: 10 log10(255^2 N / SSE) in float64 from the exact integer SSE
     (kernels.u8_sse), so it does not depend on any summation order; inf for equal images."""
-    dev = next((t.device for t in (a, b) if isinstance(t, torch.Tensor) and t.is_cuda), None)
-    ta, tb = _as_device_u8(a, dev), _as_device_u8(b, dev)
-    if ta.shape != tb.shape:
-        raise ValueError(f"psnr_u8: shapes differ ({tuple(ta.shape)} vs {tuple(tb.shape)})")
-    return _psnr(kernels.u8_sse(ta, tb.to(ta.device)), ta.numel())
+    ta, tb = _u8_pair("psnr_u8", a, b)
+    return _psnr(kernels.u8_sse(ta, tb), ta.numel())
+
+
+def _ssim(q: int, n: int) -> float:
+    """sum q / (2^32 n), one integer true division: the correctly rounded float64 of the exact quotient."""
+    return q / (kernels.SSIM_ONE * n)
+
+
+def ssim_u8(a, b) -> float:
+    """SSIM of two uint8 H x W x C images of one shape (numpy or tensor, host or device), as
+    ``skimage.metrics.structural_similarity(a, b, gaussian_weights=True, sigma=1.5, use_sample_covariance=False,
+    data_range=255, channel_axis=2)`` defines it: 11 x 11 Gaussian window, the mean over the (H - 10)(W - 10) C
+    values whose window lies inside the image.  Each value is float64 on the device, quantised to a multiple of
+    2^-32 and summed as an integer (kernels.u8_ssim), so the result is within 2^-32 of the float64 mean, the same
+    on every run and independent of any summation order; exactly 1.0 for equal images.  ValueError for a side
+    below 11."""
+    ta, tb = _u8_pair("ssim_u8", a, b)
+    if ta.dim() != 3 or not kernels.ssim_ok(ta.shape[2], ta.shape[0], ta.shape[1]):
+        raise ValueError(f"ssim_u8: expected H x W x C images with C <= 4 and both sides at least "
+                         f"{kernels.SSIM_WINDOW}, got {tuple(ta.shape)}")
+    return _ssim(kernels.u8_ssim(ta, tb), kernels.ssim_count(ta.shape[2], ta.shape[0], ta.shape[1]))
+
+
+METRICS = ("psnr", "ssim")
+
+
+def _evaluate(who: str, model: Callable, images, sigma: float, factor: int, seed: int, across_images: bool, ensemble,
+              metrics, tiling_args: dict) -> dict:
+    """The one body of evaluate and evaluate_metrics: {metric: (mean, per-image values)} for the metrics asked
+    for.  The draws, the restorations and the launches of one metric do not depend on which others are asked
+    for."""
+    modes = _ensemble_modes(who, ensemble)
+    metrics = (metrics,) if isinstance(metrics, str) else tuple(metrics)
+    if not metrics or any(m not in METRICS for m in metrics) or len(set(metrics)) != len(metrics):
+        raise ValueError(f"{who}: metrics are distinct names of {METRICS}, got {metrics!r}")
+    device = tiling_args.pop("device", None) or _model_device(model)
+    tile, halo = tiling_args.pop("tile", TILE), tiling_args.pop("halo", HALO)
+    micro_batch = tiling_args.pop("micro_batch", MICRO_BATCH)
+    if tiling_args:
+        raise TypeError(f"{who}: unexpected arguments {sorted(tiling_args)}")
+    if "ssim" in metrics:       # before any draw
+        for i in range(len(images)):
+            shape = np.shape(images[i])
+            if len(shape) != 3 or min(shape[:2]) < kernels.SSIM_WINDOW:
+                raise ValueError(f"{who}: image {i} is {tuple(shape)}; SSIM needs an H x W x C image with both sides at "
+                                 f"least {kernels.SSIM_WINDOW}")
+    rs = np.random.RandomState(seed=seed)
+    if across_images:
+        values = _evaluate_across(model, images, sigma, factor, rs, tile, halo, micro_batch, device, modes, metrics)
+    else:
+        values = {m: [] for m in metrics}
+        for i in range(len(images)):
+            clean = np.asarray(images[i], dtype=np.float32)
+            img, _ = _checked_image(_noisy(clean, sigma, rs))
+            restored = _restore_device(model, img, device, factor, tile, halo, micro_batch, True, modes)
+            clean_u8 = torch.from_numpy(_clean_u8(clean)).to(restored.device)
+            if "psnr" in metrics:
+                values["psnr"].append(psnr_u8(restored, clean_u8))
+            if "ssim" in metrics:
+                values["ssim"].append(ssim_u8(restored, clean_u8))
+    return {m: (float(np.mean(values[m])), values[m]) for m in metrics}
 
 
 def evaluate(model: Callable, images, sigma: float = 25.0, factor: int = 16, seed: int = 2204,
@@ -436,28 +507,26 @@ def evaluate(model: Callable, images, sigma: float = 25.0, factor: int = 16, see
     ``across_images``: draw the noise for all images first (the same stream, so the same draws), restore them
     with restore_images in shared window batches and take every image's SSE in one launch; the same floats
     for a batch-independent model.  ``ensemble`` as in restore_image, on either branch."""
-    modes = _ensemble_modes("evaluate", ensemble)
-    device = tiling_args.pop("device", None) or _model_device(model)
-    tile, halo = tiling_args.pop("tile", TILE), tiling_args.pop("halo", HALO)
-    micro_batch = tiling_args.pop("micro_batch", MICRO_BATCH)
-    if tiling_args:
-        raise TypeError(f"evaluate: unexpected arguments {sorted(tiling_args)}")
-    rs = np.random.RandomState(seed=seed)
-    if across_images:
-        return _evaluate_across(model, images, sigma, factor, rs, tile, halo, micro_batch, device, modes)
-    psnrs = []
-    for i in range(len(images)):
-        clean = np.asarray(images[i], dtype=np.float32)
-        img, _ = _checked_image(_noisy(clean, sigma, rs))
-        restored = _restore_device(model, img, device, factor, tile, halo, micro_batch, True, modes)
-        psnrs.append(psnr_u8(restored, torch.from_numpy(_clean_u8(clean)).to(restored.device)))
-    return float(np.mean(psnrs)), psnrs
+    return _evaluate("evaluate", model, images, sigma, factor, seed, across_images, ensemble, ("psnr",),
+                     tiling_args)["psnr"]
 
 
-def _evaluate_across(model, images, sigma, factor, rs, tile, halo, micro_batch, device,
-                     modes=(0,)) -> Tuple[float, List[float]]:
-    """evaluate(across_images=True): the same draws, the same uint8 images and the same integer SSEs as the
-    per-image loop, with the windows of all images in shared batches and one SSE launch."""
+def evaluate_metrics(model: Callable, images, sigma: float = 25.0, factor: int = 16, seed: int = 2204,
+                     across_images: bool = False, ensemble=1, metrics=("psnr", "ssim"), **tiling_args) -> dict:
+    """``evaluate`` for several metrics of the same restorations: {"psnr": (mean, per-image), "ssim": (mean,
+    per-image)} for the names in ``metrics``.  The "psnr" entry is evaluate's result bit for bit (one body, the
+    same draws); "ssim" is ssim_u8 of each restored image against rint(clean x 255).  With ``across_images`` the
+    SSIM of all images is one kernels.u8_ssim_images launch on the restored and the clean arena.  An unknown
+    metric name, and with "ssim" an image with a side below 11, is a ValueError before any draw."""
+    return _evaluate("evaluate_metrics", model, images, sigma, factor, seed, across_images, ensemble, metrics,
+                     tiling_args)
+
+
+def _evaluate_across(model, images, sigma, factor, rs, tile, halo, micro_batch, device, modes=(0,),
+                     metrics=("psnr",)) -> dict:
+    """_evaluate(across_images=True): the same draws, the same uint8 images and the same integer sums as the
+    per-image loop, with the windows of all images in shared batches and one launch per metric.  Returns
+    {metric: per-image values}."""
     cleans = [np.asarray(images[i], dtype=np.float32) for i in range(len(images))]
     pack = pack_images([_noisy(clean, sigma, rs) for clean in cleans], device)     # all draws first, in image order
     restored = _restore_pack(model, pack, plan_images(pack.shapes(), factor, tile, halo, micro_batch, modes), True,
@@ -465,7 +534,12 @@ def _evaluate_across(model, images, sigma, factor, rs, tile, halo, micro_batch, 
     clean_u8 = pack_images([_clean_u8(c) for c in cleans], restored.arena.device)
     if clean_u8.host_table != restored.host_table:
         raise ValueError(f"evaluate: the model returns {restored.c} channel(s) for {clean_u8.c}; no PSNR")
-    offsets = [off for off, _, _ in restored.host_table] + [restored.arena.numel()]
-    sses = kernels.u8_sse_segments(restored.arena, clean_u8.arena, offsets)
-    psnrs = [_psnr(sse, h * w * restored.c) for sse, (_, h, w) in zip(sses, restored.host_table)]
-    return float(np.mean(psnrs)), psnrs
+    values = {}
+    if "psnr" in metrics:
+        offsets = [off for off, _, _ in restored.host_table] + [restored.arena.numel()]
+        sses = kernels.u8_sse_segments(restored.arena, clean_u8.arena, offsets)
+        values["psnr"] = [_psnr(sse, h * w * restored.c) for sse, (_, h, w) in zip(sses, restored.host_table)]
+    if "ssim" in metrics:
+        qs = kernels.u8_ssim_images(restored, clean_u8)
+        values["ssim"] = [_ssim(q, kernels.ssim_count(restored.c, h, w)) for q, (_, h, w) in zip(qs, restored.host_table)]
+    return values

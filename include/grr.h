@@ -796,6 +796,34 @@ grr_status grr_tiles_scatter_mean(const float* y0, const float* y1, const int32_
                                   int n_modes, int n_even, int n_odd, int th, int tw, void* arena, int64_t arena_elems,
                                   int img_f32, int C, const int64_t* img_table, int n_img, void* stream);
 
+/* ---- SSIM of two uint8 H x W x C images (csrc/metric_ops.hip), beside grr_u8_sse's PSNR.  Wang et al.'s index as
+ * skimage.metrics.structural_similarity(a, b, gaussian_weights=True, sigma=1.5, use_sample_covariance=False,
+ * data_range=255, channel_axis=2) defines it: an 11 x 11 separable Gaussian window with float64 taps
+ * g[k] = exp(-(k - 5)^2 / 4.5) / sum; per channel the filtered moments mx, my, E[x^2], E[y^2], E[xy] at the
+ * (H - 10) x (W - 10) pixels whose window lies inside the image (no border rule exists); vx = E[x^2] - mx^2,
+ * vy = E[y^2] - my^2, vxy = E[xy] - mx my; C1 = 6.5025, C2 = 58.5225;
+ * s = (2 mx my + C1)(2 vxy + C2) / ((mx^2 + my^2 + C1)(vx + vy + C2)); SSIM = the mean of s over the
+ * N = (H - 10)(W - 10) C values.  Each s is float64 from the bytes in one fixed order (horizontal taps ascending,
+ * then vertical taps ascending), quantised to q = rint(2^32 s), |q| <= 2^32, and the q are added as signed 64-bit
+ * integers: the entry points return sum q, which is exact, the same on every run and independent of the grid and
+ * of what else an arena holds; SSIM = sum q / (2^32 N), within 2^-32 of the float64 mean.  Equal images give
+ * exactly N 2^32. */
+
+/* 1 where grr_u8_ssim takes the image: 1 <= C <= 4, H, W >= 11 and H W C < 2^31. */
+int grr_u8_ssim_supported(int C, int H, int W);
+/* *out = sum q over the image pair a, b (HWC, contiguous, any byte address); out: one 8-byte aligned int64 on the
+ * device, overwritten.  GRR_ERR_UNSUPPORTED where grr_u8_ssim_supported is 0. */
+grr_status grr_u8_ssim(const uint8_t* a, const uint8_t* b, int H, int W, int C, int64_t* out, void* stream);
+/* out[i] = sum q of image i of the arenas a and b, which share arena_elems and the image table (int64 [n_img, 3]
+ * on the device, 8-byte aligned, rows (element offset, H, W), as grr_tiles_gather takes it), in one launch.
+ * max_h, max_w: the largest H and the largest W of the table, which the host cannot read here; they size the grid.
+ * The table is clamped -- offset into [0, arena_elems), H into [1, max_h], W into [1, max_w], every byte index
+ * into [0, arena_elems) -- so a bad table gives wrong sums, never an access outside the arenas.  An image with a
+ * side below 11 has no valid pixel: its sum is 0.  out: n_img 8-byte aligned int64 on the device, overwritten.
+ * n_img <= 65535 (one grid row per image), else GRR_ERR_UNSUPPORTED. */
+grr_status grr_u8_ssim_images(const uint8_t* a, const uint8_t* b, int64_t arena_elems, int C, const int64_t* img_table,
+                              int n_img, int max_h, int max_w, int64_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

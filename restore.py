@@ -1,7 +1,7 @@
 """Restore image files with a trained model (irdu_amd.restore; single process, one GPU).
 
     python restore.py -yaml_path CONF.yaml --ckpt CHECKPOINT.pt --input FILE_OR_DIR --output DIR \\
-           [--sigma S --seed N] [--tile T --halo H --factor F] [--batch-images]
+           [--sigma S --seed N [--ssim]] [--tile T --halo H --factor F] [--batch-images]
            [--self-ensemble | --ensemble-modes 0,1,4,5]
 
 The model is ``training.build_model(conf["model"])``; the checkpoint is the training loop's dict (its
@@ -15,7 +15,9 @@ RGB or all grey); the noise is still drawn in file order, and the lines printed 
 the same.  With --self-ensemble every window is restored under all 8 flips and quarter turns and the results,
 turned back, are averaged (``ensemble=8``; about 8 times the work); --ensemble-modes takes a subset of the modes
 0..7 (m = 2k + f: k quarter turns counter-clockwise, then an upside-down flip if f), ascending and separated by
-commas.  Both work with --batch-images; the lines printed and the files written keep their formats.
+commas.  Both work with --batch-images; the lines printed and the files written keep their formats.  With --ssim
+(only with --sigma) each line also carries the SSIM of the restored image against the input (``irdu_amd.ssim_u8``:
+11 x 11 Gaussian window, both sides at least 11 pixels) and the mean SSIM follows the mean PSNR.
 """
 import argparse
 import os
@@ -45,6 +47,7 @@ def main(argv=None) -> None:
     ap.add_argument("--output", type=str, required=True, help="directory for the restored images (PNG)")
     ap.add_argument("--sigma", type=float, default=None, help="treat inputs as clean: add this noise, report PSNR")
     ap.add_argument("--seed", type=int, default=2204)
+    ap.add_argument("--ssim", action="store_true", help="with --sigma: report the SSIM beside the PSNR")
     ap.add_argument("--tile", type=int, default=None)
     ap.add_argument("--halo", type=int, default=None)
     ap.add_argument("--factor", type=int, default=16)
@@ -56,6 +59,8 @@ def main(argv=None) -> None:
     group.add_argument("--ensemble-modes", type=str, default=None, metavar="M,M,...",
                        help="average over these modes of 0..7 only, ascending (e.g. 0,1,4,5)")
     args = ap.parse_args(argv)
+    if args.ssim and args.sigma is None:
+        ap.error("--ssim needs --sigma: there is nothing to compare a restored image with otherwise")
     ensemble = 8 if args.self_ensemble else 1
     if args.ensemble_modes is not None:
         try:
@@ -89,7 +94,7 @@ def main(argv=None) -> None:
     halo = restore.HALO if args.halo is None else args.halo
     os.makedirs(args.output, exist_ok=True)
     rs = np.random.RandomState(seed=args.seed)
-    psnrs = []
+    psnrs, ssims = [], []
 
     def read(path):
         img = np.array(Image.open(path))
@@ -110,7 +115,14 @@ def main(argv=None) -> None:
             if out.shape != img.shape:
                 raise SystemExit(f"{path}: the model returns {out.shape[2]} channels for {img.shape[2]}; no PSNR")
             psnrs.append(irdu_amd.psnr_u8(out, img))
-            print(f"{path} -> {out_path}  sigma {args.sigma:g}  PSNR {psnrs[-1]:.4f} dB")
+            line = f"{path} -> {out_path}  sigma {args.sigma:g}  PSNR {psnrs[-1]:.4f} dB"
+            if args.ssim:
+                try:
+                    ssims.append(irdu_amd.ssim_u8(out, img))
+                except ValueError as e:
+                    raise SystemExit(f"{path}: {e}")
+                line += f"  SSIM {ssims[-1]:.4f}"
+            print(line)
         Image.fromarray(out[:, :, 0] if out.shape[2] == 1 else out).save(out_path)
 
     if args.batch_images:
@@ -130,6 +142,8 @@ def main(argv=None) -> None:
             finish(path, img, out)
     if psnrs:
         print(f"mean PSNR over {len(psnrs)} image(s): {float(np.mean(psnrs)):.4f} dB")
+    if ssims:
+        print(f"mean SSIM over {len(ssims)} image(s): {float(np.mean(ssims)):.4f}")
 
 
 if __name__ == "__main__":
