@@ -1,0 +1,174 @@
+"""Batches per second of the two ways to feed training from pictures on disk (no model runs):
+
+  host    training.ImageSuperResolution under torch's DataLoader (num_workers=4, the reference's setting), each
+          batch then sent to the GPU and made planar as Trainer.step does
+  device  training.DevicePatchLoader: the pictures decoded once into an arena on the GPU, one kernels.patch_batch
+          call per batch (the one-off decode + pack is reported apart)
+
+at the four shapes of the v2 curriculum (128^2 x 4, 192^2 x 3, 256^2 x 2, 384^2 x 1) and at C4's 32 x 512^2, on
+synthetic PNGs written to a temporary folder, and then the device loader alone on a file count like a training
+set's (8600 small pictures), where a host cost per batch that grew with the number of files would show.  Prints
+one JSON line per shape and one for the many-files run.
+
+    python bench_data.py [--steps 60] [--warmup 10] [--images 12] [--side 1200] [--workers 4] [--files 8600]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import logging
+import os
+import tempfile
+import time
+
+import numpy as np
+import torch
+
+SHAPES = ((4, 128), (3, 192), (2, 256), (1, 384), (32, 512))
+
+
+def write_pictures(folder: str, n: int, side: int, seed: int = 7) -> str:
+    """n RGB PNGs (side x side, and every third one smaller than a crop's 800-pixel threshold) and their csv:
+    smooth ramps plus noise, so the files neither compress away nor decode faster than photographs do."""
+    from PIL import Image
+    rs = np.random.RandomState(seed)
+    lines = ["index,path,height,width,nchannels"]
+    for k in range(n):
+        h, w = (side, side + 64) if k % 3 else (640, 720)
+        yy, xx = np.mgrid[0:h, 0:w]
+        base = np.stack([(yy * (k + 1) + xx * 2) % 256, (yy + xx * (k + 2)) % 256, (yy * 3 + xx) % 256], axis=2)
+        img = np.clip(base * 0.6 + rs.randint(0, 103, size=(h, w, 3)), 0, 255).astype(np.uint8)
+        Image.fromarray(img).save(os.path.join(folder, f"img{k:03d}.png"))
+        lines.append(f"{k},img{k:03d}.png,{h},{w},3")
+    csv_path = os.path.join(folder, "info.csv")
+    with open(csv_path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    return csv_path
+
+
+def write_small_pictures(folder: str, n: int, side: int, seed: int = 11) -> str:
+    """n small RGB PNGs (side x side, shifts of one noisy ramp, lightly compressed so writing them is quick) and
+    their csv: a file count like a training set's at little disk and decode cost."""
+    from PIL import Image
+    rs = np.random.RandomState(seed)
+    yy, xx = np.mgrid[0:side, 0:side]
+    base = np.clip(np.stack([yy * 2 + xx, yy + xx * 3, yy * 3 + xx * 2], axis=2) % 256 * 0.6
+                   + rs.randint(0, 103, size=(side, side, 3)), 0, 255).astype(np.uint8)
+    lines = ["index,path,height,width,nchannels"]
+    for k in range(n):
+        Image.fromarray(np.roll(base, (k * 7) % side, axis=(k // side) % 2)).save(
+            os.path.join(folder, f"s{k:05d}.png"), compress_level=1)
+        lines.append(f"{k},s{k:05d}.png,{side},{side},3")
+    csv_path = os.path.join(folder, "info.csv")
+    with open(csv_path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    return csv_path
+
+
+def timed(batches, warmup: int, steps: int, to_device) -> float:
+    """Seconds per batch over ``steps`` batches after ``warmup`` (worker start-up and first launches excluded)."""
+    it = iter(batches)
+    for _ in range(warmup):
+        to_device(next(it))
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        to_device(next(it))
+    torch.cuda.synchronize()
+    dt = (time.perf_counter() - t0) / steps
+    del it
+    return dt
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    # the DataLoader's workers hold up to 2 batches each in flight when the clock starts: enough timed batches
+    # that those 8 are a small share
+    ap.add_argument("--steps", type=int, default=60)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--device-steps", type=int, default=3000, help="timed batches of the device loader")
+    ap.add_argument("--images", type=int, default=12)
+    ap.add_argument("--side", type=int, default=1200)
+    ap.add_argument("--workers", type=int, default=4)
+    ap.add_argument("--files", type=int, default=8600,
+                    help="files of the many-files measurement of the device loader (0: skip it)")
+    ap.add_argument("--small-side", type=int, default=160, help="side of its pictures")
+    args = ap.parse_args()
+    import irdu_amd
+    irdu_amd.load_native()
+    from irdu_amd import kernels, training
+    dev = torch.device("cuda:0")
+    log = logging.getLogger("bench_data")
+
+    def planar(pair):        # what Trainer.step does with a host batch
+        return [t.to(dev, non_blocking=True).permute(0, 3, 1, 2).contiguous() for t in pair]
+
+    shared: dict = {}        # the shapes read one set of files: one arena
+    with tempfile.TemporaryDirectory() as folder:
+        csv_path = write_pictures(folder, args.images, args.side)
+        for batch, size in SHAPES:
+            n = (args.steps + args.warmup + 1) * batch
+            ds = training.ImageSuperResolution(csv_path=csv_path, root_folder=folder, dist_mode="addictive_noise_scale",
+                                               lambda_noise=25.0, use_data_aug=True, patch_size=(size, size),
+                                               max_num_patchs=n, logger=log)
+            host = torch.utils.data.DataLoader(ds, sampler=training.ResumeableSampler(ds, batch), batch_size=batch,
+                                               num_workers=args.workers)
+            host_s = timed(host, args.warmup, args.steps, planar)
+            del host
+            loader = training.DevicePatchLoader(ds, training.ResumeableSampler(ds, batch), batch, device=dev,
+                                                shared=shared)
+            t0 = time.perf_counter()
+            pack = loader.prepare()
+            torch.cuda.synchronize()
+            pack_s = time.perf_counter() - t0
+            # a batch takes a fraction of a millisecond: passes over the dataset until the window is long enough
+            def passes():
+                while True:
+                    yield from training.DevicePatchLoader(ds, training.ResumeableSampler(ds, batch), batch, device=dev,
+                                                          shared=shared)
+            dev_s = timed(passes(), args.warmup, args.device_steps, lambda pair: pair)
+            # the kernel alone: HIP events around each launch of one more pass
+            timer = kernels.LaunchTimer()
+            kernels.set_timer(timer)
+            for _ in training.DevicePatchLoader(ds, training.ResumeableSampler(ds, batch), batch, device=dev,
+                                                shared=shared):
+                pass
+            kernels.set_timer(None)
+            kern = timer.summary()["patch_batch"]
+            print(json.dumps({"bench": "data", "batch": batch, "size": size, "steps": args.steps, "device_steps": args.device_steps,
+                              "workers": args.workers, "images": args.images, "arena_mb": pack.arena.numel() / 2 ** 20,
+                              "pack_s": round(pack_s, 4), "host_ms_per_batch": round(host_s * 1e3, 3),
+                              "host_batches_per_s": round(1.0 / host_s, 2), "device_ms_per_batch": round(dev_s * 1e3, 4),
+                              "device_batches_per_s": round(1.0 / dev_s, 1),
+                              "kernel_us": round(kern["mean_ms"] * 1e3, 2), "kernel_gbps": round(kern["gbps"], 1)}),
+                  flush=True)
+
+    # The device loader's host cost per batch must not grow with the number of files: a training set's file count
+    # (DFWB: 8600) of small pictures, the first curriculum shape.
+    if args.files > 0:
+        with tempfile.TemporaryDirectory() as folder:
+            csv_path = write_small_pictures(folder, args.files, args.small_side)
+            batch, size = SHAPES[0]
+            ds = training.ImageSuperResolution(csv_path=csv_path, root_folder=folder, dist_mode="addictive_noise_scale",
+                                               lambda_noise=25.0, use_data_aug=True, patch_size=(size, size),
+                                               max_num_patchs=4 * args.files, logger=log)
+            many: dict = {}
+            loader = training.DevicePatchLoader(ds, training.ResumeableSampler(ds, batch), batch, device=dev, shared=many)
+            t0 = time.perf_counter()
+            pack = loader.prepare()
+            torch.cuda.synchronize()
+            pack_s = time.perf_counter() - t0
+
+            def passes():
+                while True:
+                    yield from training.DevicePatchLoader(ds, training.ResumeableSampler(ds, batch), batch, device=dev,
+                                                          shared=many)
+            dev_s = timed(passes(), args.warmup, args.device_steps, lambda pair: pair)
+            print(json.dumps({"bench": "data_many_files", "files": args.files, "side": args.small_side, "batch": batch,
+                              "size": size, "device_steps": args.device_steps, "arena_mb": pack.arena.numel() / 2 ** 20,
+                              "pack_s": round(pack_s, 3), "device_ms_per_batch": round(dev_s * 1e3, 4),
+                              "device_batches_per_s": round(1.0 / dev_s, 1)}), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -38,6 +38,7 @@ from . import window_graph  # noqa: F401  (window-graph MixtureGTV of lib/model_
 from . import window_graph_v1  # noqa: F401  (multiblock window denoiser of lib/model_GLR_GTV_deep_v1.py)
 
 from .training import miopen_training_defaults  # noqa: F401
+from .training import DevicePatchLoader, ImageSuperResolution  # noqa: F401  (the v2 scripts' training set)
 from . import restore  # noqa: F401  (whole-image restoration of 8-bit / float images of any size)
 from .restore import RestorePlan, evaluate, plan, psnr_u8, restore_image  # noqa: F401
 from .restore import ImagePack, pack_images, plan_images, restore_images  # noqa: F401  (lists of images)

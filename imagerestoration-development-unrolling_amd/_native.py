@@ -179,6 +179,9 @@ SIGNATURES = {
     "grr_u8_ssim_supported": [I, I, I],
     "grr_u8_ssim": [P, P, I, I, I, P, P],
     "grr_u8_ssim_images": [P, P, L, I, P, I, I, I, P, P],
+    # training batches from an image arena (training.DevicePatchLoader)
+    "grr_patch_batch_supported": [I, I, L, I, I, I],
+    "grr_patch_batch": [P, L, I, P, I, P, P, P, I, ctypes.c_uint64, I, I, P, P, P],
 }
 _RESTYPES = {"grr_version": c_int, "grr_last_error": ctypes.c_char_p, "grr_lnb_workspace_bytes": c_int64,
              "grr_conv1x1_workspace_bytes": c_int64, "grr_wgrad_workspace_bytes": c_int64,

@@ -16,6 +16,11 @@
 //   grr_tile_gather_d8 / grr_tile_scatter_mean / grr_tiles_gather_d8 / grr_tiles_scatter_mean
 // one gather body and one scatter body again, block per (window, tile), the odd quarter turns through LDS.
 //
+// and, for training on real images (training.DevicePatchLoader), the model's clean and noisy planar batches cut
+// from the arena by a device table of (image, row, col, mode), the noise a counter-based function of
+// (seed, sample id, element):
+//   grr_patch_batch
+//
 // Both families are instances of one gather body, one scatter body and one SSE kernel.  gather_kernel and
 // scatter_kernel are written against an image source (OneImage or Arena below), which says where a window's
 // image is, how wide coordinates and table rows are, and which element indices may be touched.
@@ -489,6 +494,168 @@ __global__ __launch_bounds__(kIoThreads) void u8_sse_kernel(const uint8_t* __res
   if ((threadIdx.x & (kWave - 1)) == 0 && acc) atomicAdd(out + seg, acc);
 }
 
+// ---------------------------------------------------------------------------
+// Training batches (grr_patch_batch): sample s is the ph x pw patch of image table[s][0] at (row, col), the
+// bottom / right filled by the edge-repeating mirror (np.pad "symmetric", OpenCV's BORDER_REFLECT), moved by
+// T_mode, plus Gaussian noise that is a function of (seed, sample id, element) alone.
+constexpr int kPatchTile = 32;   // a block's tile of the output patch: 32 rows of 32 floats
+
+struct PatchArgs {
+  float* clean;           // [n, C, ph, pw]
+  float* noisy;
+  const int32_t* table;   // [n, 4] (img, row, col, mode)
+  const int64_t* ids;     // [n]
+  const float* sigma;     // [n]
+  uint64_t seed;
+  int n, ph, pw;
+  int tiles_y, tiles_x;   // tiles of kPatchTile x kPatchTile per output patch
+  int vec;                // pw % 4 == 0 and both outputs 16-byte aligned
+};
+
+// index r >= 0 of the mirror ...cba|abc...|cba... of n >= 1 samples: t = r mod 2n; t < n ? t : 2n - 1 - t
+__device__ __forceinline__ int64_t sym_index(int64_t r, int64_t n) {
+  if (r < n) return r;
+  const int64_t t = r < 2 * n ? r : (int64_t)((uint64_t)r % (uint64_t)(2 * n));
+  return t < n ? t : 2 * n - 1 - t;
+}
+
+// Philox4x32-10 (Salmon et al., SC'11; Random123's constants)
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
+                                              uint32_t k1, uint32_t (&x)[4]) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0;
+    c1 = lo1;
+    c2 = hi0 ^ c3 ^ k1;
+    c3 = lo0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  x[0] = c0; x[1] = c1; x[2] = c2; x[3] = c3;
+}
+
+// the two float64 normals of a word pair: u = (x + 0.5) 2^-32 in (0, 1), Box-Muller
+__device__ __forceinline__ void box_muller(uint32_t xa, uint32_t xb, double* za, double* zb) {
+  const double u0 = ((double)xa + 0.5) * 0x1p-32, u1 = ((double)xb + 0.5) * 0x1p-32;
+  const double r = sqrt(-2.0 * log(u0)), th = 6.283185307179586 * u1;
+  *za = r * cos(th);
+  *zb = r * sin(th);
+}
+
+struct NoiseKey {
+  uint32_t id_lo, id_hi, seed_lo, seed_hi;
+};
+
+// the 4 normals of block b = e / 4 of a sample
+__device__ __forceinline__ void normals4(uint32_t b, const NoiseKey& k, double (&z)[4]) {
+  uint32_t x[4];
+  philox4x32_10(b, 0u, k.id_lo, k.id_hi, k.seed_lo, k.seed_hi, x);
+  box_muller(x[0], x[1], &z[0], &z[1]);
+  box_muller(x[2], x[3], &z[2], &z[3]);
+}
+
+// the normal of element e alone (a lane whose 4 C elements do not start on a block)
+__device__ __forceinline__ double normal_at(uint32_t e, const NoiseKey& k) {
+  uint32_t x[4];
+  philox4x32_10(e >> 2, 0u, k.id_lo, k.id_hi, k.seed_lo, k.seed_hi, x);
+  const bool hi = (e & 2u) != 0;
+  double za, zb;
+  box_muller(hi ? x[2] : x[0], hi ? x[3] : x[1], &za, &zb);
+  return (e & 1u) ? zb : za;
+}
+
+// One block per (sample, 32 x 32 tile of the OUTPUT patch).  Pass 1: a lane reads one source pixel (all C
+// channels) through the mirror rule, adjacent lanes adjacent elements of an image row -- for the odd quarter
+// turns that walks down the tile's columns -- and puts it at its output place in LDS (row stride 33 floats:
+// consecutive words for even k, 32 distinct banks for odd k).  Pass 2: a lane owns 4 consecutive output pixels
+// of a row for all C channels; their 4 C noise elements (HWC order) are C whole Philox blocks when they start
+// on one (pw C % 4 == 0, every training shape), else one block per element.  Plain and 16-byte vector stores
+// only.  Table entries are clamped, element reads go through Arena::clamped.
+template <int C>
+__global__ __launch_bounds__(kIoThreads) void patch_batch_kernel(Arena src, PatchArgs a) {
+  constexpr int LD = kPatchTile + 1;
+  __shared__ float tile[C * kPatchTile * LD];
+  const uint32_t b = blockIdx.x;
+  const int tx = (int)(b % (uint32_t)a.tiles_x);
+  const uint32_t t = b / (uint32_t)a.tiles_x;
+  const int ty = (int)(t % (uint32_t)a.tiles_y), s = (int)(t / (uint32_t)a.tiles_y);
+  const int y0 = ty * kPatchTile, x0 = tx * kPatchTile;
+  const int32_t* e = a.table + (int64_t)s * 4;
+  const Image<int64_t> im = src.image(e);
+  const int64_t row0 = clamp64(e[1], 0, im.H - 1), col0 = clamp64(e[2], 0, im.W - 1);
+  int mode = e[3] & 7;
+  if (d8_odd(mode) && a.ph != a.pw) mode &= 5;        // an odd turn of a non-square patch has no place
+  const bool fi = d8_flip_i(mode), fj = d8_flip_j(mode), odd = d8_odd(mode);
+  const uint8_t* img = static_cast<const uint8_t*>(src.base);
+#pragma unroll
+  for (int k = 0; k < kPatchTile * kPatchTile / kIoThreads; ++k) {
+    const int px = (int)threadIdx.x + k * kIoThreads;
+    const int fast = px % kPatchTile, slow = px / kPatchTile;
+    const int pl = odd ? fast : slow, ql = odd ? slow : fast;
+    const int p = y0 + pl, q = x0 + ql;
+    if (p >= a.ph || q >= a.pw) continue;
+    // (i, j) of the patch lands at (i', j') for even k and at (j', i') for odd k (ph == pw there)
+    const int ip = odd ? q : p, jp = odd ? p : q;
+    const int i = fi ? a.ph - 1 - ip : ip, j = fj ? a.pw - 1 - jp : jp;
+    const int64_t sr = sym_index(row0 + i, im.H), sc = sym_index(col0 + j, im.W);
+    const int64_t base = src.elem(im, sr * im.W + sc, C);
+#pragma unroll
+    for (int c = 0; c < C; ++c) tile[(c * kPatchTile + pl) * LD + ql] = load_px(img + src.clamped(base + c));
+  }
+  __syncthreads();
+  const int pl = (int)threadIdx.x / (kPatchTile / 4), quad = (int)threadIdx.x % (kPatchTile / 4);
+  const int p = y0 + pl, q = x0 + 4 * quad;
+  if (p >= a.ph || q >= a.pw) return;
+  float v[C][4], w[C][4];
+#pragma unroll
+  for (int c = 0; c < C; ++c)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[c][k] = tile[(c * kPatchTile + pl) * LD + 4 * quad + k];   // past pw: unused
+  const double sg = (double)a.sigma[s];
+  const uint64_t id = (uint64_t)a.ids[s];
+  const NoiseKey key{(uint32_t)id, (uint32_t)(id >> 32), (uint32_t)a.seed, (uint32_t)(a.seed >> 32)};
+  const uint32_t e0 = (uint32_t)(((int64_t)p * a.pw + q) * C);      // < ph pw C < 2^31
+  if ((e0 & 3u) == 0) {
+#pragma unroll
+    for (int blk = 0; blk < C; ++blk) {
+      double z[4];
+      normals4((e0 >> 2) + blk, key, z);
+#pragma unroll
+      for (int l = 0; l < 4; ++l) {
+        const int el = 4 * blk + l;           // element k C + c of the lane
+        w[el % C][el / C] = v[el % C][el / C] + (float)(sg * z[l]);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+      for (int c = 0; c < C; ++c)
+        w[c][k] = q + k < a.pw ? v[c][k] + (float)(sg * normal_at(e0 + k * C + c, key)) : 0.0f;
+  }
+  const int64_t plane = (int64_t)a.ph * a.pw;
+  const int64_t at = (int64_t)s * C * plane + (int64_t)p * a.pw + q;
+  if (a.vec) {
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      const f32x4 vc = {v[c][0], v[c][1], v[c][2], v[c][3]}, wc = {w[c][0], w[c][1], w[c][2], w[c][3]};
+      *reinterpret_cast<f32x4*>(a.clean + at + c * plane) = vc;
+      *reinterpret_cast<f32x4*>(a.noisy + at + c * plane) = wc;
+    }
+  } else {
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (q + k < a.pw) {
+          a.clean[at + c * plane + k] = v[c][k];
+          a.noisy[at + c * plane + k] = w[c][k];
+        }
+  }
+}
+
 // The one place that picks <T, C>; the arguments after s are the kernel's.
 #define GRR_IO_DISPATCH(kernel, Src, f32, C, grid, s, ...)                                                         \
   do {                                                                                                             \
@@ -812,6 +979,54 @@ grr_status grr_tiles_scatter_mean(const float* y0, const float* y1, const int32_
   const MeanArgs a = mean_args(y0, y1, wa, l, n, th, tw);
   GRR_IO_DISPATCH(scatter_mean_kernel, Arena, img_f32, C, tile_grid(a), (hipStream_t)stream, src, a);
   return launch_status("grr_tiles_scatter_mean");
+}
+
+int grr_patch_batch_supported(int C, int n_img, int64_t arena_elems, int n, int ph, int pw) {
+  if (!grr_image_arena_supported(C, n_img, arena_elems) || n < 1 || ph < 1 || pw < 1) return 0;
+  const int64_t rows = (int64_t)n * ph;                                       // < 2^62
+  return rows < (1ll << 31) && rows * pw <= ((1ll << 31) - 1) / C ? 1 : 0;    // n C ph pw < 2^31
+}
+
+grr_status grr_patch_batch(const uint8_t* arena, int64_t arena_elems, int C, const int64_t* img_table, int n_img,
+                           const int32_t* table, const int64_t* sample_ids, const float* sigma, int n, uint64_t seed,
+                           int ph, int pw, float* clean, float* noisy, void* stream) {
+  clear_error();
+  GRR_REQUIRE(arena && img_table && table && sample_ids && sigma && clean && noisy && arena_elems > 0 && n_img > 0 &&
+                  C > 0 && n > 0 && ph > 0 && pw > 0,
+              GRR_ERR_INVALID_ARG, "grr_patch_batch: bad args");
+  GRR_REQUIRE(grr_image_arena_supported(C, n_img, arena_elems), GRR_ERR_UNSUPPORTED,
+              "grr_patch_batch: needs C <= 4, n_img <= arena_elems < 2^62 (got C %d, %d images, %lld elements)", C,
+              n_img, (long long)arena_elems);
+  GRR_REQUIRE(grr_patch_batch_supported(C, n_img, arena_elems, n, ph, pw), GRR_ERR_UNSUPPORTED,
+              "grr_patch_batch: patch batch n C ph pw must be below 2^31 (got %d x %d x %d x %d)", n, C, ph, pw);
+  GRR_REQUIRE((uintptr_t)clean % 4 == 0 && (uintptr_t)noisy % 4 == 0 && (uintptr_t)table % 4 == 0 &&
+                  (uintptr_t)sigma % 4 == 0,
+              GRR_ERR_INVALID_ARG, "grr_patch_batch: float32 and int32 operands must be 4-byte aligned");
+  GRR_REQUIRE((uintptr_t)img_table % 8 == 0 && (uintptr_t)sample_ids % 8 == 0, GRR_ERR_INVALID_ARG,
+              "grr_patch_batch: the image table and the sample ids must be 8-byte aligned");
+  const Arena src{const_cast<uint8_t*>(arena), arena_elems, img_table, n_img};
+  PatchArgs a{};
+  a.clean = clean;
+  a.noisy = noisy;
+  a.table = table;
+  a.ids = sample_ids;
+  a.sigma = sigma;
+  a.seed = seed;
+  a.n = n;
+  a.ph = ph;
+  a.pw = pw;
+  a.tiles_y = (ph + kPatchTile - 1) / kPatchTile;
+  a.tiles_x = (pw + kPatchTile - 1) / kPatchTile;
+  a.vec = pw % 4 == 0 && (uintptr_t)clean % 16 == 0 && (uintptr_t)noisy % 16 == 0;
+  const dim3 grid((uint32_t)((int64_t)n * a.tiles_y * a.tiles_x));   // <= n ph pw < 2^31
+  hipStream_t s = (hipStream_t)stream;
+  switch (C) {
+    case 1: hipLaunchKernelGGL(patch_batch_kernel<1>, grid, dim3(kIoThreads), 0, s, src, a); break;
+    case 2: hipLaunchKernelGGL(patch_batch_kernel<2>, grid, dim3(kIoThreads), 0, s, src, a); break;
+    case 3: hipLaunchKernelGGL(patch_batch_kernel<3>, grid, dim3(kIoThreads), 0, s, src, a); break;
+    default: hipLaunchKernelGGL(patch_batch_kernel<4>, grid, dim3(kIoThreads), 0, s, src, a); break;
+  }
+  return launch_status("grr_patch_batch");
 }
 
 }  // extern "C"

@@ -2016,6 +2016,102 @@ def tiles_scatter_mean(y0: Optional[Tensor], y1: Optional[Tensor], table: Tensor
                   _arena_args(pack_out, n_img, c), core_px)
 
 
+# ---------------------------------------------------------------------------
+# ... and training batches cut from a uint8 arena (training.DevicePatchLoader)
+def patch_batch_ok(c: int, n_img: int, arena_elems: int, n: int, ph: int, pw: int) -> bool:
+    """grr_patch_batch_supported in plain Python (tests/test_patch_abi.py checks the two agree): an arena the
+    arena entry points take, n, ph, pw >= 1 and n C ph pw < 2^31."""
+    return image_arena_ok(c, n_img, arena_elems) and n >= 1 and ph >= 1 and pw >= 1 and n * c * ph * pw < (1 << 31)
+
+
+class PatchSource:
+    """A uint8 image pack that patch_batch's checks have passed (patch_source): the pack, its image count and
+    channels, and the images' (H, W) as an int64 array.  A caller that makes many batches from one pack checks it
+    once; the checks walk every image of the pack on the host."""
+    __slots__ = ("pack", "n_img", "c", "hw")
+
+    def __init__(self, pack, n_img: int, c: int, hw):
+        self.pack, self.n_img, self.c, self.hw = pack, n_img, c, hw
+
+
+def patch_source(pack) -> PatchSource:
+    """Check ``pack`` for patch_batch (as the arena wrappers check theirs, and uint8) and return its PatchSource.
+    The pack's tensors and host table must not change afterwards."""
+    import numpy as np
+    n_img, c = _check_pack("patch_batch", pack)
+    if pack.arena.dtype != torch.uint8:
+        raise ValueError(f"patch_batch: the arena must be uint8, got {pack.arena.dtype}")
+    hw = np.asarray(pack.host_table, dtype=np.int64).reshape(n_img, 3)[:, 1:3].copy()
+    return PatchSource(pack, n_img, c, hw)
+
+
+def patch_batch(pack, rows, sample_ids, sigma, seed: int, ph: int, pw: int) -> Tuple[Tensor, Tensor]:
+    """(clean, noisy), float32 [n, C, ph, pw] each: sample s is the ph x pw patch of image rows[s][0] of the
+    uint8 ``pack`` at (rows[s][1], rows[s][2]), the bottom / right filled by the edge-repeating mirror
+    (np.pad "symmetric"), moved by T_mode (rows[s][3], numbered as tiles_gather_d8's), as float(v) / 255; noisy
+    adds sigma[s] times a normal that is a function of (seed, sample_ids[s], element) alone (include/grr.h).
+    ``pack``: an image pack, checked on every call (host time in proportion to its images), or the PatchSource
+    that patch_source made of it once.
+    rows [n, 4], sample_ids [n] and sigma [n] are host data (anything np.asarray takes): they are checked here --
+    indices inside the pack, modes 0..7, the odd quarter turns only with ph == pw -- and uploaded.  Three device
+    tensors (int32 [n, 4], int64 [n], float32 [n], contiguous, on the arena's device) are taken as they are: the
+    kernel clamps what it reads from them."""
+    import numpy as np
+    src = pack if isinstance(pack, PatchSource) else patch_source(pack)
+    pack, n_img, c = src.pack, src.n_img, src.c
+    arena = pack.arena
+    if not 0 <= int(seed) < (1 << 64):
+        raise ValueError(f"patch_batch: seed must fit 64 bits, got {seed}")
+    if isinstance(rows, Tensor) and rows.is_cuda:
+        n = rows.shape[0] if rows.dim() == 2 else 0
+        for t, dtype, shape in ((rows, torch.int32, (n, 4)), (sample_ids, torch.int64, (n,)), (sigma, torch.float32, (n,))):
+            if not isinstance(t, Tensor) or t.dtype != dtype or tuple(t.shape) != shape or t.device != arena.device \
+                    or not t.is_contiguous():
+                raise ValueError("patch_batch: device tables are int32 [n, 4], int64 [n] and float32 [n], contiguous "
+                                 "and on the arena's device")
+        if not isinstance(ph, int) or not isinstance(pw, int) or not patch_batch_ok(c, n_img, arena.numel(), n, ph, pw):
+            raise ValueError(f"patch_batch: patch batch {n} x {c} x {ph} x {pw} must have 1..2^31-1 elements")
+        return _patch_batch(pack, n_img, c, rows, sample_ids, sigma, seed, ph, pw)
+    rows = np.asarray(rows)
+    if rows.ndim != 2 or rows.shape[1] != 4 or rows.shape[0] < 1 or rows.dtype.kind not in "iu":
+        raise ValueError("patch_batch: rows are integers [n, 4] (img, row, col, mode)")
+    n = rows.shape[0]
+    rows = rows.astype(np.int64)
+    ids = np.asarray(sample_ids)
+    sg = np.asarray(sigma, dtype=np.float32)
+    if ids.shape != (n,) or ids.dtype.kind not in "iu" or sg.shape != (n,):
+        raise ValueError(f"patch_batch: sample_ids (integers) and sigma must have one entry per row ({n})")
+    if not (np.isfinite(sg).all() and (sg >= 0).all()):
+        raise ValueError("patch_batch: sigma must be finite and non-negative")
+    if not isinstance(ph, int) or not isinstance(pw, int) or not patch_batch_ok(c, n_img, arena.numel(), n, ph, pw):
+        raise ValueError(f"patch_batch: patch batch {n} x {c} x {ph} x {pw} must have 1..2^31-1 elements")
+    if ((rows[:, 0] < 0) | (rows[:, 0] >= n_img)).any():
+        raise ValueError(f"patch_batch: image indices must lie in [0, {n_img})")
+    hw = src.hw[rows[:, 0]]
+    if ((rows[:, 1:3] < 0) | (rows[:, 1:3] >= hw)).any():
+        raise ValueError("patch_batch: (row, col) must lie inside the row's image")
+    if ((rows[:, 3] < 0) | (rows[:, 3] > 7)).any():
+        raise ValueError("patch_batch: modes must lie in 0..7")
+    if ph != pw and (rows[:, 3] & 2).any():
+        raise ValueError(f"patch_batch: the odd quarter turns (modes 2, 3, 6, 7) need a square patch, got {ph} x {pw}")
+    dev = arena.device
+    return _patch_batch(pack, n_img, c, torch.from_numpy(rows.astype(np.int32)).to(dev),
+                        torch.from_numpy(ids.astype(np.int64)).to(dev),
+                        torch.from_numpy(np.ascontiguousarray(sg)).to(dev), seed, ph, pw)
+
+
+def _patch_batch(pack, n_img: int, c: int, table: Tensor, ids: Tensor, sigma: Tensor, seed: int, ph: int,
+                 pw: int) -> Tuple[Tensor, Tensor]:
+    """patch_batch after its checks, on device tables."""
+    arena, n = pack.arena, table.shape[0]
+    clean = torch.empty((n, c, ph, pw), dtype=torch.float32, device=arena.device)
+    noisy = torch.empty_like(clean)
+    _launch("patch_batch", clean.numel() * 9, "grr_patch_batch", arena.data_ptr(), arena.numel(), c,
+            pack.table.data_ptr(), n_img, table.data_ptr(), ids.data_ptr(), sigma.data_ptr(), n, int(seed), ph, pw,
+            clean.data_ptr(), noisy.data_ptr(), _stream(arena.device))
+    return clean, noisy
+
+
 def u8_sse_segments(a: Tensor, b: Tensor, offsets) -> List[int]:
     """[sum (a - b)^2 over [offsets[i], offsets[i + 1]) for each i]: two 1-D uint8 device tensors of one
     length, all segments in one launch, exact Python ints; one device-to-host copy of the sums (synchronises).

@@ -23,6 +23,10 @@ reverse sweep) — the only collective of the path.
 Datasets: no image data ships with the reference, so ``SyntheticNoisyPatches`` (seeded
 procedural clean patches, the same noise law) is the default; the CSV/PNG dataset type
 is kept for real data.  Samples are (noisy, clean) HWC float32 like the reference's.
+``ImageSuperResolution`` is the v2 scripts' own training set (exploration/model_multiscale_mixture_GLR/
+lib/dataloader_v2.py:70-242); a stage with ``device_resident: true`` reads it through ``DevicePatchLoader``,
+which keeps the decoded pictures on the GPU and makes each planar batch there (csrc/image_ops.hip:
+grr_patch_batch).
 """
 from __future__ import annotations
 
@@ -178,7 +182,260 @@ class SyntheticNoisyPatches(Dataset):
         return torch.from_numpy(_noisy(clean, rs, self.dist_mode, self.lambda_noise)), torch.from_numpy(clean)
 
 
-DATASETS = {c.__name__: c for c in (AddictiveGaussianNoiseImagePair, SyntheticNoisyPatches)}
+def data_augmentation(image: np.ndarray, mode: int) -> np.ndarray:
+    """lib/dataloader_v2.py:23-66: mode m = 2k + f is np.rot90(image, k), then np.flipud if f."""
+    out = np.rot90(image, k=mode // 2)
+    return (np.flipud(out) if mode % 2 else out).copy()
+
+
+class ImageSuperResolution(Dataset):
+    """The v2 scripts' training set (model_multiscale_mixture_GLR/lib/dataloader_v2.py:70-242; csv columns
+    index, path, height, width, nchannels): pictures with both sides above 800 are cut into 512-pixel crops every
+    416 pixels (:111-153), every pass over the crops takes one random patch per crop (:155-188), and one
+    RandomState(seed) then permutes and cuts the list to max_num_patchs (:190-193).  A crop no larger than the
+    patch gives the patch at its origin, filled at the bottom and right by OpenCV's BORDER_REFLECT, the
+    edge-repeating mirror ...cba|abc...|cba... (np.pad "symmetric").  ``__getitem__`` is the reference's host
+    path (:195-242): (noisy, clean) float32 HWC, the augmentation mode and the noise drawn from that same
+    stream, so a sample depends on everything drawn before it.  The reference draws the mode as randint(0, 7),
+    modes 0..6; this path keeps that.  DevicePatchLoader is the path that does not depend on the draw order.
+
+    Beyond the reference: ``n_channels`` (a picture with another channel count is a ValueError naming the file,
+    where the reference fails with an index error), an int ``patch_size`` means a square, and a non-square patch
+    with use_data_aug is refused (the odd quarter turns change the shape; the reference's collation would fail)."""
+
+    IMG_SIZE, OVERLAP, MAX_SIZE = 512, 96, 800
+
+    def __init__(self, csv_path, dist_mode, lambda_noise, use_data_aug=False, patch_size=(64, 64),
+                 max_num_patchs=100000, root_folder="", logger=None, device=None, seed=2204, n_channels=3):
+        import pandas as pd
+        if isinstance(patch_size, int):
+            patch_size = (patch_size, patch_size)
+        self.patch_size = (int(patch_size[0]), int(patch_size[1]))
+        if use_data_aug and self.patch_size[0] != self.patch_size[1]:
+            raise ValueError(f"ImageSuperResolution: use_data_aug needs a square patch (the odd quarter turns change "
+                             f"the shape), got {self.patch_size}")
+        if dist_mode not in ("addictive_noise", "vary_addictive_noise", "addictive_noise_scale"):
+            raise ValueError(f"unknown dist_mode {dist_mode!r}")
+        self.img_infos = pd.read_csv(csv_path, index_col="index")
+        self.max_num_patchs = max_num_patchs
+        self.device, self.root_folder, self.lambda_noise = device, root_folder, lambda_noise
+        self.use_data_augmentation, self.dist_mode = bool(use_data_aug), dist_mode
+        self.logger = logger if logger is not None else LOG
+        self.seed, self.n_channels, self.epoch = int(seed), int(n_channels), 0
+        self.create_all_images()
+        self.random_state = np.random.RandomState(seed=seed)
+        self.create_patchs(self.max_num_patchs)
+        self.random_permute_subselect_patchs_data(self.max_num_patchs)
+
+    def __len__(self):
+        return len(self.patchs_data)
+
+    def create_all_images(self):
+        """:111-153: (row, col, height, width, nchannels, image) per crop; ``paths`` lists the files."""
+        size, step = self.IMG_SIZE, self.IMG_SIZE - self.OVERLAP
+        self.paths, crops = [], []
+        for i in range(self.img_infos.shape[0]):
+            info = self.img_infos.iloc[i]
+            height, width, nchannels = int(info["height"]), int(info["width"]), int(info["nchannels"])
+            self.paths.append(os.path.join(self.root_folder, info["path"]))
+            if width > self.MAX_SIZE and height > self.MAX_SIZE:
+                for r in np.arange(0, height - size, step):
+                    for c in np.arange(0, width - size, step):
+                        crops.append((int(r), int(c), size, size, nchannels, i))
+            else:
+                crops.append((0, 0, height, width, nchannels, i))
+        self.images_data_all = crops
+        self.logger.info(f"Dataset - Create total {len(crops)} cropped images")
+
+    def create_patchs(self, max_num_patchs):
+        """:155-188: rows (row, col, padding, image)."""
+        ph, pw = self.patch_size
+        rows = []
+        for _ in range(max_num_patchs // len(self.images_data_all) + 1):
+            for row, col, height, width, nchannels, img in self.images_data_all:
+                if nchannels > 3:
+                    continue
+                if ph < height and pw < width:
+                    r = row + self.random_state.randint(0, height - ph)
+                    c = col + self.random_state.randint(0, width - pw)
+                    rows.append((int(r), int(c), False, img))
+                else:
+                    rows.append((row, col, True, img))
+        self.patchs_data_all = rows
+        self.logger.info(f"Dataset - Create total {len(rows)} patchs")
+
+    def _select(self, ind):
+        self.patchs_data = [self.patchs_data_all[i] for i in ind]
+        # the same selection as int64 [n, 3] rows (image, row, col), for the device path
+        self.plan = np.array([(img, r, c) for r, c, _, img in self.patchs_data], dtype=np.int64).reshape(-1, 3)
+
+    def random_permute_subselect_patchs_data(self, max_num_patchs):
+        """:190-193, on the constructor's stream."""
+        self.logger.info(f"Dataset - Permute and select {max_num_patchs}/{len(self.patchs_data_all)} patchs")
+        self._select(self.random_state.permutation(len(self.patchs_data_all))[:max_num_patchs])
+
+    def random_permute(self, seed=2204):
+        """What ResumeableSampler.set_epoch_and_current_sample calls with 2024 + epoch: the selection is re-drawn
+        from the fixed patch list by RandomState(seed) alone, and the epoch is kept for the device path."""
+        self._select(np.random.RandomState(seed).permutation(len(self.patchs_data_all))[:self.max_num_patchs])
+        self.epoch = int(seed) - 2024
+
+    def load_image(self, img: int) -> np.ndarray:
+        """File ``img`` of ``paths`` as uint8 H x W x n_channels."""
+        from PIL import Image
+        path = self.paths[img]
+        a = np.array(Image.open(path))
+        if a.ndim == 2 and self.n_channels == 1:
+            a = a[:, :, None]
+        if a.ndim != 3 or a.shape[2] != self.n_channels or a.dtype != np.uint8:
+            raise ValueError(f"ImageSuperResolution: {path} is {a.dtype} {a.shape}, not an 8-bit picture of "
+                             f"{self.n_channels} channel(s)")
+        return a
+
+    def out_size(self) -> Tuple[int, int]:
+        """The sample's sides: the patch cut to multiples of 16 (:208-212)."""
+        return (self.patch_size[0] // 16) * 16, (self.patch_size[1] // 16) * 16
+
+    def __getitem__(self, idx):
+        row, col, need_padding, img_i = self.patchs_data[idx]
+        ph, pw = self.patch_size
+        patch = self.load_image(img_i)[row:row + ph, col:col + pw, :]
+        if need_padding:
+            patch = np.pad(patch, ((0, ph - patch.shape[0]), (0, pw - patch.shape[1]), (0, 0)), mode="symmetric")
+        h_, w_ = (patch.shape[0] // 16) * 16, (patch.shape[1] // 16) * 16
+        patch = patch[0:h_, 0:w_]
+        if self.use_data_augmentation:
+            patch = data_augmentation(patch, self.random_state.randint(0, 7))
+        patch = patch.astype(np.float32) / 255.0
+        dist = _noisy(patch, self.random_state, self.dist_mode, self.lambda_noise)
+        return torch.from_numpy(dist), torch.from_numpy(patch)
+
+
+class DevicePatchLoader:
+    """Batches of an ImageSuperResolution dataset made on the device: yields (noisy, clean) float32
+    [B, C, h, w], planar (``channels_first``), in place of a DataLoader.  On first use (or in ``prepare``) every file
+    a patch reads is decoded once into one uint8 arena laid out as restore.pack_images lays it out (a
+    restore.ImagePack; every rank holds all of it), sent in chunks so the host holds little of it at a time, and the
+    pack is checked once; a batch is then three small tables and one kernels.patch_batch call, whose host cost
+    does not grow with the number of files.
+
+    Per epoch e, vectorised in dataset order from RandomState((dataset.seed 1000003 + e) mod 2^32):
+    modes = randint(0, 8, n) -- all 8 flips and quarter turns; the host path keeps the reference's randint(0, 7),
+    modes 0..6 -- or zeros without use_data_aug, then for vary_addictive_noise choice(levels, p, size=n); the other
+    two modes use lambda_noise (on the device they are one distribution).  Position p of the epoch's selection has
+    sample id (e << 32) | p and the kernel's noise is a function of (dataset.seed, sample id, element), so a sample
+    is a function of (dataset seed, epoch, position) alone: batch size, rank count and the resume point cannot
+    change it."""
+    channels_first = True
+    CHUNK_BYTES = 256 << 20      # decoded pictures staged on the host per transfer
+
+    def __init__(self, dataset, sampler, batch_size: int, drop_last: bool = False, device=None, shared=None):
+        """shared: a dict that loaders over the same files and device put their arena in and take it from (the
+        stages of a curriculum read one csv; training.build_train_stages owns the dict, so the arena lives as
+        long as the stages do).  None: this loader's own arena."""
+        if not isinstance(dataset, ImageSuperResolution):
+            raise ValueError("DevicePatchLoader: needs an ImageSuperResolution dataset")
+        if batch_size < 1:
+            raise ValueError(f"DevicePatchLoader: batch_size must be positive (got {batch_size})")
+        self.dataset, self.sampler, self.batch_size, self.drop_last = dataset, sampler, int(batch_size), bool(drop_last)
+        self.device = device
+        self.shared = shared
+        self.source = None           # kernels.PatchSource: the arena, checked once
+        self._draws = (None, None, None)
+
+    def __len__(self):
+        n = len(self.sampler)
+        return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
+
+    def _pack(self, used: Sequence[int], dev):
+        """The files ``used`` of the dataset in one uint8 arena on ``dev``, sized from the csv's heights and
+        widths: decoded one by one and sent in chunks of about CHUNK_BYTES, so the host never holds more than two
+        chunks of decoded pictures."""
+        from . import restore
+        ds, c = self.dataset, self.dataset.n_channels
+        shapes = [(int(ds.img_infos.iloc[i]["height"]), int(ds.img_infos.iloc[i]["width"])) for i in used]
+        host_table, total = restore._host_table(shapes, c)
+        arena = torch.empty(total, dtype=torch.uint8, device=dev)
+        held, held_bytes, at = [], 0, 0
+
+        def flush():
+            nonlocal held, held_bytes, at
+            if held:
+                arena[at:at + held_bytes].copy_(torch.cat(held))
+                at += held_bytes
+                held, held_bytes = [], 0
+        for i, shape in zip(used, shapes):
+            a = ds.load_image(i)
+            if a.shape[:2] != shape:
+                raise ValueError(f"ImageSuperResolution: {ds.paths[i]} is {a.shape[0]} x {a.shape[1]}, the csv says "
+                                 f"{shape[0]} x {shape[1]}")
+            held.append(torch.from_numpy(np.ascontiguousarray(a)).reshape(-1))
+            held_bytes += a.size
+            if held_bytes >= self.CHUNK_BYTES:
+                flush()
+        flush()
+        table = torch.tensor(host_table, dtype=torch.int64).to(dev)
+        return restore.ImagePack(arena, table, host_table, c, ("numpy",) * len(used))
+
+    def prepare(self):
+        """Decode and pack the pictures now (otherwise the first batch does) and check the pack once; returns the
+        restore.ImagePack.  Serial PIL decodes: for a training set of thousands of files this takes minutes."""
+        if self.source is None:
+            from . import kernels
+            dev = self.device if self.device is not None else torch.device("cuda", torch.cuda.current_device())
+            ds = self.dataset
+            used = sorted({r[3] for r in ds.patchs_data_all})                # files no patch reads stay on disk
+            slot = np.full(len(ds.paths), -1, dtype=np.int64)
+            slot[used] = np.arange(len(used))
+            self._slot = slot
+            key = (tuple(ds.paths[i] for i in used), ds.n_channels, str(dev))
+            store = self.shared if self.shared is not None else {}
+            if key not in store:
+                store[key] = kernels.patch_source(self._pack(used, dev))
+            self.source = store[key]
+        return self.source.pack
+
+    def epoch_draws(self, epoch: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(modes int64 [n], sigma float32 [n]) of the epoch, in dataset order."""
+        ds = self.dataset
+        if self._draws[0] != (epoch, len(ds)):
+            rs = np.random.RandomState((ds.seed * 1000003 + epoch) % (2 ** 32))
+            n = len(ds)
+            modes = rs.randint(0, 8, n) if ds.use_data_augmentation else np.zeros(n, np.int64)
+            if ds.dist_mode == "vary_addictive_noise":
+                levels = rs.choice(ds.lambda_noise[0], p=ds.lambda_noise[1], size=n)
+            else:
+                levels = np.full(n, ds.lambda_noise)
+            sigma = (np.asarray(levels, dtype=np.float64) / 255.0).astype(np.float32)
+            self._draws = ((epoch, n), modes.astype(np.int64), sigma)
+        return self._draws[1], self._draws[2]
+
+    def batch(self, positions: Sequence[int]):
+        """(noisy, clean) of the samples at these positions of the current epoch's selection."""
+        from . import kernels
+        ds = self.dataset
+        epoch = int(ds.epoch)
+        modes, sigma = self.epoch_draws(epoch)
+        pos = np.asarray(positions, dtype=np.int64)
+        self.prepare()
+        plan = ds.plan[pos]
+        rows = np.stack([self._slot[plan[:, 0]], plan[:, 1], plan[:, 2], modes[pos]], axis=1)
+        h, w = ds.out_size()
+        clean, noisy = kernels.patch_batch(self.source, rows, (np.int64(epoch) << 32) | pos, sigma[pos], ds.seed, h, w)
+        return noisy, clean
+
+    def __iter__(self):
+        held: List[int] = []
+        for p in self.sampler:
+            held.append(p)
+            if len(held) == self.batch_size:
+                yield self.batch(held)
+                held = []
+        if held and not self.drop_last:
+            yield self.batch(held)
+
+
+DATASETS = {c.__name__: c for c in (AddictiveGaussianNoiseImagePair, SyntheticNoisyPatches, ImageSuperResolution)}
 
 
 # ---------------------------------------------------------------------------
@@ -346,13 +603,21 @@ class TrainStage:
     """One loader of the training curriculum: dataset + resumable sampler + dataloader, and the
     optimisation steps it holds per epoch."""
 
-    def __init__(self, index: int, ds_conf: dict, environ_conf: dict, rank: int, world: int):
+    def __init__(self, index: int, ds_conf: dict, environ_conf: dict, rank: int, world: int, shared=None):
         self.index = index
         self.dataset = create_dataset(ds_conf, environ_conf)
         self.batch_size = int(ds_conf["dataloader_args"].get("batch_size", 1))
         self.drop_last = bool(ds_conf["dataloader_args"].get("drop_last", False))
         self.sampler = ResumeableSampler(self.dataset, self.batch_size, rank, world)
-        self.loader = create_dataloader(self.dataset, self.sampler, ds_conf, environ_conf)
+        if ds_conf.get("device_resident"):
+            # batches made on the device from a packed arena; dataloader_args' num_workers is ignored
+            if ds_conf["type"] != "ImageSuperResolution":
+                raise ValueError(f"training stage {index}: device_resident needs type ImageSuperResolution, got "
+                                 f"{ds_conf['type']}")
+            self.loader = DevicePatchLoader(self.dataset, self.sampler, self.batch_size, self.drop_last,
+                                            shared=shared)
+        else:
+            self.loader = create_dataloader(self.dataset, self.sampler, ds_conf, environ_conf)
         self.steps = self.sampler.steps_per_epoch(self.drop_last)
         if self.steps <= 0:
             raise ValueError(f"training stage {index}: dataset of {len(self.dataset)} samples holds no batch of "
@@ -372,7 +637,8 @@ def build_train_stages(conf: dict, rank: int = 0, world: int = 1) -> List[TrainS
     global batch is batch_size x world) and each stage's epoch is cut to whole global batches, so every
     rank runs the same number of steps in every stage and all ranks stay in one all-reduce sequence --
     the 384^2 x 1 stage on 8 GPUs is a global batch of 8, one patch per rank."""
-    return [TrainStage(k, dc, conf, rank, world) for k, dc in enumerate(train_stage_confs(conf))]
+    shared: dict = {}     # the device-resident stages' arena, one per set of files: it lives as long as the stages
+    return [TrainStage(k, dc, conf, rank, world, shared) for k, dc in enumerate(train_stage_confs(conf))]
 
 
 # ---------------------------------------------------------------------------
@@ -452,13 +718,17 @@ class Trainer:
             loss = loss + self.w_perturb * nn.functional.mse_loss(rec, disturbed)
         return loss
 
-    def step(self, noisy_hwc: torch.Tensor, clean_hwc: torch.Tensor) -> float:
-        """noisy/clean: [B,H,W,C] batches as the dataset yields them (permuted like :191-193)."""
+    def step(self, noisy_hwc: torch.Tensor, clean_hwc: torch.Tensor, channels_first: bool = False) -> float:
+        """noisy/clean: [B,H,W,C] batches as the dataset yields them (permuted like :191-193), or, with
+        channels_first, the planar [B,C,H,W] batches of a DevicePatchLoader, taken as they are."""
         self.model.train()
         self.optimizer.zero_grad(set_to_none=True)
         self.reducer.prepare()
-        noisy = noisy_hwc.to(self.device, non_blocking=True).permute(0, 3, 1, 2).contiguous()
-        clean = clean_hwc.to(self.device, non_blocking=True).permute(0, 3, 1, 2).contiguous()
+        noisy = noisy_hwc.to(self.device, non_blocking=True)
+        clean = clean_hwc.to(self.device, non_blocking=True)
+        if not channels_first:
+            noisy = noisy.permute(0, 3, 1, 2).contiguous()
+            clean = clean.permute(0, 3, 1, 2).contiguous()
         outs: list = []
         with stream_guard.maybe_guard():       # GRR_STREAM_GUARD=1: check the internal-stream invariant
             loss = self.loss(noisy, clean, outs)
@@ -522,6 +792,9 @@ def run(conf: dict, device=None, max_iters: Optional[int] = None) -> Trainer:
             else torch.device("cpu")
     tconf = conf.get("train", {})
     stages = build_train_stages(conf, rank, world)
+    for st in stages:
+        if isinstance(st.loader, DevicePatchLoader) and st.loader.device is None:
+            st.loader.device = device      # the arena lives where the model trains
     trainer = Trainer(build_model(conf.get("model", {})), tconf, device)
     ckpt_path = conf["path"].get("latest_checkpoint_path") or latest_checkpoint(conf)
     if world > 1:
@@ -574,7 +847,7 @@ def run(conf: dict, device=None, max_iters: Optional[int] = None) -> Trainer:
             for noisy, clean in st.loader:
                 if trainer.i >= total:
                     break
-                loss = trainer.step(noisy, clean)
+                loss = trainer.step(noisy, clean, channels_first=getattr(st.loader, "channels_first", False))
                 stepped = True
                 if trainer.i % verbose == 0:
                     psnr_tr, mse_tr = trainer.train_metrics() if trainer.track_metrics else (float("nan"),) * 2

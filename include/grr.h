@@ -824,6 +824,37 @@ grr_status grr_u8_ssim(const uint8_t* a, const uint8_t* b, int H, int W, int C, 
 grr_status grr_u8_ssim_images(const uint8_t* a, const uint8_t* b, int64_t arena_elems, int C, const int64_t* img_table,
                               int n_img, int max_h, int max_w, int64_t* out, void* stream);
 
+/* ---- training batches cut from an arena of uint8 images (training.DevicePatchLoader; the reference's
+ * lib/dataloader_v2.py:ImageSuperResolution does this per sample on the host).  arena, arena_elems, C, img_table,
+ * n_img: as grr_tiles_gather takes them, uint8 only.  table: int32 [n, 4] on the device, rows (img, row, col,
+ * mode); sample_ids: int64 [n] on the device, 8-byte aligned; sigma: float32 [n] on the device, the noise standard
+ * deviation in [0, 1] units (level / 255 as float32); clean, noisy: float32 [n, C, ph, pw], planar.
+ *
+ * clean: before the transform, pixel (i, j) of sample s is image pixel (sym(row + i, H), sym(col + j, W)) with
+ * sym(r, n): t = r mod 2n; t < n ? t : 2n - 1 - t -- the edge-repeating mirror ...cba|abc...|cba... of
+ * np.pad(mode="symmetric") and OpenCV's BORDER_REFLECT, periodic where the fill exceeds the side (not the "reflect"
+ * of grr_tile_gather).  The pixel then moves by T_mode, numbered and indexed as for grr_tile_gather_d8 above; the
+ * value is float(v) / 255.0f, correctly rounded.  The odd quarter turns (modes 2, 3, 6, 7) need ph == pw: the
+ * tables are device data, so the caller checks this before upload, and the kernel reads an illegal mode as
+ * mode & 5.  Modes are taken & 7.
+ *
+ * noisy = clean + noise in float32, noise = (float)((double)sigma[s] * z), where z is a function of (seed,
+ * sample_ids[s], element) alone: with e = (y pw + x) C + c the element's position in the output patch in HWC
+ * order, block b = e / 4 is Philox4x32-10 of counter (b, 0, low32(id), high32(id)) and key (low32(seed),
+ * high32(seed)); its words x0..x3 give u_k = (x_k + 0.5) 2^-32 in float64; lanes e % 4 = 0, 1 are r cos(t) and
+ * r sin(t) with r = sqrt(-2 log(u0)), t = 6.283185307179586 u1, all float64, and lanes 2, 3 the same from
+ * (u2, u3).  sigma = 0 gives noisy == clean bit for bit.  A sample does not depend on the batch it is in.
+ *
+ * Every index from a table is clamped -- img into [0, n_img), row and col into the image, every element index
+ * into [0, arena_elems) -- so a bad table gives wrong pixels, never an access outside the buffers.  No atomics. */
+
+/* 1 where grr_patch_batch takes the call: grr_image_arena_supported(C, n_img, arena_elems), n, ph, pw >= 1 and
+ * n C ph pw < 2^31. */
+int grr_patch_batch_supported(int C, int n_img, int64_t arena_elems, int n, int ph, int pw);
+grr_status grr_patch_batch(const uint8_t* arena, int64_t arena_elems, int C, const int64_t* img_table, int n_img,
+                           const int32_t* table, const int64_t* sample_ids, const float* sigma, int n, uint64_t seed,
+                           int ph, int pw, float* clean, float* noisy, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
