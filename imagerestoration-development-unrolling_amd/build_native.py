@@ -9,6 +9,7 @@ or header is newer than the library.
 from __future__ import annotations
 
 import argparse
+import glob
 import os
 import shutil
 import subprocess
@@ -18,8 +19,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgrr.so")
-SOURCES = ["graph_ops.hip", "feature_ops.hip", "lnb_ops.hip", "graph_bwd.hip", "lnb_bwd.hip", "window_ops.hip", "window_bwd.hip", "subapi_ops.hip", "subapi_bwd.hip", "wgrad_ops.hip", "feature_edge.hip", "codec_ops.hip", "image_ops.hip", "metric_ops.hip"]
-HEADERS = [os.path.join(CSRC, "grr_common.h"), os.path.join(ROOT, "include", "grr.h")]
+SOURCES = ["graph_ops.hip", "feature_ops.hip", "lnb_ops.hip", "graph_bwd.hip", "lnb_bwd.hip", "window_ops.hip", "window_bwd.hip", "subapi_ops.hip", "subapi_bwd.hip", "wgrad_ops.hip", "feature_edge.hip", "codec_ops.hip", "image_ops.hip", "metric_ops.hip", "runtime.hip"]
+# every header of csrc/ (a new one can never go stale unnoticed) and the public ABI
+HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(ROOT, "include", "grr.h")]
 ARCH = "gfx950"
 # lnb_ops, graph_ops: no SLP packing of independent f32 FMAs into v_pk_fma_f32 (the packing
 # needs register-pair moves that cost more than it saves, MI355X_MICROARCH.md; graph_step2_kernel:

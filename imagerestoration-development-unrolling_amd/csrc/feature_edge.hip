@@ -25,16 +25,10 @@
 // power-of-two factor; the 1e-12 floor is scaled alike).
 #include <type_traits>
 
-#include "grr_common.h"
+#include "grr_split.h"
 
 namespace grr {
 namespace {
-
-typedef _Float16 fe_f16x8 __attribute__((ext_vector_type(8)));
-typedef float fe_f32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t fe_u32x4 __attribute__((ext_vector_type(4)));
-typedef float fe_f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 fe_f16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int FE_KS = 6;                 // k-steps of 16: input channels <= 96
 constexpr int FE_GH = 4;                 // graphs per lane half (12 of the 16 accumulator rows)
@@ -75,12 +69,6 @@ struct FeArgs {
   uint32_t nblk;
 };
 
-__device__ __forceinline__ int fe_scale_exp(float mx) {   // mx 2^s in [2^13, 2^14)
-  if (mx == 0.f) return 0;
-  int e;
-  frexpf(mx, &e);
-  return clampi(14 - e, -100, 100);
-}
 // (slab, graph) -> the exponent of its three weight rows
 __device__ __forceinline__ int fe_graph_exp(const float* __restrict__ wf, int slab, int g, int G, int K) {
   float mx = 0.f;
@@ -88,7 +76,7 @@ __device__ __forceinline__ int fe_graph_exp(const float* __restrict__ wf, int sl
     const float* row = wf + (int64_t)(slab * 3 * G + 3 * g + f) * K;
     for (int k = 0; k < K; ++k) mx = fmaxf(mx, fabsf(row[k]));
   }
-  return fe_scale_exp(mx);
+  return scale_exp(mx, 100);
 }
 
 // A images: tile T (slab T / 4, graphs 8 (T % 4) ..), k-step s, term q; lane l, element j: A row i = l & 31
@@ -118,28 +106,17 @@ __global__ void fe_pack_kernel(const float* __restrict__ wf, char* __restrict__ 
         const int k = 16 * s + 8 * (l >> 5) + 2 * jw + u;
         v[u] = k < K ? ldexpf(wf[(int64_t)row * K + k], sc) : 0.f;
       }
-      const _Float16 h0 = (_Float16)v[0], h1 = (_Float16)v[1];
-      const _Float16 t0 = q == 0 ? h0 : (_Float16)(v[0] - (float)h0), t1 = q == 0 ? h1 : (_Float16)(v[1] - (float)h1);
-      word = (uint32_t)__builtin_bit_cast(uint16_t, t0) | ((uint32_t)__builtin_bit_cast(uint16_t, t1) << 16);
+      word = f16_pair_word(v[0], v[1], q);
     }
     reinterpret_cast<uint32_t*>(pack)[i] = word;
   }
 }
 
-// (DPP moves are convergent: never sunk into a branch, where inactive lanes would read as 0.  No inline asm in
-// the edge arithmetic: an asm statement ends the scheduling region and the conv MFMAs could not be spread over it)
-__device__ __forceinline__ float fe_prev(float v) {   // lane - 1 (DPP wave shift; whole wave active)
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x138, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float fe_next(float v) {   // lane + 1
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xF, 0xF, true));
-}
-template <int E>
-__device__ __forceinline__ float fe_quad_e(float v) {   // every lane of a quad takes the quad's element E
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), E * 0x55, 0xF, 0xF, true));
-}
+// Lane shifts here are the unpinned lane_prev_free / lane_next_free / quad_bcast of grr_device.h: no inline asm
+// in the edge arithmetic (an asm statement ends the scheduling region and the conv MFMAs could not be spread
+// over it)
 __device__ __forceinline__ float fe_quad(float v, int e) {   // e a compile-time constant after unrolling
-  return e == 0 ? fe_quad_e<0>(v) : e == 1 ? fe_quad_e<1>(v) : e == 2 ? fe_quad_e<2>(v) : fe_quad_e<3>(v);
+  return e == 0 ? quad_bcast<0>(v) : e == 1 ? quad_bcast<1>(v) : e == 2 ? quad_bcast<2>(v) : quad_bcast<3>(v);
 }
 
 template <bool IN8>
@@ -174,7 +151,7 @@ __global__ __launch_bounds__(FE_THREADS, 1) void feat_edge_kernel(FeArgs a) {
 
   // the tiles' A images into LDS (every workgroup reads the same 96 KB: L2)
   for (int i = threadIdx.x; i < FE_NT * FE_AIMG / 4; i += FE_THREADS)
-    reinterpret_cast<fe_u32x4*>(aimg)[i] = reinterpret_cast<const fe_u32x4*>(a.pack)[i];
+    reinterpret_cast<u32x4*>(aimg)[i] = reinterpret_cast<const u32x4*>(a.pack)[i];
 
   if (wave == FE_NT) {
     // ---------------- loader: the main pixels of a row, one row ahead; the halo pixels of FE_HB rows at a time
@@ -195,10 +172,10 @@ __global__ __launch_bounds__(FE_THREADS, 1) void feat_edge_kernel(FeArgs a) {
         const uint32_t vo = (uint32_t)((kh * HW + gy * W + cc) * 32);
 #pragma unroll
         for (int s = 0; s < FE_KS; ++s) {
-          const fe_u32x4 lo =
-              __builtin_bit_cast(fe_u32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, vo, 16 * s * hw4, 0));
-          const fe_u32x4 hi =
-              __builtin_bit_cast(fe_u32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, vo + 16, 16 * s * hw4, 0));
+          const u32x4 lo =
+              __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, vo, 16 * s * hw4, 0));
+          const u32x4 hi =
+              __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, vo + 16, 16 * s * hw4, 0));
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             v[set][s][j] = __uint_as_float(lo[j]);
@@ -224,20 +201,15 @@ __global__ __launch_bounds__(FE_THREADS, 1) void feat_edge_kernel(FeArgs a) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) mx = fmaxf(mx, fabsf(v[set][s][j]));
       mx = fmaxf(mx, __shfl_xor(mx, 32));
-      const int ep = fe_scale_exp(mx);
+      const int ep = scale_exp(mx, 100);
 #pragma unroll
       for (int s = 0; s < FE_KS; ++s) {
         uint32_t hw[4], lw[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const fe_f32x2 p = fe_f32x2{ldexpf(v[set][s][2 * j], ep), ldexpf(v[set][s][2 * j + 1], ep)};
-          const fe_f16x2 h = __builtin_convertvector(p, fe_f16x2);
-          const fe_f16x2 l = __builtin_convertvector(p - __builtin_convertvector(h, fe_f32x2), fe_f16x2);
-          hw[j] = __builtin_bit_cast(uint32_t, h);
-          lw[j] = __builtin_bit_cast(uint32_t, l);
-        }
-        *reinterpret_cast<fe_u32x4*>(slot + (2 * s) * 256 + 4 * lane) = fe_u32x4{hw[0], hw[1], hw[2], hw[3]};
-        *reinterpret_cast<fe_u32x4*>(slot + (2 * s + 1) * 256 + 4 * lane) = fe_u32x4{lw[0], lw[1], lw[2], lw[3]};
+        for (int j = 0; j < 4; ++j)
+          split2_f16(ldexpf(v[set][s][2 * j], ep), ldexpf(v[set][s][2 * j + 1], ep), hw[j], lw[j]);
+        *reinterpret_cast<u32x4*>(slot + (2 * s) * 256 + 4 * lane) = u32x4{hw[0], hw[1], hw[2], hw[3]};
+        *reinterpret_cast<u32x4*>(slot + (2 * s + 1) * 256 + 4 * lane) = u32x4{lw[0], lw[1], lw[2], lw[3]};
       }
       if (kh == 0) reinterpret_cast<int*>(slot + FE_IMG)[n] = ep;
     };
@@ -311,7 +283,7 @@ __global__ __launch_bounds__(FE_THREADS, 1) void feat_edge_kernel(FeArgs a) {
 
   // F.normalize * multiM of one pixel's 4 x 3 features (REF:146-157): one hardware reciprocal per (pixel,
   // graph) instead of three IEEE divisions (the IEEE sequence serialises on VCC); <= 1.5 ulp
-  auto norm4 = [&](const fe_f32x16& acc, int ep, float (&out)[FE_GH][3]) __attribute__((always_inline)) {
+  auto norm4 = [&](const f32x16& acc, int ep, float (&out)[FE_GH][3]) __attribute__((always_inline)) {
 #pragma unroll
     for (int gi = 0; gi < FE_GH; ++gi) {
       const float f0 = acc[3 * gi], f1 = acc[3 * gi + 1], f2 = acc[3 * gi + 2];
@@ -397,7 +369,7 @@ __global__ __launch_bounds__(FE_THREADS, 1) void feat_edge_kernel(FeArgs a) {
 #pragma unroll
       for (int f = 0; f < 3; ++f) {
         const float v = fw[Q][gi][f];
-        const float pl = fe_prev(v), pr = fe_next(v);
+        const float pl = lane_prev_free(v), pr = lane_next_free(v);
         // at the image's edges the neighbour is the pixel itself (REF's replicate padding): the halo columns and
         // the lanes past W are clamped into the image, so their features already equal v bitwise
         const float lv = n == 0 ? hb[gi][f] : pl;
@@ -419,7 +391,7 @@ __global__ __launch_bounds__(FE_THREADS, 1) void feat_edge_kernel(FeArgs a) {
       if (slab == 0) {   // wave-uniform: pair weights (REF:452-516's C^T C as pair weights)
         // w_left(p + right): lane n + 1's w1; for lane 31 the softmax of R1 = x0 + 32 from the halo rows (R1's
         // up / down rows, R2 = x0 + 33 to its right, this lane's column to its left)
-        const float w1n = fe_next(w1);   // (outside the select: a DPP read in a branch sees inactive lanes as 0)
+        const float w1n = lane_next_free(w1);   // (outside the select: a DPP read in a branch sees inactive lanes as 0)
         const float wln = n == 31 ? w1r[gi] : w1n;
         const float ch = col + 1 < W ? __builtin_fmaf(w2, w2, wln * wln) : 0.f;
         // row ey - 1: w_down(p)^2 + w_up(p + down)^2
@@ -437,17 +409,15 @@ __global__ __launch_bounds__(FE_THREADS, 1) void feat_edge_kernel(FeArgs a) {
   asm volatile("" ::: "memory");
   // the halo batch of conv rows k .. k + FE_HB - 1 into the halo feature ring (the main image's product order)
   auto halo = [&](int k) __attribute__((always_inline)) {
-    fe_f32x16 ax = fe_f32x16{};
+    f32x16 ax = f32x16{};
     const float* hs = himg + 4 * lane;
 #pragma unroll
     for (int s = 0; s < FE_KS; ++s) {
-      const fe_f16x8 ah = *reinterpret_cast<const fe_f16x8*>(at + (2 * s) * 256);
-      const fe_f16x8 al = *reinterpret_cast<const fe_f16x8*>(at + (2 * s + 1) * 256);
-      const fe_f16x8 ch = *reinterpret_cast<const fe_f16x8*>(hs + (2 * s) * 256);
-      const fe_f16x8 cl = *reinterpret_cast<const fe_f16x8*>(hs + (2 * s + 1) * 256);
-      ax = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, ch, ax, 0, 0, 0);
-      ax = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, cl, ax, 0, 0, 0);
-      ax = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, ch, ax, 0, 0, 0);
+      const f16x8 ah = *reinterpret_cast<const f16x8*>(at + (2 * s) * 256);
+      const f16x8 al = *reinterpret_cast<const f16x8*>(at + (2 * s + 1) * 256);
+      const f16x8 ch = *reinterpret_cast<const f16x8*>(hs + (2 * s) * 256);
+      const f16x8 cl = *reinterpret_cast<const f16x8*>(hs + (2 * s + 1) * 256);
+      GRR_X2_MFMA(__builtin_amdgcn_mfma_f32_32x32x16_f16, ax, ah, al, ch, cl);
     }
     float hf[FE_GH][3];
     norm4(ax, reinterpret_cast<const int*>(himg + FE_IMG)[n], hf);
@@ -469,20 +439,18 @@ __global__ __launch_bounds__(FE_THREADS, 1) void feat_edge_kernel(FeArgs a) {
     using IP = std::integral_constant<int, PH>;
     using IQ = std::integral_constant<int, (PH + 1) % 3>;
     using IN = std::integral_constant<int, (PH + 2) % 3>;
-    fe_f32x16 am = fe_f32x16{};
+    f32x16 am = f32x16{};
     int epm = 0;
     auto conv = [&]() __attribute__((always_inline)) {
       if (CONV && !(FE_DIAG & 8)) {
         const float* slot = ring + (k & 1) * FE_SLOT + 4 * lane;
 #pragma unroll
         for (int s = 0; s < FE_KS; ++s) {
-          const fe_f16x8 ah = *reinterpret_cast<const fe_f16x8*>(at + (2 * s) * 256);
-          const fe_f16x8 al = *reinterpret_cast<const fe_f16x8*>(at + (2 * s + 1) * 256);
-          const fe_f16x8 bh = *reinterpret_cast<const fe_f16x8*>(slot + (2 * s) * 256);
-          const fe_f16x8 bl = *reinterpret_cast<const fe_f16x8*>(slot + (2 * s + 1) * 256);
-          am = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, am, 0, 0, 0);
-          am = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, am, 0, 0, 0);
-          am = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, am, 0, 0, 0);
+          const f16x8 ah = *reinterpret_cast<const f16x8*>(at + (2 * s) * 256);
+          const f16x8 al = *reinterpret_cast<const f16x8*>(at + (2 * s + 1) * 256);
+          const f16x8 bh = *reinterpret_cast<const f16x8*>(slot + (2 * s) * 256);
+          const f16x8 bl = *reinterpret_cast<const f16x8*>(slot + (2 * s + 1) * 256);
+          GRR_X2_MFMA(__builtin_amdgcn_mfma_f32_32x32x16_f16, am, ah, al, bh, bl);
         }
         epm = reinterpret_cast<const int*>(ring + (k & 1) * FE_SLOT + FE_IMG)[n];
       }

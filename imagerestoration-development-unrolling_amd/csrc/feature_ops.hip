@@ -8,11 +8,10 @@
 // stays within fp32 rounding of the reference's CPU conv).  The B-operand loader
 // fuses CustomLayerNorm's normalisation (LN GEMM) or the 2x2/s2 im2col gather.
 // Depthwise 3x3 + gating and the LayerNorm statistics are memory-bound kernels.
-#include "grr_common.h"
+#include "grr_split.h"
+#include "lnb_ops.h"
 
 namespace grr {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int GT = 256;                    // threads per GEMM workgroup (4 waves, 2x2)
 constexpr int BM = 128, BN = 128, BK = 16;  // block tile; each wave owns a 64x64 quadrant
@@ -354,38 +353,8 @@ __global__ __launch_bounds__(256) void dw_gate_kernel(const float* __restrict__ 
 // tiles).  A (pre-split, fragment order, lnb_x3_pack_kernel) streams through a 2-slot
 // LDS-DMA ring shared by the 4 waves.
 // ---------------------------------------------------------------------------
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ uint32_t bf16_rne(float v) {
-  const uint32_t u = __builtin_bit_cast(uint32_t, v);
-  return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-}
-__device__ __forceinline__ float bf16_val(uint32_t h) { return __builtin_bit_cast(float, h << 16); }
-// exact 3-term split: returns the bf16 bit patterns of v0, v1, v2
-__device__ __forceinline__ void split3(float v, uint32_t& h0, uint32_t& h1, uint32_t& h2) {
-  h0 = bf16_rne(v);
-  const float r1 = v - bf16_val(h0);
-  h1 = bf16_rne(r1);
-  const float r2 = r1 - bf16_val(h1);
-  h2 = bf16_rne(r2);
-}
-
-// the same exact split of 8 values with the hardware RNE conversion (v_cvt_pk_bf16_f32: two values per
-// instruction; the residuals come back through a shift / mask): about half the vector instructions of
-// the integer-rounding split3 above, the same bits for finite values
-__device__ __forceinline__ void split3x8(const float (&v)[8], bf16x8& t0, bf16x8& t1, bf16x8& t2) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const __bf16 h0 = (__bf16)v[j];
-    const float r1 = v[j] - (float)h0;
-    const __bf16 h1 = (__bf16)r1;
-    const float r2 = r1 - (float)h1;
-    t0[j] = h0;
-    t1[j] = h1;
-    t2[j] = (__bf16)r2;
-  }
-}
-
+// The split itself (split_term at pack time, split3x8 in the kernels) and the product order (GRR_X3_MFMA)
+// are in grr_split.h.
 #ifndef GRR_X3_TILES
 #define GRR_X3_TILES 1   // 32-row chunks: 36 KB LDS ring at K = 96 -> 4 workgroups per CU (2 tiles: 2.38 -> 1 tile: 1.88 ms per bench step)
 #endif
@@ -413,9 +382,12 @@ __global__ void x3_pack_kernel(const float* __restrict__ w, const float* __restr
       const int m = c * X3_MCH + t * 32 + (lane & 31), k = 16 * s + 8 * (lane >> 5) + j;
       if (m < M && k < K) {
         const float v = ln_w ? w[(int64_t)m * K + k] * ln_w[k] : w[(int64_t)m * K + k];
-        uint32_t h0, h1, h2;
-        split3(v, h0, h1, h2);
-        out = (uint16_t)(q == 0 ? h0 : q == 1 ? h1 : h2);
+        // all three terms, then the select (not split_term(v, q): through it this kernel's assembly differed)
+        const uint16_t h0 = bf16_bits_rne(v);
+        const float r1 = v - bf16_bits_val(h0);
+        const uint16_t h1 = bf16_bits_rne(r1);
+        const uint16_t h2 = bf16_bits_rne(r1 - bf16_bits_val(h1));
+        out = q == 0 ? h0 : q == 1 ? h1 : h2;
       }
     }
     frag[i] = out;
@@ -461,8 +433,7 @@ __global__ __launch_bounds__(64 * X3_WV) void gemm_x3_kernel(X3Args a) {
     for (int i = 0; i < (NIW * 4 + X3_WV - 1) / X3_WV; ++i) {
       const int img = i * X3_WV + wave;
       if (X3_WV > 4 && img >= NIW * 4) break;   // the chunk holds NIW * 4 images
-      __builtin_amdgcn_global_load_lds((const void*)(src + img * 1024 + lane * 16),
-                                       (__attribute__((address_space(3))) void*)(slot + img * 256), 16, 0, 0);
+      dma16(src + img * 1024 + lane * 16, slot + img * 256);
     }
   };
   issue(0);
@@ -548,12 +519,7 @@ __global__ __launch_bounds__(64 * X3_WV) void gemm_x3_kernel(X3Args a) {
           n1 = *reinterpret_cast<const bf16x8*>(im + (s + 1) * 768 + 256);
           n2 = *reinterpret_cast<const bf16x8*>(im + (s + 1) * 768 + 512);
         }
-        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, bq[s][1], acc[t], 0, 0, 0);
-        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, bq[s][0], acc[t], 0, 0, 0);
-        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, bq[s][2], acc[t], 0, 0, 0);
-        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, bq[s][0], acc[t], 0, 0, 0);
-        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, bq[s][1], acc[t], 0, 0, 0);
-        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, bq[s][0], acc[t], 0, 0, 0);
+        GRR_X3_MFMA(__builtin_amdgcn_mfma_f32_32x32x16_bf16, acc[t], a0, a1, a2, bq[s][0], bq[s][1], bq[s][2]);
         a0 = n0; a1 = n1; a2 = n2;
       }
     }
@@ -607,16 +573,9 @@ static grr_status launch_x3(const float* x, const uint16_t* frag, float* out, in
 // ---------------------------------------------------------------------------
 constexpr int X3K_KC = 2;   // k-steps per ring slot (3 slots: 72 KB at 4 row tiles, two workgroups per CU)
 
-// 16-byte LDS-DMA (lane l -> LDS m0 + 16 l) as an asm statement: hipcc answers the LDS-DMA builtin with
-// vmcnt(0) before every later LDS read (it cannot order the DMA's LDS write against them), which drains
-// the x loads the k-loop keeps two steps ahead.  The ring is ordered by the kernel itself (counted
-// vmcnt + barrier per chunk); the compiler's own counted waits stay correct with these extra,
-// uncounted operations in flight (vmcnt retires loads in order: a wait only gets stricter).
-typedef __attribute__((address_space(3))) float* x3_lds_t;
-__device__ __forceinline__ void x3_dma16(const void* src, const float* lds_wave_base) {
-  const uint32_t m0v = (uint32_t)(uintptr_t)(x3_lds_t)lds_wave_base;
-  asm volatile("global_load_lds_dwordx4 %0, off" ::"v"(src), "{m0}"(__builtin_amdgcn_readfirstlane(m0v)) : "memory");
-}
+// The ring's 16-byte LDS-DMAs are issued opaquely (dma16_opaque, grr_device.h): the builtin's vmcnt(0) before
+// every later LDS read would drain the x loads the k-loop keeps two steps ahead.  The ring is ordered by the
+// kernel itself (counted vmcnt + barrier per chunk).
 
 enum { X3K_STORE = 0, X3K_LN = 1, X3K_SKIP = 2 };
 struct X3KArgs {
@@ -676,7 +635,7 @@ __global__ __launch_bounds__(64 * X3_WV, 4) void gemm_x3k_kernel(X3KArgs a) {
       if (NIMG % X3_WV == 0 || i < NIMG) {
         const int s = c * X3K_KC + img_si[n];
         const int ss = s < KS ? s : KS - 1;
-        x3_dma16(fragb + img_src[n] + (int64_t)ss * 3072 + lane * 16, slot + i * 256);
+        dma16_opaque(fragb + img_src[n] + (int64_t)ss * 3072 + lane * 16, slot + i * 256);
       }
     }
   };
@@ -736,12 +695,7 @@ __global__ __launch_bounds__(64 * X3_WV, 4) void gemm_x3k_kernel(X3KArgs a) {
       const bf16x8 a0 = *reinterpret_cast<const bf16x8*>(im);
       const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(im + 256);
       const bf16x8 a2 = *reinterpret_cast<const bf16x8*>(im + 512);
-      acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, bq1, acc[t], 0, 0, 0);
-      acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, bq0, acc[t], 0, 0, 0);
-      acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, bq2, acc[t], 0, 0, 0);
-      acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, bq0, acc[t], 0, 0, 0);
-      acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, bq1, acc[t], 0, 0, 0);
-      acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, bq0, acc[t], 0, 0, 0);
+      GRR_X3_MFMA(__builtin_amdgcn_mfma_f32_32x32x16_bf16, acc[t], a0, a1, a2, bq0, bq1, bq2);
     }
   };
   // chunk c: this wave's DMAs of chunk c landed (younger: chunk c - 2's x loads, chunk c + 1's DMAs if
@@ -961,17 +915,16 @@ struct FfnLayout {
   int64_t sd, h, g, f1, f2, total;
   int KS1, nch1, KS2, nch2;
 };
-static int64_t a64(int64_t n) { return (n + 63) / 64 * 64; }
 static FfnLayout ffn_layout(int B, int C, int hid, int64_t P) {
   FfnLayout L{};
   L.KS1 = (C + 15) / 16; L.nch1 = (2 * hid + 31) / 32;
   L.KS2 = (hid + 15) / 16; L.nch2 = (C + 31) / 32;
   L.sd = 0;
-  L.h = a64((int64_t)B * P);
-  L.g = L.h + a64((int64_t)B * 2 * hid * P);
-  L.f1 = L.g + a64((int64_t)B * hid * P);
-  L.f2 = L.f1 + a64((int64_t)L.nch1 * x3_chunk_bytes(L.KS1) / 4);
-  L.total = L.f2 + a64((int64_t)L.nch2 * x3_chunk_bytes(L.KS2) / 4);
+  L.h = align64((int64_t)B * P);
+  L.g = L.h + align64((int64_t)B * 2 * hid * P);
+  L.f1 = L.g + align64((int64_t)B * hid * P);
+  L.f2 = L.f1 + align64((int64_t)L.nch1 * x3_chunk_bytes(L.KS1) / 4);
+  L.total = L.f2 + align64((int64_t)L.nch2 * x3_chunk_bytes(L.KS2) / 4);
   return L;
 }
 

@@ -21,7 +21,7 @@
 // Reductions (per-graph scalars, per-channel taps, multiM) are accumulated in registers
 // over a grid-strided pixel range, reduced across the wave with shuffles and across the
 // workgroup through LDS in wave order, and stored into the contributor's own slot of a
-// partials array; red_finish_kernel adds the slots in order (grr_common.h, "Fixed-order
+// partials array; red_finish_kernel (runtime.hip) adds the slots in order (grr_common.h, "Fixed-order
 // reductions"): bitwise run-to-run reproducible, no float atomics.
 //
 // Tap order (host computes taps [C,5] from stats_kernel_p01/p02a/p02b/p03):
@@ -29,41 +29,14 @@
 // Edge order (REF:42-53): 0 up, 1 left, 2 right, 3 down; opposite(e) = 3 - e.
 #include <algorithm>
 #include <cstdlib>
-#include <mutex>
 
-#include "grr_common.h"
+#include "grr_device.h"
 
 namespace grr {
 namespace {
 
 constexpr int NT = 256;
 constexpr int TARGET_BLOCKS = 4096;   // grid size of the pixel-looping reduction kernels
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-// one partial per block: wave sums -> LDS -> thread 0 adds them in wave order and stores the
-// block's slot.  Every thread of the block must call it (it synchronises); consecutive calls
-// reuse the LDS slots safely.
-__device__ __forceinline__ void block_red_put(const Red& r, int idx, uint32_t slot, float v) {
-  __shared__ float red[NT / 64];
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float t = 0.f;
-#pragma unroll
-    for (int i = 0; i < NT / 64; ++i) t += red[i];
-    red_put(r, idx, slot, t);
-  }
-}
-// slot of block (blockIdx.x, blockIdx.y) of a (chunks, B * per) grid: one per (b, chunk)
-__device__ __forceinline__ uint32_t chunk_slot(int per) {
-  return (uint32_t)(blockIdx.y / per) * gridDim.x + blockIdx.x;
-}
 
 __device__ __forceinline__ bool inside_e(int e, int r, int c, int H, int W) {
   switch (e) {
@@ -131,7 +104,6 @@ __global__ __launch_bounds__(NT) void stencil_kernel(const float* __restrict__ x
 
 // The same four stencils, four adjacent columns per thread (W % 4 == 0, 16-byte aligned planes):
 // rows r-1, r, r+1 as float4 plus the two flanking columns of row r.  grid (ceil(HW/4/NT), B*C).
-typedef float f4 __attribute__((ext_vector_type(4)));
 template <int mode>
 __global__ __launch_bounds__(NT) void stencil4_kernel(const float* __restrict__ x, const float* __restrict__ taps,
                                                       const float* __restrict__ scale, int acc,
@@ -145,21 +117,21 @@ __global__ __launch_bounds__(NT) void stencil4_kernel(const float* __restrict__ 
   const float k0 = taps[ch * 5], ku = taps[ch * 5 + 1], kl = taps[ch * 5 + 2], kr = taps[ch * 5 + 3],
               kd = taps[ch * 5 + 4];
   const bool top = r == 0, bot = r == H - 1, lft = c0 == 0, rgt = c0 + 4 == W;
-  const f4 cv = *reinterpret_cast<const f4*>(xp + r * W + c0);
-  f4 uv, dv;
+  const f32x4 cv = *reinterpret_cast<const f32x4*>(xp + r * W + c0);
+  f32x4 uv, dv;
   float lv, rv;
   if constexpr (mode == 0) {   // replicate
-    uv = *reinterpret_cast<const f4*>(xp + (top ? r : r - 1) * W + c0);
-    dv = *reinterpret_cast<const f4*>(xp + (bot ? r : r + 1) * W + c0);
+    uv = *reinterpret_cast<const f32x4*>(xp + (top ? r : r - 1) * W + c0);
+    dv = *reinterpret_cast<const f32x4*>(xp + (bot ? r : r + 1) * W + c0);
     lv = lft ? cv[0] : xp[r * W + c0 - 1];
     rv = rgt ? cv[3] : xp[r * W + c0 + 4];
   } else {                     // zero frame
-    uv = top ? f4{0.f, 0.f, 0.f, 0.f} : *reinterpret_cast<const f4*>(xp + (r - 1) * W + c0);
-    dv = bot ? f4{0.f, 0.f, 0.f, 0.f} : *reinterpret_cast<const f4*>(xp + (r + 1) * W + c0);
+    uv = top ? f32x4{0.f, 0.f, 0.f, 0.f} : *reinterpret_cast<const f32x4*>(xp + (r - 1) * W + c0);
+    dv = bot ? f32x4{0.f, 0.f, 0.f, 0.f} : *reinterpret_cast<const f32x4*>(xp + (r + 1) * W + c0);
     lv = lft ? 0.f : xp[r * W + c0 - 1];
     rv = rgt ? 0.f : xp[r * W + c0 + 4];
   }
-  f4 y;
+  f32x4 y;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const float l = j > 0 ? cv[j - 1] : lv, rr = j < 3 ? cv[j + 1] : rv;
@@ -181,7 +153,7 @@ __global__ __launch_bounds__(NT) void stencil4_kernel(const float* __restrict__ 
     y[j] = v;
   }
   if (scale) y *= scale[ch / F];
-  f4* o = reinterpret_cast<f4*>(out + (int64_t)plane * HW + r * W + c0);
+  f32x4* o = reinterpret_cast<f32x4*>(out + (int64_t)plane * HW + r * W + c0);
   *o = acc ? *o + y : y;
 }
 
@@ -190,15 +162,15 @@ __global__ __launch_bounds__(NT) void stencil4_kernel(const float* __restrict__ 
 //   out += s1[g] P1*(v1) + s2[g] P2*(v2)
 // reads v1, v2, out and writes out once (two stencil4_kernel<3> launches read out twice and write it
 // twice).  Four adjacent columns per thread, W % 4 == 0.  grid (ceil(HW/4/NT), B*C).
-__device__ __forceinline__ f4 padj4(const float* xp, float k0, float ku, float kl, float kr, float kd, int r, int c0,
+__device__ __forceinline__ f32x4 padj4(const float* xp, float k0, float ku, float kl, float kr, float kd, int r, int c0,
                                     int H, int W) {
   const bool top = r == 0, bot = r == H - 1, lft = c0 == 0, rgt = c0 + 4 == W;
-  const f4 cv = *reinterpret_cast<const f4*>(xp + r * W + c0);
-  const f4 uv = top ? f4{0.f, 0.f, 0.f, 0.f} : *reinterpret_cast<const f4*>(xp + (r - 1) * W + c0);
-  const f4 dv = bot ? f4{0.f, 0.f, 0.f, 0.f} : *reinterpret_cast<const f4*>(xp + (r + 1) * W + c0);
+  const f32x4 cv = *reinterpret_cast<const f32x4*>(xp + r * W + c0);
+  const f32x4 uv = top ? f32x4{0.f, 0.f, 0.f, 0.f} : *reinterpret_cast<const f32x4*>(xp + (r - 1) * W + c0);
+  const f32x4 dv = bot ? f32x4{0.f, 0.f, 0.f, 0.f} : *reinterpret_cast<const f32x4*>(xp + (r + 1) * W + c0);
   const float lv = lft ? 0.f : xp[r * W + c0 - 1];
   const float rv = rgt ? 0.f : xp[r * W + c0 + 4];
-  f4 y;
+  f32x4 y;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {   // stencil4_kernel<3>'s expression, term by term
     const float l = j > 0 ? cv[j - 1] : lv, rr = j < 3 ? cv[j + 1] : rv;
@@ -224,11 +196,11 @@ __global__ __launch_bounds__(NT) void padj2_kernel(const float* __restrict__ x1,
   const int r = q4 / W4, c0 = (q4 - r * W4) * 4;
   const float* t1 = taps1 + ch * 5;
   const float* t2 = taps2 + ch * 5;
-  f4 y1 = padj4(x1 + (int64_t)plane * HW, t1[0], t1[1], t1[2], t1[3], t1[4], r, c0, H, W);
-  f4 y2 = padj4(x2 + (int64_t)plane * HW, t2[0], t2[1], t2[2], t2[3], t2[4], r, c0, H, W);
+  f32x4 y1 = padj4(x1 + (int64_t)plane * HW, t1[0], t1[1], t1[2], t1[3], t1[4], r, c0, H, W);
+  f32x4 y2 = padj4(x2 + (int64_t)plane * HW, t2[0], t2[1], t2[2], t2[3], t2[4], r, c0, H, W);
   y1 *= scale1[ch / F];
   y2 *= scale2[ch / F];
-  f4* o = reinterpret_cast<f4*>(out + (int64_t)plane * HW + r * W + c0);
+  f32x4* o = reinterpret_cast<f32x4*>(out + (int64_t)plane * HW + r * W + c0);
   *o = (*o + y1) + y2;   // the order of two accumulating stencil launches
 }
 
@@ -259,7 +231,7 @@ __global__ __launch_bounds__(NT) void tapgrad_kernel(const float* __restrict__ u
   }
   const float sc = scale ? scale[ch / F] : 1.f;
 #pragma unroll
-  for (int t = 0; t < 5; ++t) block_red_put(gt, ch * 5 + t, chunk_slot(C), sc * acc[t]);
+  for (int t = 0; t < 5; ++t) block_red_put<NT>(gt, ch * 5 + t, chunk_slot(C), sc * acc[t]);
 }
 
 // ---------------------------------------------------------------------------
@@ -318,7 +290,7 @@ __global__ __launch_bounds__(NT) void glr_bwd_kernel(const float* __restrict__ s
 #pragma unroll
     for (int e = 0; e < 4; ++e) gwb[e * HW] += sc * gwa[e];
   }
-  if (gdot.p) block_red_put(gdot, g, chunk_slot(G), coef * dot);
+  if (gdot.p) block_red_put<NT>(gdot, g, chunk_slot(G), coef * dot);
 }
 
 // Pair-Laplacian reverse (GTV C^T C, linear part).  K s(p) = sum over the 4 incident edges
@@ -360,7 +332,7 @@ __global__ __launch_bounds__(NT) void pair_bwd_kernel(const float* __restrict__ 
     if (hr) gcb[0] += sc * gh;
     if (vd) gcb[HW] += sc * gv;
   }
-  if (gdot.p) block_red_put(gdot, g, chunk_slot(G), coef * dot);
+  if (gdot.p) block_red_put<NT>(gdot, g, chunk_slot(G), coef * dot);
 }
 
 // ---------------------------------------------------------------------------
@@ -446,8 +418,8 @@ __global__ __launch_bounds__(NT) void prox_bwd_kernel(const float* __restrict__ 
     for (int e = 0; e < 4; ++e) gwb[e * HW] += sc * gwa[e];
   }
   dgam *= scale ? scale[g] : 1.f;
-  if (gdot.p) block_red_put(gdot, g, chunk_slot(G), coef * dot);
-  if (ggam.p) block_red_put(ggam, g, chunk_slot(G), dgam);
+  if (gdot.p) block_red_put<NT>(gdot, g, chunk_slot(G), coef * dot);
+  if (ggam.p) block_red_put<NT>(ggam, g, chunk_slot(G), dgam);
 }
 
 // c[0](p) = w_right(p)^2 + w_left(p+1)^2, c[1](p) = w_down(p)^2 + w_up(p+W)^2 (0 at the frame):
@@ -560,10 +532,9 @@ __global__ __launch_bounds__(NT) void edge_weights_bwd_kernel(const float* __res
       gfp[(int64_t)f * HW + p] = small ? gn * ic : (gn - n * ndg) * ic;
     }
   }
-  for (int f = 0; f < F; ++f) block_red_put(gM, g * F + f, chunk_slot(G), gm_sm[f * NT + threadIdx.x]);
+  for (int f = 0; f < F; ++f) block_red_put<NT>(gM, g * F + f, chunk_slot(G), gm_sm[f * NT + threadIdx.x]);
 }
 
-typedef float f4v __attribute__((ext_vector_type(4)));
 
 // gdot[g] += coef * sum_{b,f,p} u v.      grid (chunks, B*G); V4: float4 loads (n % 4 == 0, aligned)
 template <bool V4>
@@ -577,13 +548,13 @@ __global__ __launch_bounds__(NT) void graph_dot_kernel(const float* __restrict__
   float acc = 0.f;
   if constexpr (V4) {
     for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < n / 4; i += (int64_t)gridDim.x * NT) {
-      const f4v a = *reinterpret_cast<const f4v*>(up + 4 * i), b = *reinterpret_cast<const f4v*>(vp + 4 * i);
+      const f32x4 a = *reinterpret_cast<const f32x4*>(up + 4 * i), b = *reinterpret_cast<const f32x4*>(vp + 4 * i);
       acc += a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w;
     }
   } else {
     for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * NT) acc += up[i] * vp[i];
   }
-  block_red_put(gdot, g, chunk_slot(G), coef * acc);
+  block_red_put<NT>(gdot, g, chunk_slot(G), coef * acc);
 }
 
 // out = sa[g] * x + sb[g] * y  (sa/sb NULL -> 1; y NULL -> term dropped); acc: out += ...
@@ -598,9 +569,9 @@ __global__ __launch_bounds__(NT) void lincomb_kernel(const float* __restrict__ x
   if constexpr (V4) {
     for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < n / 4; i += (int64_t)gridDim.x * NT) {
       const int64_t o = base + 4 * i;
-      f4v v = a * *reinterpret_cast<const f4v*>(x + o);
-      if (y) v += bb * *reinterpret_cast<const f4v*>(y + o);
-      f4v* dst = reinterpret_cast<f4v*>(out + o);
+      f32x4 v = a * *reinterpret_cast<const f32x4*>(x + o);
+      if (y) v += bb * *reinterpret_cast<const f32x4*>(y + o);
+      f32x4* dst = reinterpret_cast<f32x4*>(out + o);
       *dst = acc ? *dst + v : v;
     }
   } else {
@@ -646,38 +617,36 @@ __global__ __launch_bounds__(NT) void cg_glue_kernel(const float* gx, const floa
   };
   float da = 0.f, db = 0.f;
   if constexpr (V4) {
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    typedef float f2 __attribute__((ext_vector_type(2)));
     // four columns at slab element li (W % 4 == 0 where pj / gxh / gud are given)
     auto glue4 = [&](int li) __attribute__((always_inline)) {
       const int64_t o = base + li;
-      f4 x = *reinterpret_cast<const f4*>(gx + o);
-      const f4 uv = *reinterpret_cast<const f4*>(u + o);
+      f32x4 x = *reinterpret_cast<const f32x4*>(gx + o);
+      const f32x4 uv = *reinterpret_cast<const f32x4*>(u + o);
       if (pj.v1) {
         const int f = li / HW, p = li - f * HW, r = p / W, c = p - r * W;
         const int ch = g * F + f;
         const int64_t po = ((int64_t)bg * F + f) * HW;
         const float *k1 = pj.t1 + ch * 5, *k2 = pj.t2 + ch * 5;
-        f4 y1 = padj4(pj.v1 + po, k1[0], k1[1], k1[2], k1[3], k1[4], r, c, H, W);
-        f4 y2 = padj4(pj.v2 + po, k2[0], k2[1], k2[2], k2[3], k2[4], r, c, H, W);
+        f32x4 y1 = padj4(pj.v1 + po, k1[0], k1[1], k1[2], k1[3], k1[4], r, c, H, W);
+        f32x4 y2 = padj4(pj.v2 + po, k2[0], k2[1], k2[2], k2[3], k2[4], r, c, H, W);
         y1 *= pj.s1[g];
         y2 *= pj.s2[g];
         x = (x + y1) + y2;
       }
       if (gxh) {   // the four columns sit over two half-level columns
-        const f2 q = *reinterpret_cast<const f2*>(gxh + half_at(li));
+        const f32x2 q = *reinterpret_cast<const f32x2*>(gxh + half_at(li));
         x.x += 0.25f * q.x; x.y += 0.25f * q.x; x.z += 0.25f * q.y; x.w += 0.25f * q.y;
       }
-      f4 gu = al * x;
-      if (gun) gu += be * *reinterpret_cast<const f4*>(gun + o);
+      f32x4 gu = al * x;
+      if (gun) gu += be * *reinterpret_cast<const f32x4*>(gun + o);
       da += x.x * uv.x + x.y * uv.y + x.z * uv.z + x.w * uv.w;
       if (up) {
-        const f4 pv = *reinterpret_cast<const f4*>(up + o);
+        const f32x4 pv = *reinterpret_cast<const f32x4*>(up + o);
         db += gu.x * pv.x + gu.y * pv.y + gu.z * pv.z + gu.w * pv.w;
       }
-      if (gbb) *reinterpret_cast<f4*>(gbb + o) += gu;
-      *reinterpret_cast<f4*>(gu_out + o) = gu;
-      *reinterpret_cast<f4*>(gx_out + o) = x - gu;
+      if (gbb) *reinterpret_cast<f32x4*>(gbb + o) += gu;
+      *reinterpret_cast<f32x4*>(gu_out + o) = gu;
+      *reinterpret_cast<f32x4*>(gx_out + o) = x - gu;
       return gu;
     };
     if (gud) {   // (f, half row, column quad) per step
@@ -686,11 +655,11 @@ __global__ __launch_bounds__(NT) void cg_glue_kernel(const float* gx, const floa
       for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < nq; i += (int64_t)gridDim.x * NT) {
         const int q = (int)i, f = q / hq, rem = q - f * hq, hr = rem / W4, c4 = rem - hr * W4;
         const int li = f * HW + 2 * hr * W + 4 * c4;
-        const f4 g0 = glue4(li), g1 = glue4(li + W);
-        f2 d;
+        const f32x4 g0 = glue4(li), g1 = glue4(li + W);
+        f32x2 d;
         d.x = 0.25f * g0.x + 0.25f * g0.y + 0.25f * g1.x + 0.25f * g1.y;
         d.y = 0.25f * g0.z + 0.25f * g0.w + 0.25f * g1.z + 0.25f * g1.w;
-        *reinterpret_cast<f2*>(gud + hbase + (int64_t)f * (HW / 4) + hr * w2 + 2 * c4) = d;
+        *reinterpret_cast<f32x2*>(gud + hbase + (int64_t)f * (HW / 4) + hr * w2 + 2 * c4) = d;
       }
     } else {
       const int64_t n4 = n / 4;
@@ -711,8 +680,8 @@ __global__ __launch_bounds__(NT) void cg_glue_kernel(const float* gx, const floa
       gx_out[o] = x - gu;
     }
   }
-  block_red_put(galpha, g, chunk_slot(G), da);
-  if (up) block_red_put(gbeta, g, chunk_slot(G), db);
+  block_red_put<NT>(galpha, g, chunk_slot(G), da);
+  if (up) block_red_put<NT>(gbeta, g, chunk_slot(G), db);
 }
 
 // out(q) += 0.25 * xd(q / 2)   (U = conv_transpose2d of the 0.25 2x2 kernel, stride 2; REF:676-679)
@@ -736,10 +705,9 @@ __global__ __launch_bounds__(NT) void unpool2_acc4_kernel(const float* __restric
   float* op = out + plane * H * W;
   for (int i = blockIdx.x * NT + threadIdx.x; i < n4; i += gridDim.x * NT) {
     const int r = i / W4, c4 = i - r * W4;
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    const f2 q = *reinterpret_cast<const f2*>(xp + (r >> 1) * w + 2 * c4);
-    f4v* dst = reinterpret_cast<f4v*>(op + r * W + 4 * c4);
-    f4v v = *dst;
+    const f32x2 q = *reinterpret_cast<const f32x2*>(xp + (r >> 1) * w + 2 * c4);
+    f32x4* dst = reinterpret_cast<f32x4*>(op + r * W + 4 * c4);
+    f32x4 v = *dst;
     v.x += 0.25f * q.x; v.y += 0.25f * q.x; v.z += 0.25f * q.y; v.w += 0.25f * q.y;
     *dst = v;
   }
@@ -935,14 +903,14 @@ __global__ __launch_bounds__(NT) void term_bwd_fused_kernel(
     }
   }
   const uint32_t slot = chunk_slot(G);
-  if (gdot.p) block_red_put(gdot, gi, slot, coef * dot);
+  if (gdot.p) block_red_put<NT>(gdot, gi, slot, coef * dot);
   if constexpr (MODE == 2) {
-    if (ggam.p) block_red_put(ggam, gi, slot, sc * dgam);
+    if (ggam.p) block_red_put<NT>(ggam, gi, slot, sc * dgam);
   }
 #pragma unroll
   for (int f = 0; f < F; ++f)
 #pragma unroll
-    for (int t = 0; t < 5; ++t) block_red_put(gtaps, (gi * F + f) * 5 + t, slot, sc * (accT[f][t] + accP[f][t]));
+    for (int t = 0; t < 5; ++t) block_red_put<NT>(gtaps, (gi * F + f) * 5 + t, slot, sc * (accT[f][t] + accP[f][t]));
 }
 
 // ---------------------------------------------------------------------------
@@ -972,42 +940,6 @@ int g_term_tail = [] {
   return e ? atoi(e) : 1;
 }();
 
-template <int V> struct RowT;
-template <> struct RowT<1> { typedef float T; };
-template <> struct RowT<2> { typedef float __attribute__((ext_vector_type(2))) T; };
-template <> struct RowT<4> { typedef float __attribute__((ext_vector_type(4))) T; };
-template <int V>
-__device__ __forceinline__ void rload(float (&d)[V], const float* p) {
-  const typename RowT<V>::T t = *reinterpret_cast<const typename RowT<V>::T*>(p);
-  if constexpr (V == 1) {
-    d[0] = t;
-  } else {
-#pragma unroll
-    for (int j = 0; j < V; ++j) d[j] = t[j];
-  }
-}
-template <int V>
-__device__ __forceinline__ void rstore(float* p, const float (&v)[V]) {
-  typename RowT<V>::T t;
-  if constexpr (V == 1) {
-    t = v[0];
-  } else {
-#pragma unroll
-    for (int j = 0; j < V; ++j) t[j] = v[j];
-  }
-  *reinterpret_cast<typename RowT<V>::T*>(p) = t;
-}
-__device__ __forceinline__ float lprev(float v) {   // lane - 1 (0 at lane 0)
-  float r = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x138, 0xF, 0xF, true));
-  asm volatile("" : "+v"(r));
-  return r;
-}
-__device__ __forceinline__ float lnext(float v) {   // lane + 1 (0 at lane 63)
-  float r = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xF, 0xF, true));
-  asm volatile("" : "+v"(r));
-  return r;
-}
-
 // Workgroup = F channel waves: up to 12 for V = 4 (a 768-thread bound caps the kernel at 168
 // VGPRs = 3 waves per SIMD, which also gives 4 three-wave workgroups per CU instead of 2 at the
 // 176-182 VGPRs the compiler picks unconstrained), up to 16 for V <= 2 (128 VGPRs).
@@ -1021,11 +953,6 @@ template <int V> struct TermRowMax { static constexpr int F = V == 4 ? 12 : 16; 
 // slower); 12 % faster at W = 128, 7 % at W = 512 (strips)
 __host__ __device__ constexpr bool term_gw_dma(int mode, int v, bool strips) {
   return mode != 2 && (strips || v < 4);
-}
-typedef __attribute__((address_space(3))) float* lds_f32_t;
-__device__ __forceinline__ void dma_dword(const float* src, float* lds_wave_base) {
-  const uint32_t m0v = (uint32_t)(uintptr_t)(lds_f32_t)lds_wave_base;
-  asm volatile("global_load_lds_dword %0, off" ::"v"(src), "{m0}"(__builtin_amdgcn_readfirstlane(m0v)) : "memory");
 }
 // PADJ: no v_out; the x-gradient pass that follows it (gx += scale[g] P*(v), grr_bwd_stencil mode 3 /
 // padj2) runs in the kernel one row behind v: v rows go to an LDS ring (P* reaches one row and one
@@ -1042,13 +969,6 @@ __device__ __forceinline__ void dma_dword(const float* src, float* lds_wave_base
 // slot the previous step read.  Column strips (W > 64 V) start on 16-byte boundaries: 64 V - 8 owned
 // columns, 4 halo columns per side.  Same arithmetic, same order: results equal the non-ring kernel's.
 constexpr int kRingRows(int V) { return 4 / V; }   // rows one 64-lane 16-byte DMA moves
-// scalar base + a loop-invariant per-lane byte offset: the VGPR operand is never rewritten while DMAs that
-// read it are in flight (a rewritten address VGPR drew compiler vmcnt(0) waits inside the issue loop)
-__device__ __forceinline__ void dma_row16(const float* sbase, uint32_t voff, float* lds_dst) {
-  const uint32_t m0v = (uint32_t)(uintptr_t)(lds_f32_t)lds_dst;
-  asm volatile("global_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "{m0}"(__builtin_amdgcn_readfirstlane(m0v))
-               : "memory");
-}
 // s_waitcnt vmcnt(n) for a wave-uniform run-time n (the immediate is 6 bits)
 __device__ __forceinline__ void vm_wait_rt(int n) {
   switch (n) {
@@ -1241,18 +1161,18 @@ __global__ __launch_bounds__(RING ? 64 * (TermRingMax<V>::F + 1) : 64 * TermRowM
   float accT[5] = {0.f, 0.f, 0.f, 0.f, 0.f}, accP[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
   float dot = 0.f, dgam = 0.f;
 
-  auto xrow = [&](float (&d)[V], int rr) { rload<V>(d, xp + (int64_t)clampi(rr, 0, H - 1) * W); };
+  auto xrow = [&](float (&d)[V], int rr) { row_load<V>(d, xp + (int64_t)clampi(rr, 0, H - 1) * W); };
   // always one load (a clamped row, zeroed outside the image): the prefetch's load count is fixed, which
   // the counted vmcnt of the gw / gx LDS-DMA rings below relies on (kAfter)
   auto grow = [&](float (&d)[V], int rr) {
-    rload<V>(d, gp + (int64_t)clampi(rr, 0, H - 1) * W);
+    row_load<V>(d, gp + (int64_t)clampi(rr, 0, H - 1) * W);
     if (rr < 0 || rr >= H) {
 #pragma unroll
       for (int j = 0; j < V; ++j) d[j] = 0.f;
     }
   };
   auto wrow = [&](float (&d)[V], int e, int rr) {   // rows outside the image are never used (selects)
-    rload<V>(d, wb + e * HW + (int64_t)clampi(rr, 0, H - 1) * W);
+    row_load<V>(d, wb + e * HW + (int64_t)clampi(rr, 0, H - 1) * W);
   };
   // prefetched operands of the next step
   float NX[V], NG[V], NW0[V], NW3[V], NW1[V], NW2[V];
@@ -1288,25 +1208,25 @@ __global__ __launch_bounds__(RING ? 64 * (TermRingMax<V>::F + 1) : 64 * TermRowM
     const float* vc = vring(q);
     const bool top = q == 0, bot = q == H - 1;
     float cv[V], uv[V], dv[V];
-    rload<V>(cv, vc + lc0);
+    row_load<V>(cv, vc + lc0);
     if (top) {
 #pragma unroll
       for (int j = 0; j < V; ++j) uv[j] = 0.f;
     } else {
-      rload<V>(uv, vring(q + 2) + lc0);
+      row_load<V>(uv, vring(q + 2) + lc0);
     }
     if (bot) {
 #pragma unroll
       for (int j = 0; j < V; ++j) dv[j] = 0.f;
     } else {
-      rload<V>(dv, vring(q + 1) + lc0);
+      row_load<V>(dv, vring(q + 1) + lc0);
     }
     const float lv = (c0 > 0 && lane > 0) ? vc[lc0 - 1] : 0.f;
     const float rv = (c0 + V < W && lane < 63) ? vc[lc0 + V] : 0.f;
     const float* os = oring(q) + lane;
     float gq[V];
     if constexpr (RING) {
-      rload<V>(gq, gx_lane);
+      row_load<V>(gq, gx_lane);
     } else {
 #pragma unroll
       for (int j = 0; j < V; ++j) gq[j] = os[j * 64];
@@ -1324,7 +1244,7 @@ __global__ __launch_bounds__(RING ? 64 * (TermRingMax<V>::F + 1) : 64 * TermRowM
       if (col == W - 1) y += k[3] * cv[j];
       o[j] = gq[j] + y * sc;
     }
-    if (on) rstore<V>(gxp + (int64_t)q * W, o);
+    if (on) row_store<V>(gxp + (int64_t)q * W, o);
   };
   auto gx_dma = [&](int q) {
 #pragma unroll
@@ -1338,22 +1258,22 @@ __global__ __launch_bounds__(RING ? 64 * (TermRingMax<V>::F + 1) : 64 * TermRowM
     const float* const slot_lane = rslot(sl) + lc0;
     if constexpr (RING) {
       sl = sl + 1 == ring_d ? 0 : sl + 1;
-      rload<V>(NX, slot_lane + f * (64 * V));
+      row_load<V>(NX, slot_lane + f * (64 * V));
       if (t >= 0 && t < H) {
-        rload<V>(NG, slot_lane + (ring_fx + f) * (64 * V));
+        row_load<V>(NG, slot_lane + (ring_fx + f) * (64 * V));
       } else {
 #pragma unroll
         for (int j = 0; j < V; ++j) NG[j] = 0.f;
       }
       const float* const wr = slot_lane + 2 * ring_fx * (64 * V);
       if constexpr (MODE == 1) {
-        rload<V>(NW0, wr);
-        rload<V>(NW3, wr + 64 * V);
+        row_load<V>(NW0, wr);
+        row_load<V>(NW3, wr + 64 * V);
       } else {
-        rload<V>(NW0, wr);
-        rload<V>(NW1, wr + 64 * V);
-        rload<V>(NW2, wr + 2 * (64 * V));
-        rload<V>(NW3, wr + 3 * (64 * V));
+        row_load<V>(NW0, wr);
+        row_load<V>(NW1, wr + 64 * V);
+        row_load<V>(NW2, wr + 2 * (64 * V));
+        row_load<V>(NW3, wr + 3 * (64 * V));
       }
     }
 #pragma unroll
@@ -1374,8 +1294,8 @@ __global__ __launch_bounds__(RING ? 64 * (TermRingMax<V>::F + 1) : 64 * TermRowM
     }
     // s = P x (replicate) and a = T* g (zero frame) at row t - 1
     {
-      const float xp_ = lprev(X[2][V - 1]), xn_ = lnext(X[2][0]);
-      const float gp_ = lprev(Gr[2][V - 1]), gn_ = lnext(Gr[2][0]);
+      const float xp_ = lane_prev(X[2][V - 1]), xn_ = lane_next(X[2][0]);
+      const float gp_ = lane_prev(Gr[2][V - 1]), gn_ = lane_next(Gr[2][0]);
 #pragma unroll
       for (int j = 0; j < V; ++j) {
         const int col = c0 + j;
@@ -1397,13 +1317,13 @@ __global__ __launch_bounds__(RING ? 64 * (TermRingMax<V>::F + 1) : 64 * TermRowM
     const bool own = !PADJ || (r >= r0 && r < r1);   // (PADJ) rows r0 - 1 and r1: v only
     // output row r: s, a rows r-1, r, r+1 = S[0..2]; x, g rows r-1, r, r+1 = X[0..2], Gr[0..2]
     const bool in0 = r > 0, in3 = r + 1 < H;
-    const float s_p = lprev(S[1][V - 1]), s_n = lnext(S[1][0]);
-    const float a_p = lprev(A[1][V - 1]), a_n = lnext(A[1][0]);
-    const float x_p = lprev(X[1][V - 1]), x_n = lnext(X[1][0]);
-    const float g_p = lprev(Gr[1][V - 1]), g_n = lnext(Gr[1][0]);
+    const float s_p = lane_prev(S[1][V - 1]), s_n = lane_next(S[1][0]);
+    const float a_p = lane_prev(A[1][V - 1]), a_n = lane_next(A[1][0]);
+    const float x_p = lane_prev(X[1][V - 1]), x_n = lane_next(X[1][0]);
+    const float g_p = lane_prev(Gr[1][V - 1]), g_n = lane_next(Gr[1][0]);
     float w1n = 0.f, w2p = 0.f, c0p = 0.f;
-    if constexpr (MODE == 1) c0p = lprev(W0[0][V - 1]);
-    else { w1n = lnext(W1[0]); w2p = lprev(W2[V - 1]); }
+    if constexpr (MODE == 1) c0p = lane_prev(W0[0][V - 1]);
+    else { w1n = lane_next(W1[0]); w2p = lane_prev(W2[V - 1]); }
     float vrow[V], gwa[WPL][V];
 #pragma unroll
     for (int j = 0; j < V; ++j) {
@@ -1496,12 +1416,12 @@ __global__ __launch_bounds__(RING ? 64 * (TermRingMax<V>::F + 1) : 64 * TermRowM
         accP[tt] += vv * xt[tt];
       }
     }
-    if constexpr (PADJ) rstore<V>(vring(r) + lc0, vrow);
-    else if (on) rstore<V>(vp + (int64_t)r * W, vrow);
+    if constexpr (PADJ) row_store<V>(vring(r) + lc0, vrow);
+    else if (on) row_store<V>(vp + (int64_t)r * W, vrow);
     // weight gradient: partials of the F channels -> LDS -> sum in channel order -> gw
     if (own) {
 #pragma unroll
-      for (int e = 0; e < WPL; ++e) rstore<V>(part(par, f, e) + lc0, gwa[e]);
+      for (int e = 0; e < WPL; ++e) row_store<V>(part(par, f, e) + lc0, gwa[e]);
       if constexpr (!RING) __syncthreads();
     }
     if constexpr (RING) ring_barrier();   // every step, halo rows included (the producer counts them)
@@ -1518,10 +1438,10 @@ __global__ __launch_bounds__(RING ? 64 * (TermRingMax<V>::F + 1) : 64 * TermRowM
     if (own) {
     for (int e = f; e < WPL; e += F) {
       float sum[V];
-      rload<V>(sum, part(par, 0, e) + lc0);
+      row_load<V>(sum, part(par, 0, e) + lc0);
       for (int ff = 1; ff < F; ++ff) {
         float pv[V];
-        rload<V>(pv, part(par, ff, e) + lc0);
+        row_load<V>(pv, part(par, ff, e) + lc0);
 #pragma unroll
         for (int j = 0; j < V; ++j) sum[j] += pv[j];
       }
@@ -1529,13 +1449,13 @@ __global__ __launch_bounds__(RING ? 64 * (TermRingMax<V>::F + 1) : 64 * TermRowM
         float* dst = gwb + e * HW + (int64_t)r * W;
         float cv[V];
         if constexpr (RING) {
-          rload<V>(cv, slot_lane + (2 * ring_fx + ring_wx + e) * (64 * V));
+          row_load<V>(cv, slot_lane + (2 * ring_fx + ring_wx + e) * (64 * V));
         } else if constexpr (kGwDma) {
           const float* sl = gring(r & 1, e) + lane;
 #pragma unroll
           for (int j = 0; j < V; ++j) cv[j] = sl[j * 64];
         } else {
-          rload<V>(cv, dst);
+          row_load<V>(cv, dst);
         }
 #pragma unroll
         for (int j = 0; j < V; ++j) {
@@ -1543,7 +1463,7 @@ __global__ __launch_bounds__(RING ? 64 * (TermRingMax<V>::F + 1) : 64 * TermRowM
           const bool keep = MODE != 1 || (e == 0 ? col + 1 < W : r + 1 < H);
           if (keep) cv[j] += sc * sum[j];
         }
-        rstore<V>(dst, cv);
+        row_store<V>(dst, cv);
       }
     }
     if constexpr (kGwDma) {
@@ -1675,7 +1595,7 @@ __global__ __launch_bounds__(NT) void edge_row_bwd_kernel(const float* __restric
     for (int j = 0; j < V; ++j) ss[j] = 0.f;
 #pragma unroll
     for (int f = 0; f < F; ++f) {
-      rload<V>(FE[slot][f], fp + f * HW + ro);
+      row_load<V>(FE[slot][f], fp + f * HW + ro);
 #pragma unroll
       for (int j = 0; j < V; ++j) ss[j] += FE[slot][f][j] * FE[slot][f][j];
     }
@@ -1684,8 +1604,8 @@ __global__ __launch_bounds__(NT) void edge_row_bwd_kernel(const float* __restric
     float wv[4][V], gv[4][V];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      rload<V>(wv[e], wb + e * HW + ro);
-      rload<V>(gv[e], gwb + e * HW + ro);
+      row_load<V>(wv[e], wb + e * HW + ro);
+      row_load<V>(gv[e], gwb + e * HW + ro);
     }
 #pragma unroll
     for (int j = 0; j < V; ++j) {
@@ -1715,11 +1635,11 @@ __global__ __launch_bounds__(NT) void edge_row_bwd_kernel(const float* __restric
     // output row r: rows r-1, r, r+1 in slots 0, 1, 2
     const bool in0 = r > 0, in3 = r + 1 < H;
     float gout[F][V];
-    const float icp = lprev(IC[1][V - 1]), icn = lnext(IC[1][0]);
-    const float g1n = lnext(GS[1][1][0]), g2p = lprev(GS[1][2][V - 1]);
+    const float icp = lane_prev(IC[1][V - 1]), icn = lane_next(IC[1][0]);
+    const float g1n = lane_next(GS[1][1][0]), g2p = lane_prev(GS[1][2][V - 1]);
     float fpv[F], fnx[F];
 #pragma unroll
-    for (int f = 0; f < F; ++f) { fpv[f] = lprev(FE[1][f][V - 1]); fnx[f] = lnext(FE[1][f][0]); }
+    for (int f = 0; f < F; ++f) { fpv[f] = lane_prev(FE[1][f][V - 1]); fnx[f] = lane_next(FE[1][f][0]); }
 #pragma unroll
     for (int j = 0; j < V; ++j) {
       const int col = c0 + j;
@@ -1767,7 +1687,7 @@ __global__ __launch_bounds__(NT) void edge_row_bwd_kernel(const float* __restric
     }
     if (on) {
 #pragma unroll
-      for (int f = 0; f < F; ++f) rstore<V>(gfp + f * HW + (int64_t)r * W, gout[f]);
+      for (int f = 0; f < F; ++f) row_store<V>(gfp + f * HW + (int64_t)r * W, gout[f]);
     }
   }
   const uint32_t wslot = ((uint32_t)b * nsegs + seg) * nstrips + strip;   // (b, segment, strip)
@@ -2034,240 +1954,13 @@ int chunks_for(int64_t n, int64_t planes) {
 }
 int blocks_for(int64_t n) { return (int)std::min<int64_t>((n + NT - 1) / NT, 1 << 16); }
 
-// dst[i] += sum_s part[i][s] for every planned reduction of a launch, slots in order: lane l adds
-// slots l, l + 64, ... in order, then the fixed shuffle tree.   grid (sum of n), one wave per value
-struct RedFinishArgs {
-  const float* part[RedScratch::kMax];
-  float* dst[RedScratch::kMax];
-  uint32_t nslot[RedScratch::kMax];
-  int first[RedScratch::kMax + 1];   // value ranges of the reductions in the grid
-  int k;
-};
-__global__ __launch_bounds__(64) void red_finish_kernel(RedFinishArgs a) {
-  int i = 0;
-  while (i + 1 < a.k && (int)blockIdx.x >= a.first[i + 1]) ++i;
-  const int idx = blockIdx.x - a.first[i];
-  const uint32_t nslot = a.nslot[i];
-  const float* row = a.part[i] + (size_t)idx * nslot;
-  float v = 0.f;
-  for (uint32_t s = threadIdx.x; s < nslot; s += 64) v += row[s];
-  v = wave_sum(v);
-  if (threadIdx.x == 0) a.dst[i][idx] += v;
-}
-
 }  // namespace
-
-// ---- RedScratch (grr_common.h) ---------------------------------------------
-// Scratch leases.  Each (device, stream) owns grow-only buffers, each leased by one RedScratch at a time
-// (alloc() to finish()); normally one per stream, a second one only while a lease is nested inside
-// another on the same stream.  Later calls on the same stream reuse a buffer: their kernels run after
-// the earlier finish kernel in stream order.  Memory comes from the allocator registered by
-// grr_set_scratch_allocator (the Python package registers PyTorch's caching allocator, so the scratch
-// is visible to and reclaimable through torch), else from hipMalloc / hipFree.  An outgrown buffer is
-// retired, not freed (a queued kernel may still read it), until grr_release_scratch.
-// A lease taken while its stream is being captured into a HIP graph is the graph's own: a
-// hipMallocAsync / hipFreeAsync pair on the capturing stream (memory nodes of the graph), never one of
-// the stream's buffers, so replays do not share memory with eager calls on that stream or with another
-// graph, and grr_release_scratch cannot free memory a graph still points at.
-namespace {
-struct ScratchBuf {
-  int dev;
-  hipStream_t s;
-  void* p;
-  size_t bytes;
-  bool cb;        // from the registered allocator
-  bool leased;
-};
-struct ScratchState {
-  grr_scratch_alloc_fn alloc = nullptr;
-  grr_scratch_free_fn free = nullptr;
-  void* ctx = nullptr;
-  std::vector<ScratchBuf> bufs;      // live buffers, by (device, stream)
-  std::vector<ScratchBuf> retired;   // outgrown, freed by grr_release_scratch
-  size_t total = 0;
-};
-ScratchState g_scratch;
-std::mutex g_scratch_mu;
-struct CaptureLease {
-  void* p;
-  hipStream_t s;
-};
-std::vector<CaptureLease> g_capture_leases;   // leased inside a stream capture, freed by scratch_return
-
-grr_status scratch_raw_alloc(int dev, hipStream_t s, size_t bytes, ScratchBuf* out, const char* what) {
-  void* p = nullptr;
-  bool cb = false;
-  if (g_scratch.alloc) {
-    p = g_scratch.alloc((uint64_t)bytes, dev, (void*)s, g_scratch.ctx);
-    cb = true;
-  } else if (hipMalloc(&p, bytes) != hipSuccess) {
-    p = nullptr;
-  }
-  if (!p) {
-    set_error("%s: reduction scratch of %zu bytes: allocation failed", what, bytes);
-    return GRR_ERR_HIP;
-  }
-  *out = ScratchBuf{dev, s, p, bytes, cb, false};
-  g_scratch.total += bytes;
-  return GRR_OK;
-}
-void scratch_raw_free(const ScratchBuf& b) {
-  if (b.cb) {
-    if (g_scratch.free) g_scratch.free(b.p, b.dev, (void*)b.s, g_scratch.ctx);
-  } else {
-    (void)hipFree(b.p);
-  }
-  g_scratch.total -= b.bytes;
-}
-
-// lease >= bytes for stream s (returned by scratch_return)
-grr_status scratch_lease(hipStream_t s, size_t bytes, void** out, const char* what) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) {
-    set_error("%s: hipGetDevice failed", what);
-    return GRR_ERR_HIP;
-  }
-  std::lock_guard<std::mutex> lk(g_scratch_mu);
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  GRR_REQUIRE(hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusInvalidated,
-              GRR_ERR_HIP, "%s: the stream's capture state is invalid", what);
-  if (cap == hipStreamCaptureStatusActive) {
-    void* p = nullptr;
-    if (hipMallocAsync(&p, std::max<size_t>(bytes, 256), s) != hipSuccess || !p) {
-      set_error("%s: reduction scratch of %zu bytes inside a stream capture: hipMallocAsync failed", what, bytes);
-      return GRR_ERR_HIP;
-    }
-    g_capture_leases.push_back(CaptureLease{p, s});
-    *out = p;
-    return GRR_OK;
-  }
-  ScratchBuf* small = nullptr;
-  for (auto& b : g_scratch.bufs) {
-    if (b.dev != dev || b.s != s || b.leased) continue;
-    if (b.bytes >= bytes) {
-      b.leased = true;
-      *out = b.p;
-      return GRR_OK;
-    }
-    small = &b;
-  }
-  size_t want = std::max<size_t>(bytes, (size_t)1 << 20);
-  if (small) want = std::max(want, 2 * small->bytes);
-  ScratchBuf nb{};
-  grr_status st = scratch_raw_alloc(dev, s, want, &nb, what);
-  if (st != GRR_OK) return st;
-  nb.leased = true;
-  if (small) {   // outgrown: retired (queued kernels may still read it), replaced
-    g_scratch.retired.push_back(*small);
-    *small = nb;
-  } else {       // first lease on this stream, or nested inside a live one
-    g_scratch.bufs.push_back(nb);
-  }
-  *out = nb.p;
-  return GRR_OK;
-}
-void scratch_return(void* p) {
-  std::lock_guard<std::mutex> lk(g_scratch_mu);
-  for (size_t i = 0; i < g_capture_leases.size(); ++i)
-    if (g_capture_leases[i].p == p) {   // after the finish kernel on the capturing stream: a free node
-      (void)hipFreeAsync(p, g_capture_leases[i].s);
-      g_capture_leases.erase(g_capture_leases.begin() + (std::ptrdiff_t)i);
-      return;
-    }
-  for (auto& b : g_scratch.bufs)
-    if (b.p == p) b.leased = false;
-}
-}  // namespace
-
-int RedScratch::plan(float* dst, int n, uint32_t nslot) {
-  const int i = k_++;
-  dst_[i] = dst;
-  n_[i] = n;
-  nslot_[i] = nslot < 1 ? 1 : nslot;
-  return i;
-}
-
-grr_status RedScratch::alloc(const char* what) {
-  size_t total = 0;
-  for (int i = 0; i < k_; ++i)
-    if (dst_[i]) total += (size_t)n_[i] * nslot_[i];
-  if (total == 0) return GRR_OK;
-  grr_status st = scratch_lease(s_, total * sizeof(float), &base_, what);
-  if (st != GRR_OK) {
-    base_ = nullptr;
-    return st;
-  }
-  float* p = static_cast<float*>(base_);
-  for (int i = 0; i < k_; ++i)
-    if (dst_[i]) {
-      part_[i] = p;
-      p += (size_t)n_[i] * nslot_[i];
-    }
-  // no fill: every contributor of a launch stores its slot (zero partials included)
-  return GRR_OK;
-}
-
-grr_status RedScratch::finish(const char* what) {
-  RedFinishArgs a{};
-  int total = 0;
-  for (int i = 0; i < k_; ++i)
-    if (dst_[i] && part_[i] && n_[i] > 0) {
-      a.part[a.k] = part_[i];
-      a.dst[a.k] = dst_[i];
-      a.nslot[a.k] = nslot_[i];
-      a.first[a.k] = total;
-      total += n_[i];
-      ++a.k;
-    }
-  a.first[a.k] = total;
-  if (total > 0) hipLaunchKernelGGL(red_finish_kernel, dim3(total), dim3(64), 0, s_, a);
-  grr_status st = launch_status(what);
-  if (base_) {
-    scratch_return(base_);
-    base_ = nullptr;
-  }
-  return st;
-}
-
-RedScratch::~RedScratch() {
-  if (base_) scratch_return(base_);   // an error path before finish(): nothing was added
-}
 
 }  // namespace grr
 
 using namespace grr;
 
 extern "C" {
-
-grr_status grr_set_scratch_allocator(grr_scratch_alloc_fn alloc, grr_scratch_free_fn free_fn, void* ctx) {
-  clear_error();
-  GRR_REQUIRE((alloc == nullptr) == (free_fn == nullptr), GRR_ERR_INVALID_ARG,
-              "grr_set_scratch_allocator: give both functions or neither");
-  std::lock_guard<std::mutex> lk(g_scratch_mu);
-  // buffers already handed out stay with the allocator that made them (ScratchBuf::cb); a buffer made
-  // by the previous registered allocator is freed through the new one only if that is the same pair
-  g_scratch.alloc = alloc;
-  g_scratch.free = free_fn;
-  g_scratch.ctx = ctx;
-  return GRR_OK;
-}
-
-grr_status grr_release_scratch(void) {
-  clear_error();
-  std::lock_guard<std::mutex> lk(g_scratch_mu);
-  for (const auto& b : g_scratch.bufs)
-    GRR_REQUIRE(!b.leased, GRR_ERR_INVALID_ARG, "grr_release_scratch: a reduction scratch is in use");
-  for (const auto& b : g_scratch.bufs) scratch_raw_free(b);
-  for (const auto& b : g_scratch.retired) scratch_raw_free(b);
-  g_scratch.bufs.clear();
-  g_scratch.retired.clear();
-  return GRR_OK;
-}
-
-int64_t grr_scratch_bytes(void) {
-  std::lock_guard<std::mutex> lk(g_scratch_mu);
-  return (int64_t)g_scratch.total;
-}
 
 grr_status grr_bwd_set_term_acc_max_w(int w) {
   clear_error();

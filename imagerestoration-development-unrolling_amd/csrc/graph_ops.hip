@@ -16,35 +16,13 @@
 // is evaluated LDS-to-LDS, followed by a fused epilogue (rhs / CG stage /
 // half-level term).  Everything is memory-bound (≈3.5 flop/B), so the design goal is HBM
 // bytes: each launch reads each of its inputs once and writes each output once.
-#include <cstdarg>
 #include <type_traits>
 
-#include "grr_common.h"
+#include "grr_device.h"
 
 namespace grr {
 
-static thread_local std::string g_err;
 static int g_kernel_variant = 0;   // grr_set_kernel_variant: 0 auto, 1 strip kernels only
-
-void set_error(const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  g_err = buf;
-}
-
-void clear_error() { g_err.clear(); }
-
-grr_status launch_status(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: %s", what, hipGetErrorString(e));
-    return GRR_ERR_HIP;
-  }
-  return GRR_OK;
-}
 
 constexpr int NT = 256;     // threads per workgroup (4 waves)
 constexpr int TILE = 32;    // output tile edge
@@ -272,20 +250,7 @@ static int seg_rows(int H, uint64_t units_per_seg) {
   return sseg < SSEG ? SSEG : sseg;
 }
 
-// Cross-lane reads must execute with the whole wave active: a DPP read of a lane that
-// is masked off returns 0.  The empty asm pins each result at its definition, so the
-// compiler cannot sink the v_mov_b32_dpp into a divergent branch (it turned
-// `c > 0 ? lane_prev(v) : 0` into an exec-masked branch before this was added).
-__device__ __forceinline__ float lane_prev(float v) {  // value of lane-1 (column c-1)
-  float r = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x138, 0xF, 0xF, true));
-  asm volatile("" : "+v"(r));
-  return r;
-}
-__device__ __forceinline__ float lane_next(float v) {  // value of lane+1 (column c+1)
-  float r = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xF, 0xF, true));
-  asm volatile("" : "+v"(r));
-  return r;
-}
+// Horizontal neighbours across lanes: the pinned lane_prev / lane_next of grr_device.h (column c-1 / c+1).
 
 // Addressing: a wave-uniform row base (SGPRs) + a per-lane 32-bit byte offset, so the
 // compiler can use the global_load/store "saddr" form with no per-access 64-bit VALU math.
@@ -568,12 +533,6 @@ __global__ __launch_bounds__(NT) void graph_op_kernel(OpArgs a) {
 // shift per row array and direction).  Image-edge columns apply the operators'
 // boundary rules explicitly (replicate for S, zero outside for S^T / C^T C).
 // ---------------------------------------------------------------------------
-typedef __attribute__((address_space(3))) float* lds_f32_t;
-template <int V> struct VecT;
-template <> struct VecT<1> { typedef float type; };
-template <> struct VecT<2> { typedef float __attribute__((ext_vector_type(2))) type; };
-template <> struct VecT<4> { typedef float __attribute__((ext_vector_type(4))) type; };
-
 template <int N>
 __device__ __forceinline__ void vload(float (&d)[N], const float* row_base, uint32_t off_bytes) {
   typedef typename VecT<N>::type T;
@@ -631,11 +590,9 @@ __device__ __forceinline__ void bstore(rsrc_t r, uint32_t off, const float (&v)[
 #pragma unroll
     for (int j = 0; j < N; ++j) t[j] = v[j];
     if constexpr (N == 2) {
-      typedef uint32_t U2 __attribute__((ext_vector_type(2)));
-      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(U2, t), r, off, 0, AUX);
+      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, t), r, off, 0, AUX);
     } else {
-      typedef uint32_t U4 __attribute__((ext_vector_type(4)));
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(U4, t), r, off, 0, AUX);
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, t), r, off, 0, AUX);
     }
   }
 }
@@ -973,11 +930,6 @@ void graph_row_kernel(OpArgs a) {
   if constexpr (LW) {
     // ring slot (pair q, parity) holds the weight rows of step t = ts + 2 q' + parity, q = q' mod 3
     if (producer) {
-      auto dma = [&](const float* src, float* dst) {
-        const uint32_t m0v = (uint32_t)(uintptr_t)(lds_f32_t)dst;
-        asm volatile("global_load_lds_dwordx4 %0, off" ::"v"(src), "{m0}"(__builtin_amdgcn_readfirstlane(m0v))
-                     : "memory");
-      };
       auto dma_pair = [&](int t, int q) {
         if constexpr (V == 4) {
 #pragma unroll
@@ -986,14 +938,14 @@ void graph_row_kernel(OpArgs a) {
             float* slot = wring + q * LW_PAIR + par * LW_PAR;
 #pragma unroll
             for (int e = 0; e < LW_ROWS; ++e)
-              dma(e < 4 ? pwl + e * HW + rw : pwg + (e - 4) * HW + rw, slot + e * 256);
+              dma16_opaque(e < 4 ? pwl + e * HW + rw : pwg + (e - 4) * HW + rw, slot + e * 256);
           }
         } else {   // W == 128: lanes 0-31 row t-2, lanes 32-63 row t-1, 4 columns each
           const int rw = clampi(t + (lane >> 5) - 2, 0, H - 1) * W + (lane & 31) * 4;
           float* slot = wring + q * LW_PAIR;
 #pragma unroll
           for (int e = 0; e < LW_ROWS; ++e)
-            dma(e < 4 ? pwl + e * HW + rw : pwg + (e - 4) * HW + rw, slot + e * 256);
+            dma16_opaque(e < 4 ? pwl + e * HW + rw : pwg + (e - 4) * HW + rw, slot + e * 256);
         }
       };
       dma_pair(ts, 0);
@@ -2241,7 +2193,6 @@ using namespace grr;
 
 // Streaming copy (one float4 per lane, non-temporal): the HBM ceiling the bench reports
 // beside the step kernel's rate (measured on the same GPU in the same run).
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(256) void stream_copy_kernel(const f32x4* __restrict__ src, f32x4* __restrict__ dst,
                                                           int64_t n4) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -2273,7 +2224,6 @@ grr_status grr_set_kernel_variant(int variant) {
   g_kernel_variant = variant;
   return GRR_OK;
 }
-const char* grr_last_error(void) { return g_err.c_str(); }
 
 grr_status grr_neighbor_table(int32_t* out, int H, int W, void* stream) {
   clear_error();

@@ -1,5 +1,7 @@
-// Shared helpers for the gfx950 kernels of libgrr.so (status plumbing, indexing,
-// XCD-aware block remap).  Written for CDNA4 only: wave64, 8 XCDs.
+// Shared by every translation unit of libgrr.so, host and device side: status plumbing and the host
+// runtime's declarations (runtime.hip), indexing, the XCD-aware block remap and the fixed-order
+// reductions' types.  Device primitives are in grr_device.h, split-operand arithmetic in grr_split.h.
+// Written for CDNA4 only: wave64, 8 XCDs.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -12,7 +14,7 @@
 
 namespace grr {
 
-// thread-local last error (grr_last_error)
+// thread-local last error (grr_last_error; runtime.hip)
 void set_error(const char* fmt, ...);
 void clear_error();
 
@@ -27,6 +29,9 @@ void clear_error();
 // Check the launch that was just queued on the stream.
 grr_status launch_status(const char* what);
 
+int num_cus();                  // compute units of the current device (cached per device)
+int64_t align64(int64_t n);     // n floats rounded up to a 256-byte boundary
+
 constexpr int kWave = 64;
 constexpr int kXcd = 8;
 
@@ -39,21 +44,6 @@ __device__ __forceinline__ uint32_t xcd_remap(uint32_t bid, uint32_t n) {
   const uint32_t base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
   return base + bid / kXcd;
 }
-
-// LocalNonLinearBlock on the split-bf16 MFMA kernels (lnb_ops.hip), C <= 128
-int64_t lnb_mfma_workspace_floats(int B, int C, int hid, int H, int W);
-int64_t fused_pack_floats(int C, int hid);   // the fused block's chunk images + W2 row scales
-bool lnb_fused(int C, int hid);
-// C <= 96 runs the whole block as one fused pass (lnb_fused16_kernel); keep_g: it also stores the gated
-// activation g [B, hid, H, W] at the workspace's start (where the two-kernel path leaves it anyway)
-bool lnb_fused(int C, int hid);
-grr_status lnb_forward_mfma(const float* x, const float* ln_w, const float* w1, const float* wdw, const float* w2,
-                            const float* skip, float* out, float* ws, int B, int C, int hid, int H, int W,
-                            hipStream_t s, bool keep_g = false, int io = 0);
-// the same block when x holds R stacked copies of the Ch-channel image xh (GEMM1 runs on xh)
-grr_status lnb_forward_mfma_rep(const float* xh, int Ch, int R, const float* x, const float* ln_w, const float* w1,
-                                const float* wdw, const float* w2, const float* skip, float* out, float* ws, int B,
-                                int hid, int H, int W, hipStream_t s);
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
@@ -75,7 +65,7 @@ __device__ __forceinline__ void red_put(const Red& r, int idx, uint32_t slot, fl
 
 // Host side: the partial arrays of one launch, carved from a scratch buffer leased for the stream (a
 // per-stream grow-only buffer from the registered allocator -- PyTorch's caching allocator in the
-// Python package -- or hipMalloc; grr_set_scratch_allocator, graph_bwd.hip), then finished (one launch
+// Python package -- or hipMalloc; grr_set_scratch_allocator, runtime.hip), then finished (one launch
 // for all of them) and returned.  Every kernel stores every slot of its plan (zero partials included),
 // so the scratch needs no fill.
 class RedScratch {

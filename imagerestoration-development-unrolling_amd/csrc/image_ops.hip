@@ -36,13 +36,10 @@
 // inside [0, arena_elems): reads are clamped, writes outside are dropped.
 #include <algorithm>
 
-#include "grr_common.h"
+#include "grr_device.h"
 
 namespace grr {
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kIoThreads = 256;
 constexpr int kMaxSegments = 65535;                  // grr_u8_sse_segments: one grid row (blockIdx.y) per segment

@@ -12,37 +12,12 @@
 // HIP conv1x1; their weight gradients are library GEMMs (host side).
 #include <algorithm>
 
-#include "grr_common.h"
+#include "grr_device.h"
 
 namespace grr {
 namespace {
 
 constexpr int NT = 256;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-// one partial per block (grr_common.h, fixed-order reductions): wave sums -> LDS -> thread 0 adds
-// them in wave order and stores the block's slot
-__device__ __forceinline__ void block_red_put(const Red& r, int idx, uint32_t slot, float v) {
-  __shared__ float red[NT / 64];
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float t = 0.f;
-#pragma unroll
-    for (int i = 0; i < NT / 64; ++i) t += red[i];
-    red_put(r, idx, slot, t);
-  }
-}
-// slot of block (blockIdx.x, blockIdx.y) of a (chunks, B * per) grid: one per (b, chunk)
-__device__ __forceinline__ uint32_t chunk_slot(int per) {
-  return (uint32_t)(blockIdx.y / per) * gridDim.x + blockIdx.x;
-}
 
 // n = ln_w x isd, isd per pixel.   grid-stride over B*P pixels
 __global__ __launch_bounds__(NT) void ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ lnw,
@@ -111,7 +86,7 @@ __global__ __launch_bounds__(NT) void ln_bwd_kernel(const float* __restrict__ x,
       }
     }
   }
-  if constexpr (SKIP) block_red_put(gdot, 0, blockIdx.x, dacc);
+  if constexpr (SKIP) block_red_put<NT>(gdot, 0, blockIdx.x, dacc);
 }
 
 // gw[c] += sum_{b,p} u v isd(b,p)          grid (chunks, B*C)
@@ -124,7 +99,7 @@ __global__ __launch_bounds__(NT) void ln_wgrad_kernel(const float* __restrict__ 
   float acc = 0.f;
   for (int64_t p = blockIdx.x * (int64_t)NT + threadIdx.x; p < P; p += (int64_t)gridDim.x * NT)
     acc += up[p] * vp[p] * sp[p];
-  block_red_put(gw, c, chunk_slot(C), acc);
+  block_red_put<NT>(gw, c, chunk_slot(C), acc);
 }
 
 // h'(p) = sum_t w_t h(clamp(p + t)), t = (dy, dx) in {-1,0,1}^2, tap index (dy+1)*3 + dx+1
@@ -206,7 +181,7 @@ __global__ __launch_bounds__(NT) void dw3_wgrad_kernel(const float* __restrict__
         acc[(dy + 1) * 3 + dx + 1] += gv * hp[clampi(r + dy, 0, H - 1) * W + clampi(col + dx, 0, W - 1)];
   }
 #pragma unroll
-  for (int t = 0; t < 9; ++t) block_red_put(gw, c * 9 + t, chunk_slot(C), acc[t]);
+  for (int t = 0; t < 9; ++t) block_red_put<NT>(gw, c * 9 + t, chunk_slot(C), acc[t]);
 }
 
 // gate = sigmoid(m) m v (if gate != NULL); gm, gv from ggate (if ggate != NULL).   hp [B, 2hid, P]
@@ -246,7 +221,7 @@ __global__ __launch_bounds__(NT) void gate_bwd_scaled_kernel(const float* __rest
     ghp[om] = gg * v * (sg + m * sg * (1.0f - sg));
     ghp[ov] = gg * sg * m;
   }
-  block_red_put(gdot, 0, blockIdx.x, dot);
+  block_red_put<NT>(gdot, 0, blockIdx.x, dot);
 }
 
 // ---------------------------------------------------------------------------
@@ -256,44 +231,7 @@ __global__ __launch_bounds__(NT) void gate_bwd_scaled_kernel(const float* __rest
 // neighbours come from DPP lane shifts.  The per-pixel kernels above issue nine scalar
 // loads per output pixel and are L1-bound (dwconv3 2.3 TB/s, dwconv3_bwd 1.6 TB/s).
 // ---------------------------------------------------------------------------
-template <int V> struct RowVec;
-template <> struct RowVec<1> { typedef float T; };
-template <> struct RowVec<2> { typedef float __attribute__((ext_vector_type(2))) T; };
-template <> struct RowVec<4> { typedef float __attribute__((ext_vector_type(4))) T; };
-template <> struct RowVec<8> { typedef float __attribute__((ext_vector_type(8))) T; };
-
-template <int V>
-__device__ __forceinline__ void row_load(float (&d)[V], const float* p) {
-  const typename RowVec<V>::T t = *reinterpret_cast<const typename RowVec<V>::T*>(p);
-  if constexpr (V == 1) {
-    d[0] = t;
-  } else {
-#pragma unroll
-    for (int j = 0; j < V; ++j) d[j] = t[j];
-  }
-}
-template <int V>
-__device__ __forceinline__ void row_store(float* p, const float (&v)[V]) {
-  typename RowVec<V>::T t;
-  if constexpr (V == 1) {
-    t = v[0];
-  } else {
-#pragma unroll
-    for (int j = 0; j < V; ++j) t[j] = v[j];
-  }
-  *reinterpret_cast<typename RowVec<V>::T*>(p) = t;
-}
-// value of lane -1 / +1 (0 past the wave's ends); the asm pins the DPP at its definition
-__device__ __forceinline__ float dpp_prev(float v) {
-  float r = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x138, 0xF, 0xF, true));
-  asm volatile("" : "+v"(r));
-  return r;
-}
-__device__ __forceinline__ float dpp_next(float v) {
-  float r = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xF, 0xF, true));
-  asm volatile("" : "+v"(r));
-  return r;
-}
+// (row_load / row_store and the pinned DPP shifts lane_prev / lane_next: grr_device.h)
 
 // Rows wider than one wave (W > 64 V, W % V == 0) run as column strips: strip k's waves hold columns
 // [x0, x0 + 64 V), x0 = k STEP - V (0 for the first), and own the output columns [k STEP, (k + 1) STEP):
@@ -361,7 +299,7 @@ __global__ __launch_bounds__(NT) void dw3_row_fwd_kernel(const float* __restrict
     for (int j = 0; j < V; ++j) o[j] = 0.f;
 #pragma unroll
     for (int dy = 0; dy < 3; ++dy) {
-      const float pv = dpp_prev(R[dy][V - 1]), nx = dpp_next(R[dy][0]);
+      const float pv = lane_prev(R[dy][V - 1]), nx = lane_next(R[dy][0]);
 #pragma unroll
       for (int j = 0; j < V; ++j) {
         const int col = q.c0 + j;
@@ -434,7 +372,7 @@ __global__ __launch_bounds__(NT) void dw3_row_bwd_kernel(const float* __restrict
     for (int j = 0; j < V; ++j) o[j] = 0.f;
 #pragma unroll
     for (int dy = 0; dy < 3; ++dy) {
-      const float pv = dpp_prev(A[dy][V - 1]), nx = dpp_next(A[dy][0]);
+      const float pv = lane_prev(A[dy][V - 1]), nx = lane_next(A[dy][0]);
 #pragma unroll
       for (int j = 0; j < V; ++j) {
         const int col = q.c0 + j;
@@ -452,7 +390,7 @@ __global__ __launch_bounds__(NT) void dw3_row_bwd_kernel(const float* __restrict
     // weight gradient: g(r, c) h(clamp(r + dy), clamp(c + dx))
 #pragma unroll
     for (int dy = 0; dy < 3; ++dy) {
-      const float pv = dpp_prev(Hh[dy][V - 1]), nx = dpp_next(Hh[dy][0]);
+      const float pv = lane_prev(Hh[dy][V - 1]), nx = lane_next(Hh[dy][0]);
 #pragma unroll
       for (int j = 0; j < V; ++j) {
         const int col = q.c0 + j;
@@ -490,7 +428,7 @@ __device__ __forceinline__ void dw3_row_out(const float (&R0)[V], const float (&
 #pragma unroll
   for (int dy = 0; dy < 3; ++dy) {
     const float* R = Rs[dy];
-    const float pv = dpp_prev(R[V - 1]), nx = dpp_next(R[0]);
+    const float pv = lane_prev(R[V - 1]), nx = lane_next(R[0]);
 #pragma unroll
     for (int k = 0; k < V; ++k) {
       const int col = c0 + k;
@@ -698,7 +636,7 @@ __global__ __launch_bounds__(NT) void dw3_gate_row_bwd_kernel(
     for (int k = 0; k < V; ++k) o[k] = 0.f;
 #pragma unroll
     for (int dy = 0; dy < 3; ++dy) {
-      const float pvv = dpp_prev(A[dy][V - 1]), nx = dpp_next(A[dy][0]);
+      const float pvv = lane_prev(A[dy][V - 1]), nx = lane_next(A[dy][0]);
 #pragma unroll
       for (int k = 0; k < V; ++k) {
         const int col = q.c0 + k;
@@ -715,7 +653,7 @@ __global__ __launch_bounds__(NT) void dw3_gate_row_bwd_kernel(
     if (q.on) row_store<V>(dst + (int64_t)r * W, o);
 #pragma unroll
     for (int dy = 0; dy < 3; ++dy) {
-      const float pvv = dpp_prev(Hp[dy][V - 1]), nx = dpp_next(Hp[dy][0]);
+      const float pvv = lane_prev(Hp[dy][V - 1]), nx = lane_next(Hp[dy][0]);
 #pragma unroll
       for (int k = 0; k < V; ++k) {
         const int col = q.c0 + k;
@@ -774,11 +712,6 @@ __host__ __device__ constexpr int dw3_ring_depth(int V) { return V == 8 ? 3 : DW
 // 0 the register kernel (A/B and tests)
 int g_dw3_bwd_ring = 1;
 #define HW_ALIGNED(H, W) (((int64_t)(H) * (W)) % 4 == 0)
-__device__ __forceinline__ void dma_row16s(const float* sbase, uint32_t voff, float* lds_dst) {
-  const uint32_t m0v = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) float*)lds_dst;
-  asm volatile("global_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "{m0}"(__builtin_amdgcn_readfirstlane(m0v))
-               : "memory");
-}
 // a wave-uniform pointer the compiler cannot prove uniform (derived from threadIdx.x >> 6) into SGPRs
 __device__ __forceinline__ const float* uniform_ptr(const float* p) {
   const uint64_t v = (uint64_t)(uintptr_t)p;
@@ -837,13 +770,13 @@ __global__ __launch_bounds__(NT) void dw3_gate_row_bwd_ring_kernel(
   auto issue = [&](int r, int sl) {   // rows of iteration r: gq row r + 1, hh rows r + 2
     if (dma_lane) {
       float* dst = ring + sl * (3 * RW);
-      dma_row16s(uniform_ptr(gq0 + (int64_t)clampi(r + 1, 0, H - 1) * W), voff, dst);
-      dma_row16s(uniform_ptr(hm0 + (int64_t)clampi(r + 2, 0, H - 1) * W), voff, dst + RW);
-      dma_row16s(uniform_ptr(hv0 + (int64_t)clampi(r + 2, 0, H - 1) * W), voff, dst + 2 * RW);
+      dma_row16(uniform_ptr(gq0 + (int64_t)clampi(r + 1, 0, H - 1) * W), voff, dst);
+      dma_row16(uniform_ptr(hm0 + (int64_t)clampi(r + 2, 0, H - 1) * W), voff, dst + RW);
+      dma_row16(uniform_ptr(hv0 + (int64_t)clampi(r + 2, 0, H - 1) * W), voff, dst + 2 * RW);
       if constexpr (RG::NDMA == 2) {   // the second KB of each 2-KB row
-        dma_row16s(uniform_ptr(gq0 + (int64_t)clampi(r + 1, 0, H - 1) * W), voff1, dst + RG::LANES * 4);
-        dma_row16s(uniform_ptr(hm0 + (int64_t)clampi(r + 2, 0, H - 1) * W), voff1, dst + RW + RG::LANES * 4);
-        dma_row16s(uniform_ptr(hv0 + (int64_t)clampi(r + 2, 0, H - 1) * W), voff1, dst + 2 * RW + RG::LANES * 4);
+        dma_row16(uniform_ptr(gq0 + (int64_t)clampi(r + 1, 0, H - 1) * W), voff1, dst + RG::LANES * 4);
+        dma_row16(uniform_ptr(hm0 + (int64_t)clampi(r + 2, 0, H - 1) * W), voff1, dst + RW + RG::LANES * 4);
+        dma_row16(uniform_ptr(hv0 + (int64_t)clampi(r + 2, 0, H - 1) * W), voff1, dst + 2 * RW + RG::LANES * 4);
       }
     }
   };
@@ -916,7 +849,7 @@ __global__ __launch_bounds__(NT) void dw3_gate_row_bwd_ring_kernel(
     for (int k = 0; k < V; ++k) o[k] = 0.f;
 #pragma unroll
     for (int dy = 0; dy < 3; ++dy) {
-      const float pvv = dpp_prev(A[dy][V - 1]), nx = dpp_next(A[dy][0]);
+      const float pvv = lane_prev(A[dy][V - 1]), nx = lane_next(A[dy][0]);
 #pragma unroll
       for (int k = 0; k < V; ++k) {
         const int col = q.c0 + k;
@@ -934,7 +867,7 @@ __global__ __launch_bounds__(NT) void dw3_gate_row_bwd_ring_kernel(
 #pragma unroll
     for (int dy = 0; dy < 3; ++dy) {
       const float* Hd = Hp[dy];
-      const float pvv = dpp_prev(Hd[V - 1]), nx = dpp_next(Hd[0]);
+      const float pvv = lane_prev(Hd[V - 1]), nx = lane_next(Hd[0]);
 #pragma unroll
       for (int k = 0; k < V; ++k) {
         const int col = q.c0 + k;

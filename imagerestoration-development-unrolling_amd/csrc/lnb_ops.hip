@@ -28,73 +28,14 @@
 //    g loaded two k-steps ahead and split in registers (B operand of
 //    v_mfma_f32_32x32x16_bf16, 32 consecutive pixels per 32-lane half = 128-B loads).
 //
-// Arithmetic: both GEMMs use the exact 3-term bf16 split of feature_ops.hip (six products,
+// Arithmetic: both GEMMs use the exact 3-term bf16 split of grr_split.h (six products,
 // fp32-accurate); depthwise 3x3 and the gate in fp32 with the reference's tap order.
 #include <cstdlib>
 
-#include "grr_common.h"
+#include "grr_split.h"
+#include "lnb_ops.h"
 
 namespace grr {
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-// exact split v = v0 + v1 + v2 of 8 values into bf16 terms (RNE casts: v_cvt_pk_bf16_f32)
-__device__ __forceinline__ void split3x8(const float (&v)[8], bf16x8& t0, bf16x8& t1, bf16x8& t2) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const __bf16 h0 = (__bf16)v[j];
-    const float r1 = v[j] - (float)h0;
-    const __bf16 h1 = (__bf16)r1;
-    const float r2 = r1 - (float)h1;
-    t0[j] = h0;
-    t1[j] = h1;
-    t2[j] = (__bf16)r2;
-  }
-}
-__host__ __device__ inline uint16_t bf16_bits_rne(float v) {
-  uint32_t u;
-  __builtin_memcpy(&u, &v, 4);
-  return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
-__device__ __forceinline__ float bf16_bits_val(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
-__device__ __forceinline__ uint16_t split_term(float v, int q) {
-  const uint16_t h0 = bf16_bits_rne(v);
-  if (q == 0) return h0;
-  const float r1 = v - bf16_bits_val(h0);
-  const uint16_t h1 = bf16_bits_rne(r1);
-  if (q == 1) return h1;
-  return bf16_bits_rne(r1 - bf16_bits_val(h1));
-}
-
-// six-product accumulation of (a0+a1+a2)(b0+b1+b2), smallest terms first
-#define GRR_X3_MFMA(FN, acc, a0, a1, a2, b0, b1, b2) \
-  do {                                               \
-    acc = FN(a1, b1, acc, 0, 0, 0);                  \
-    acc = FN(a2, b0, acc, 0, 0, 0);                  \
-    acc = FN(a0, b2, acc, 0, 0, 0);                  \
-    acc = FN(a1, b0, acc, 0, 0, 0);                  \
-    acc = FN(a0, b1, acc, 0, 0, 0);                  \
-    acc = FN(a0, b0, acc, 0, 0, 0);                  \
-  } while (0)
-
-__device__ __forceinline__ void dma16(const void* src, float* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds(src, (lds_ptr_t)lds_wave_base, 16, 0, 0);
-}
-// The same 16-byte LDS-DMA as an asm statement.  hipcc answers every LDS-DMA builtin with
-// lgkmcnt(0) waits at all later LDS reads (it cannot order the DMA's LDS write against them);
-// the head kernel orders its ring itself (counted vmcnt + barrier), so it issues the DMA
-// opaquely and keeps the compiler's counted lgkmcnt waits.  The compiler does not count these
-// operations: they are only issued where no compiler-visible vector-memory load is pending
-// behind them.
-typedef __attribute__((address_space(3))) float* lds_f32_t;
-__device__ __forceinline__ void dma16_opaque(const void* src, float* lds_wave_base) {
-  const uint32_t m0v = (uint32_t)(uintptr_t)(lds_f32_t)lds_wave_base;
-  asm volatile("global_load_lds_dwordx4 %0, off" ::"v"(src), "{m0}"(__builtin_amdgcn_readfirstlane(m0v)) : "memory");
-}
 
 // ---------------------------------------------------------------------------
 // head: LN + W1 + dw3x3 + gate
@@ -384,8 +325,6 @@ constexpr int L6_XE = 10;                   // common power-of-two scale of the 
 constexpr int L6_TAPF = L6_NP * 18;         // tap floats per chunk
 __host__ __device__ constexpr int head16_images(int KS) { return 2 * KS + 2; }   // fp16 hi/lo per k-step + 2 tap images
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 // largest |W1 diag(ln_w)| entry of GEMM row `row` (folded over the R replicas) -> its scale exponent
 __device__ __forceinline__ int head16_row_exp(const float* __restrict__ w1, const float* __restrict__ ln_w, int row,
                                               int C, int R) {
@@ -568,9 +507,7 @@ __global__ __launch_bounds__(64 * NW, 1) void lnb_head16_kernel(LnbHeadArgs a) {
       const f16x8 al = *reinterpret_cast<const f16x8*>(slot + (2 * s + 1) * 256);
 #pragma unroll
       for (int blk = 0; blk < NB; ++blk) {
-        acc[blk] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, xh[blk][s], acc[blk], 0, 0, 0);
-        acc[blk] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, xl[blk][s], acc[blk], 0, 0, 0);
-        acc[blk] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, xh[blk][s], acc[blk], 0, 0, 0);
+        GRR_X2_MFMA(__builtin_amdgcn_mfma_f32_32x32x16_f16, acc[blk], ah, al, xh[blk][s], xl[blk][s]);
       }
     }
   };
@@ -722,13 +659,6 @@ struct LnbRepArgs {
   uint32_t nblk;
 };
 
-// scale exponent of a row whose largest |entry| is mx: mx 2^s in [2^13, 2^14)
-__device__ __forceinline__ int rep_scale_exp(float mx) {
-  if (mx == 0.f) return 0;
-  int e;
-  frexpf(mx, &e);
-  return clampi(14 - e, -60, 60);
-}
 __device__ __forceinline__ float rep_w1f(const float* __restrict__ w1, const float* __restrict__ ln_w, int row, int c,
                                          int Cs, int R) {
   float w = 0.f;
@@ -743,17 +673,12 @@ __device__ __forceinline__ int rep_row_exp(const float* __restrict__ w1, const f
     const float w = rep_w1f(w1, ln_w, row, c, Cs, R);
     for (int t = 0; t < 9; ++t) mx = fmaxf(mx, fabsf(wdw[(int64_t)row * 9 + t] * w));
   }
-  return rep_scale_exp(mx);
+  return scale_exp(mx, 60);
 }
 __device__ __forceinline__ int rep_w2_exp(const float* __restrict__ w2, int m, int hid) {
   float mx = 0.f;
   for (int k = 0; k < hid; ++k) mx = fmaxf(mx, fabsf(w2[(int64_t)m * hid + k]));
-  return rep_scale_exp(mx);
-}
-__device__ __forceinline__ uint32_t f16_pair_word(float a, float b, int q) {   // term q (0 hi, 1 lo) of a, b
-  const _Float16 ha = (_Float16)a, hb = (_Float16)b;
-  const _Float16 ta = q == 0 ? ha : (_Float16)(a - (float)ha), tb = q == 0 ? hb : (_Float16)(b - (float)hb);
-  return (uint32_t)__builtin_bit_cast(uint16_t, ta) | ((uint32_t)__builtin_bit_cast(uint16_t, tb) << 16);
+  return scale_exp(mx, 60);
 }
 
 // Per chunk c (16 pairs): images 0..3 = A1 (k-step s = im >> 1, term hi / lo = im & 1; lane l, element j:
@@ -911,9 +836,7 @@ __global__ __launch_bounds__(64 * LR_NW, MT <= 3 ? 4 : 3) void lnb_rep_kernel(Ln
     for (int s2 = 0; s2 < 2; ++s2) {
       const f16x8 ah = *reinterpret_cast<const f16x8*>(slot + (2 * s2 + 0) * 256);
       const f16x8 al = *reinterpret_cast<const f16x8*>(slot + (2 * s2 + 1) * 256);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, xh[s2], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, xl[s2], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, xh[s2], acc, 0, 0, 0);
+      GRR_X2_MFMA(__builtin_amdgcn_mfma_f32_32x32x16_f16, acc, ah, al, xh[s2], xl[s2]);
     }
     return acc;
   };
@@ -972,9 +895,7 @@ __global__ __launch_bounds__(64 * LR_NW, MT <= 3 ? 4 : 3) void lnb_rep_kernel(Ln
     for (int t = 0; t < MT; ++t) {
       const f16x8 ah = *reinterpret_cast<const f16x8*>(slot + (4 + 2 * t + 0) * 256);
       const f16x8 al = *reinterpret_cast<const f16x8*>(slot + (4 + 2 * t + 1) * 256);
-      acc2[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, gh, acc2[t], 0, 0, 0);
-      acc2[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, gl, acc2[t], 0, 0, 0);
-      acc2[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, gh, acc2[t], 0, 0, 0);
+      GRR_X2_MFMA(__builtin_amdgcn_mfma_f32_32x32x16_f16, acc2[t], ah, al, gh, gl);
     }
   };
 
@@ -1129,18 +1050,7 @@ __global__ void lnb_fused_pack_kernel(const float* __restrict__ w1, const float*
   }
 }
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(4))) const float* const_f32_t;
-typedef float f32x2v __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-// exact two-term fp16 split of (a, b) with packed round-to-nearest conversions (v_cvt_pk_f16_f32): hi, lo
-__device__ __forceinline__ void split2_f16(float a, float b, uint32_t& hi, uint32_t& lo) {
-  const f32x2v v = f32x2v{a, b};
-  const f16x2 h = __builtin_convertvector(v, f16x2);
-  const f16x2 l = __builtin_convertvector(v - __builtin_convertvector(h, f32x2v), f16x2);
-  hi = __builtin_bit_cast(uint32_t, h);
-  lo = __builtin_bit_cast(uint32_t, l);
-}
 // consumer mapping: lane per (column, pair half), two rows per lane, taps from the LDS ring (a lane per
 // pixel with scalar taps and B operands by v_permlane32_swap measured slower)
 
@@ -1360,9 +1270,7 @@ __global__ __launch_bounds__(512, 1) void lnb_fused16_kernel(LnbFusedArgs a) {
 #pragma unroll
           for (int k = 0; k < NBW; ++k) {
             if (k == NBW - 1 && !has_last) continue;
-            acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, xh[k][s], acc[k], 0, 0, 0);
-            acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, xl[k][s], acc[k], 0, 0, 0);
-            acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, xh[k][s], acc[k], 0, 0, 0);
+            GRR_X2_MFMA(__builtin_amdgcn_mfma_f32_32x32x16_f16, acc[k], ah, al, xh[k][s], xl[k][s]);
           }
           if (s + 1 < KS) {
             ah = bh;
@@ -1549,9 +1457,7 @@ __global__ __launch_bounds__(512, 1) void lnb_fused16_kernel(LnbFusedArgs a) {
         for (int t = 0; t < MT; ++t) {
           const f16x8 ah = *reinterpret_cast<const f16x8*>(w2s + (2 * t + 0) * 256);
           const f16x8 al = *reinterpret_cast<const f16x8*>(w2s + (2 * t + 1) * 256);
-          acc2[rb][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, gh, acc2[rb][t], 0, 0, 0);
-          acc2[rb][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, gl, acc2[rb][t], 0, 0, 0);
-          acc2[rb][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, gh, acc2[rb][t], 0, 0, 0);
+          GRR_X2_MFMA(__builtin_amdgcn_mfma_f32_32x32x16_f16, acc2[rb][t], ah, al, gh, gl);
         }
       }
       FSTAMP(2);
@@ -1822,7 +1728,6 @@ __global__ __launch_bounds__(256, MT >= 4 ? 1 : 2) void lnb_mix_kernel(LnbMixArg
 // host side
 static int head_ks(int C) { return (C + 31) / 32; }
 static int head_nb(int KS) { return KS <= 3 ? 4 : 3; }
-static int64_t align64(int64_t n) { return (n + 63) / 64 * 64; }
 // GEMM1 on the fp16 two-term head (lnb_head16_kernel): C <= 96 (its 2-slot ring + 2 x 64 KB of
 // h planes fill the CU's LDS at 6 k-steps); 96 < C <= 128 runs the split-bf16 head (lnb_head_kernel)
 static int head16_ks(int C) { return (C + 15) / 16; }
@@ -1880,18 +1785,6 @@ static void launch_fused(const LnbFusedArgs& f, unsigned grid, int io, hipStream
     case 3: hipLaunchKernelGGL((lnb_fused16_kernel<KS, (KS + 1) / 2, 3>), dim3(grid), dim3(512), 0, s, f); break;
     default: hipLaunchKernelGGL((lnb_fused16_kernel<KS, (KS + 1) / 2, 0>), dim3(grid), dim3(512), 0, s, f);
   }
-}
-// compute units of the current device (cached per device)
-static int num_cus() {
-  static int cache[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-  if (!cache[dev]) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    cache[dev] = n;
-  }
-  return cache[dev];
 }
 
 grr_status lnb_forward_mfma(const float* x, const float* ln_w, const float* w1, const float* wdw, const float* w2,

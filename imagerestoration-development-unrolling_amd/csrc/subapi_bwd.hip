@@ -13,7 +13,7 @@
 // block (grr_common.h).
 // These are off the solver's path (it fuses the same arithmetic in graph_bwd.hip); one thread per
 // output pixel, HBM-bound.
-#include "grr_common.h"
+#include "grr_device.h"
 
 namespace grr {
 
@@ -55,7 +55,7 @@ __device__ __forceinline__ void block_red(float (&v)[NV], const Red& r, int idx0
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
   for (int k = 0; k < NV; ++k) {
-    float s = v[k];
+    float s = v[k];   // not wave_sum: through it this kernel's assembly differed (device-assembly check)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
     if (lane == 0) red[k][wv] = s;
@@ -68,10 +68,6 @@ __device__ __forceinline__ void block_red(float (&v)[NV], const Red& r, int idx0
     red_put(r, idx0 + (int)threadIdx.x, slot, s);
   }
   __syncthreads();
-}
-// slot of block (blockIdx.x, blockIdx.y) of a (chunks, B * per) grid: one per (b, chunk)
-__device__ __forceinline__ uint32_t chunk_slot(int per) {
-  return (uint32_t)(blockIdx.y / per) * gridDim.x + blockIdx.x;
 }
 
 // grid: (blocks per plane, planes); the pixels of one plane per block row

@@ -17,13 +17,11 @@
 // on another: the result is deterministic and the kernel cannot stall behind a concurrent launch on
 // another stream (the library GEMMs it replaces are stream-K kernels whose workgroups wait on each
 // other's partial tiles).
-#include "grr_common.h"
+#include "grr_split.h"
 
 #include <cstdlib>
 
 namespace grr {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct WgArgs {
   const float* a;      // [B, M, P]
@@ -41,26 +39,11 @@ struct WgArgs {
 // output tile per wave: 32 TA x 32 TB (TA TB accumulators in AGPRs); wgrad_plan picks the tile.  (A
 // 64 x 96 tile at two waves per SIMD measured slower than 128 x 96 on a 512 x 96 output, 1.03 vs 0.86 ms,
 // it is taken only where 128 x 96 would be mostly padding.)
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-// exact split v = v0 + v1 + v2 of 8 values into bf16 terms (RNE casts: v_cvt_pk_bf16_f32)
-__device__ __forceinline__ void wg_split3x8(const float (&v)[8], bf16x8& t0, bf16x8& t1, bf16x8& t2) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const __bf16 h0 = (__bf16)v[j];
-    const float r1 = v[j] - (float)h0;
-    const __bf16 h1 = (__bf16)r1;
-    const float r2 = r1 - (float)h1;
-    t0[j] = h0;
-    t1[j] = h1;
-    t2[j] = (__bf16)r2;
-  }
-}
-
+//
 // 16 pixels per step on v_mfma_f32_32x32x16_bf16: lane l holds k = 8 (l >> 5) + j, i.e. half-wave h
 // takes pixels p0 + 8 h + j (one 32-B run per row and lane; the two halves cover 64 B of each row).
 // Both operands are split exactly into three bf16 terms and the six products above 2^-24 |a b| are
-// accumulated in fp32, smallest first (the x3 GEMM of feature_ops.hip / lnb_ops.hip: fp32-accurate,
+// accumulated in fp32, smallest first (split3x8 / GRR_X3_MFMA of grr_split.h: fp32-accurate,
 // 2.7x the v_mfma_f32_32x32x2_f32 rate).  Row loads run two steps ahead.
 template <int TA, int TB, bool VEC, int WPS>
 __global__ __launch_bounds__(64, WPS) void wgrad_x3_kernel(WgArgs a) {
@@ -129,21 +112,17 @@ __global__ __launch_bounds__(64, WPS) void wgrad_x3_kernel(WgArgs a) {
   bf16x8 fa[TA][3], fb[TB][3];
   auto split = [&](const float (&xa)[TA][8], const float (&xb)[TB][8]) {
 #pragma unroll
-    for (int t = 0; t < TA; ++t) wg_split3x8(xa[t], fa[t][0], fa[t][1], fa[t][2]);
+    for (int t = 0; t < TA; ++t) split3x8(xa[t], fa[t][0], fa[t][1], fa[t][2]);
 #pragma unroll
-    for (int t = 0; t < TB; ++t) wg_split3x8(xb[t], fb[t][0], fb[t][1], fb[t][2]);
+    for (int t = 0; t < TB; ++t) split3x8(xb[t], fb[t][0], fb[t][1], fb[t][2]);
   };
   auto mma = [&]() {
 #pragma unroll
     for (int i = 0; i < TA; ++i)
 #pragma unroll
       for (int j = 0; j < TB; ++j) {
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][1], fb[j][1], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][2], fb[j][0], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[j][2], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][1], fb[j][0], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[j][1], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[j][0], acc[i][j], 0, 0, 0);
+        GRR_X3_MFMA(__builtin_amdgcn_mfma_f32_32x32x16_bf16, acc[i][j], fa[i][0], fa[i][1], fa[i][2], fb[j][0],
+                    fb[j][1], fb[j][2]);
       }
   };
 

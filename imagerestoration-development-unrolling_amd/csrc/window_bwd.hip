@@ -18,7 +18,7 @@
 // Every kernel here is a per-pixel kernel (grid-stride over the elements, reductions by wave
 // sums and one fixed-order partial per block); the K-edge windows (K = 8, 12, 24, reach <= 2) make the
 // per-pixel working set large, and this path trains the older window models, not the metric's.
-#include "grr_common.h"
+#include "grr_device.h"
 
 namespace grr {
 namespace {
@@ -31,11 +31,6 @@ struct WinDeltaB {
   int8_t dx[kWinMaxEdges];
 };
 
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 // Block-wide sums of N per-thread values, one partial per value and block (grr_common.h, fixed-order
 // reductions): value i goes to row idx[i] of r[i], slot `slot`.  Every thread of the block must call
 // it (the grid-stride loops end before it).
@@ -45,7 +40,7 @@ __device__ __forceinline__ void block_red(float (&v)[N], const Red (&r)[N], cons
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #pragma unroll
   for (int i = 0; i < N; ++i) {
-    const float s = wsum(v[i]);
+    const float s = wave_sum(v[i]);
     if (lane == 0) red[wave][i] = s;
   }
   __syncthreads();
@@ -60,10 +55,6 @@ __device__ __forceinline__ void block_red(float (&v)[N], const Red (&r)[N], cons
       if (i == (int)threadIdx.x) { rr = r[i]; ii = idx[i]; }
     red_put(rr, ii, slot, t);
   }
-}
-// slot of block (blockIdx.x, blockIdx.y) of a (chunks, B * per) grid: one per (b, chunk)
-__device__ __forceinline__ uint32_t chunk_slot(int per) {
-  return (uint32_t)(blockIdx.y / per) * gridDim.x + blockIdx.x;
 }
 __device__ __forceinline__ int refl(int v, int n) {   // one-pixel reflect frame
   v = v < 0 ? -v : v;

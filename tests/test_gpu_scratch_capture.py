@@ -1,4 +1,4 @@
-"""The reverse's reduction scratch under HIP-graph capture (graph_bwd.hip scratch_lease).
+"""The reverse's reduction scratch under HIP-graph capture (runtime.hip scratch_lease).
 
 A reduction captured into a graph takes its own scratch (hipMallocAsync / hipFreeAsync memory nodes
 of the graph), not the capturing stream's grow-only buffer: a replay running next to eager calls on
