@@ -10,7 +10,18 @@ synthetic PNGs written to a temporary folder, and then the device loader alone o
 set's (8600 small pictures), where a host cost per batch that grew with the number of files would show.  Prints
 one JSON line per shape and one for the many-files run.
 
-    python bench_data.py [--steps 60] [--warmup 10] [--images 12] [--side 1200] [--workers 4] [--files 8600]
+With --paired both paths read training.PairedImageRestoration (dist_mode "none") over degraded / clean file pairs:
+the host path decodes two files per sample, the device loader holds two arenas and makes each batch with one
+kernels.patch_pair_batch call.  The same JSON line per shape ("bench": "data_paired", arena_mb counting both
+arenas); the many-files run is the unpaired loader's and is left out.
+
+With --pair-kernel only the two kernels are timed, in one process on one shape (B = 64, C = 3, 128^2, all eight
+modes, random origins in 8 pictures of 512^2): grr_patch_pair_batch without sigma against grr_patch_batch at
+sigma 25/255, device events around runs of 200 launches on preallocated outputs, the two alternating, 15 rounds.
+One JSON line ("bench": "pair_kernel") with each kernel's median, fastest and slowest round in microseconds per
+launch.
+
+    python bench_data.py [--paired | --pair-kernel] [--steps 60] [--warmup 10] [--images 12] [--side 1200] [--workers 4] [--files 8600]
 """
 from __future__ import annotations
 
@@ -27,19 +38,23 @@ import torch
 SHAPES = ((4, 128), (3, 192), (2, 256), (1, 384), (32, 512))
 
 
-def write_pictures(folder: str, n: int, side: int, seed: int = 7) -> str:
+def write_pictures(folder: str, n: int, side: int, seed: int = 7, paired: bool = False) -> str:
     """n RGB PNGs (side x side, and every third one smaller than a crop's 800-pixel threshold) and their csv:
-    smooth ramps plus noise, so the files neither compress away nor decode faster than photographs do."""
+    smooth ramps plus noise, so the files neither compress away nor decode faster than photographs do.  paired:
+    each picture is a degraded file, its target_path a second file of the same kind and size."""
     from PIL import Image
     rs = np.random.RandomState(seed)
-    lines = ["index,path,height,width,nchannels"]
+    lines = ["index,path,target_path,height,width,nchannels" if paired else "index,path,height,width,nchannels"]
     for k in range(n):
         h, w = (side, side + 64) if k % 3 else (640, 720)
         yy, xx = np.mgrid[0:h, 0:w]
         base = np.stack([(yy * (k + 1) + xx * 2) % 256, (yy + xx * (k + 2)) % 256, (yy * 3 + xx) % 256], axis=2)
         img = np.clip(base * 0.6 + rs.randint(0, 103, size=(h, w, 3)), 0, 255).astype(np.uint8)
         Image.fromarray(img).save(os.path.join(folder, f"img{k:03d}.png"))
-        lines.append(f"{k},img{k:03d}.png,{h},{w},3")
+        if paired:
+            clean = np.clip(base * 0.6 + rs.randint(0, 103, size=(h, w, 3)), 0, 255).astype(np.uint8)
+            Image.fromarray(clean).save(os.path.join(folder, f"clean{k:03d}.png"))
+        lines.append(f"{k},img{k:03d}.png,clean{k:03d}.png,{h},{w},3" if paired else f"{k},img{k:03d}.png,{h},{w},3")
     csv_path = os.path.join(folder, "info.csv")
     with open(csv_path, "w") as f:
         f.write("\n".join(lines) + "\n")
@@ -80,6 +95,52 @@ def timed(batches, warmup: int, steps: int, to_device) -> float:
     return dt
 
 
+def pair_kernel(rounds: int = 15, launches: int = 200) -> None:
+    import irdu_amd
+    irdu_amd.load_native()
+    from irdu_amd import _native, kernels, restore
+    dev = torch.device("cuda:0")
+    n, c, size, side = 64, 3, 128, 512
+    rs = np.random.RandomState(3)
+    packs = [restore.pack_images([rs.randint(0, 256, (side, side, c)).astype(np.uint8) for _ in range(8)], dev)
+             for _ in range(2)]
+    src = kernels.patch_pair_source(*packs)
+    rows = np.stack([np.arange(n) % 8, rs.randint(0, side - size, n), rs.randint(0, side - size, n), np.arange(n) % 8], 1)
+    table = torch.from_numpy(rows.astype(np.int32)).to(dev)
+    ids = torch.arange(n, dtype=torch.int64, device=dev)
+    sigma = torch.full((n,), 25.0 / 255.0, dtype=torch.float32, device=dev)
+    out = [torch.empty((n, c, size, size), dtype=torch.float32, device=dev) for _ in range(2)]
+    stream = torch.cuda.current_stream().cuda_stream
+    arena, target = packs[0].arena, packs[1].arena
+    common = (c, packs[0].table.data_ptr(), 8, table.data_ptr(), ids.data_ptr())
+    tail = (n, 2204, size, size, out[0].data_ptr(), out[1].data_ptr(), stream)
+    calls = {"patch_pair_batch": lambda: _native.call("grr_patch_pair_batch", arena.data_ptr(), target.data_ptr(),
+                                                      arena.numel(), *common, None, *tail),
+             "patch_batch": lambda: _native.call("grr_patch_batch", target.data_ptr(), target.numel(), *common,
+                                                 sigma.data_ptr(), *tail)}
+    # the two entry points on these tables: the pair's target is patch_batch's clean batch
+    t, _ = kernels.patch_pair_batch(src, table, ids, None, 2204, size, size)
+    cl, _ = kernels.patch_batch(packs[1], table, ids, sigma, 2204, size, size)
+    assert torch.equal(t, cl)
+    us = {k: [] for k in calls}
+    for r in range(rounds + 1):                      # round 0 warms both up
+        for name, call in calls.items():
+            start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            for _ in range(launches):
+                call()
+            end.record()
+            torch.cuda.synchronize()
+            if r:
+                us[name].append(start.elapsed_time(end) * 1e3 / launches)
+    line = {"bench": "pair_kernel", "batch": n, "channels": c, "size": size, "rounds": rounds, "launches": launches}
+    for name, v in us.items():
+        nbytes = n * c * size * size * (10 if name == "patch_pair_batch" else 9)
+        line[name] = {"median_us": round(float(np.median(v)), 2), "min_us": round(min(v), 2), "max_us": round(max(v), 2),
+                      "median_gbps": round(nbytes / float(np.median(v)) / 1e3, 1)}
+    print(json.dumps(line), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     # the DataLoader's workers hold up to 2 batches each in flight when the clock starts: enough timed batches
@@ -93,7 +154,13 @@ def main():
     ap.add_argument("--files", type=int, default=8600,
                     help="files of the many-files measurement of the device loader (0: skip it)")
     ap.add_argument("--small-side", type=int, default=160, help="side of its pictures")
+    ap.add_argument("--paired", action="store_true",
+                    help="degraded / clean file pairs: PairedImageRestoration on both paths (no many-files run)")
+    ap.add_argument("--pair-kernel", action="store_true",
+                    help="only time grr_patch_pair_batch (no sigma) against grr_patch_batch (sigma > 0) on one shape")
     args = ap.parse_args()
+    if args.pair_kernel:
+        return pair_kernel()
     import irdu_amd
     irdu_amd.load_native()
     from irdu_amd import kernels, training
@@ -105,12 +172,16 @@ def main():
 
     shared: dict = {}        # the shapes read one set of files: one arena
     with tempfile.TemporaryDirectory() as folder:
-        csv_path = write_pictures(folder, args.images, args.side)
+        csv_path = write_pictures(folder, args.images, args.side, paired=args.paired)
         for batch, size in SHAPES:
             n = (args.steps + args.warmup + 1) * batch
-            ds = training.ImageSuperResolution(csv_path=csv_path, root_folder=folder, dist_mode="addictive_noise_scale",
-                                               lambda_noise=25.0, use_data_aug=True, patch_size=(size, size),
-                                               max_num_patchs=n, logger=log)
+            if args.paired:
+                ds = training.PairedImageRestoration(csv_path=csv_path, root_folder=folder, use_data_aug=True,
+                                                     patch_size=(size, size), max_num_patchs=n, logger=log)
+            else:
+                ds = training.ImageSuperResolution(csv_path=csv_path, root_folder=folder, dist_mode="addictive_noise_scale",
+                                                   lambda_noise=25.0, use_data_aug=True, patch_size=(size, size),
+                                                   max_num_patchs=n, logger=log)
             host = torch.utils.data.DataLoader(ds, sampler=training.ResumeableSampler(ds, batch), batch_size=batch,
                                                num_workers=args.workers)
             host_s = timed(host, args.warmup, args.steps, planar)
@@ -134,9 +205,10 @@ def main():
                                                 shared=shared):
                 pass
             kernels.set_timer(None)
-            kern = timer.summary()["patch_batch"]
-            print(json.dumps({"bench": "data", "batch": batch, "size": size, "steps": args.steps, "device_steps": args.device_steps,
-                              "workers": args.workers, "images": args.images, "arena_mb": pack.arena.numel() / 2 ** 20,
+            kern = timer.summary()["patch_pair_batch" if args.paired else "patch_batch"]
+            arena_elems = sum(p.arena.numel() for p in pack) if args.paired else pack.arena.numel()
+            print(json.dumps({"bench": "data_paired" if args.paired else "data", "batch": batch, "size": size, "steps": args.steps, "device_steps": args.device_steps,
+                              "workers": args.workers, "images": args.images, "arena_mb": arena_elems / 2 ** 20,
                               "pack_s": round(pack_s, 4), "host_ms_per_batch": round(host_s * 1e3, 3),
                               "host_batches_per_s": round(1.0 / host_s, 2), "device_ms_per_batch": round(dev_s * 1e3, 4),
                               "device_batches_per_s": round(1.0 / dev_s, 1),
@@ -145,7 +217,7 @@ def main():
 
     # The device loader's host cost per batch must not grow with the number of files: a training set's file count
     # (DFWB: 8600) of small pictures, the first curriculum shape.
-    if args.files > 0:
+    if args.files > 0 and not args.paired:
         with tempfile.TemporaryDirectory() as folder:
             csv_path = write_small_pictures(folder, args.files, args.small_side)
             batch, size = SHAPES[0]

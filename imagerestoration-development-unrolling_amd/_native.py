@@ -182,6 +182,9 @@ SIGNATURES = {
     # training batches from an image arena (training.DevicePatchLoader)
     "grr_patch_batch_supported": [I, I, L, I, I, I],
     "grr_patch_batch": [P, L, I, P, I, P, P, P, I, ctypes.c_uint64, I, I, P, P, P],
+    # ... from a degraded and a clean arena under one image table (training.PairedImageRestoration)
+    "grr_patch_pair_batch_supported": [I, I, L, I, I, I],
+    "grr_patch_pair_batch": [P, P, L, I, P, I, P, P, P, I, ctypes.c_uint64, I, I, P, P, P],
 }
 _RESTYPES = {"grr_version": c_int, "grr_last_error": ctypes.c_char_p, "grr_lnb_workspace_bytes": c_int64,
              "grr_conv1x1_workspace_bytes": c_int64, "grr_wgrad_workspace_bytes": c_int64,

@@ -20,6 +20,8 @@
 // from the arena by a device table of (image, row, col, mode), the noise a counter-based function of
 // (seed, sample id, element):
 //   grr_patch_batch
+// and the same batch for degraded / clean picture pairs, two arenas under one image table (one kernel body):
+//   grr_patch_pair_batch
 //
 // Both families are instances of one gather body, one scatter body and one SSE kernel.  gather_kernel and
 // scatter_kernel are written against an image source (OneImage or Arena below), which says where a window's
@@ -494,19 +496,22 @@ __global__ __launch_bounds__(kIoThreads) void u8_sse_kernel(const uint8_t* __res
 // ---------------------------------------------------------------------------
 // Training batches (grr_patch_batch): sample s is the ph x pw patch of image table[s][0] at (row, col), the
 // bottom / right filled by the edge-repeating mirror (np.pad "symmetric", OpenCV's BORDER_REFLECT), moved by
-// T_mode, plus Gaussian noise that is a function of (seed, sample id, element) alone.
+// T_mode, plus Gaussian noise that is a function of (seed, sample id, element) alone.  grr_patch_pair_batch
+// cuts the same patch from two arenas that share the image table -- the ground truth and its degraded version --
+// and adds the noise, if any, to the degraded one.
 constexpr int kPatchTile = 32;   // a block's tile of the output patch: 32 rows of 32 floats
 
 struct PatchArgs {
-  float* clean;           // [n, C, ph, pw]
-  float* noisy;
+  float* clean;           // [n, C, ph, pw]; the pair's target
+  float* noisy;           // the pair's input
   const int32_t* table;   // [n, 4] (img, row, col, mode)
   const int64_t* ids;     // [n]
-  const float* sigma;     // [n]
+  const float* sigma;     // [n]; Pair only: may be null (no noise)
   uint64_t seed;
   int n, ph, pw;
   int tiles_y, tiles_x;   // tiles of kPatchTile x kPatchTile per output patch
   int vec;                // pw % 4 == 0 and both outputs 16-byte aligned
+  const uint8_t* pair;    // Pair only: the input (degraded) arena, element for element the layout of src
 };
 
 // index r >= 0 of the mirror ...cba|abc...|cba... of n >= 1 samples: t = r mod 2n; t < n ? t : 2n - 1 - t
@@ -570,10 +575,14 @@ __device__ __forceinline__ double normal_at(uint32_t e, const NoiseKey& k) {
 // of a row for all C channels; their 4 C noise elements (HWC order) are C whole Philox blocks when they start
 // on one (pw C % 4 == 0, every training shape), else one block per element.  Plain and 16-byte vector stores
 // only.  Table entries are clamped, element reads go through Arena::clamped.
-template <int C>
+// Pair: pass 1 reads the same clamped element of a.pair as well into a second tile (2 C 32 33 floats of LDS in
+// all), pass 2 writes the first tile to a.clean and the second, plus the noise, to a.noisy; a block whose sigma
+// is absent or 0 skips the noise (adding (float)(0 z) = +-0 to a value >= +0 leaves its bits).
+template <int C, bool Pair>
 __global__ __launch_bounds__(kIoThreads) void patch_batch_kernel(Arena src, PatchArgs a) {
   constexpr int LD = kPatchTile + 1;
-  __shared__ float tile[C * kPatchTile * LD];
+  constexpr int kTile = C * kPatchTile * LD;
+  __shared__ float tile[(Pair ? 2 : 1) * kTile];
   const uint32_t b = blockIdx.x;
   const int tx = (int)(b % (uint32_t)a.tiles_x);
   const uint32_t t = b / (uint32_t)a.tiles_x;
@@ -599,22 +608,34 @@ __global__ __launch_bounds__(kIoThreads) void patch_batch_kernel(Arena src, Patc
     const int64_t sr = sym_index(row0 + i, im.H), sc = sym_index(col0 + j, im.W);
     const int64_t base = src.elem(im, sr * im.W + sc, C);
 #pragma unroll
-    for (int c = 0; c < C; ++c) tile[(c * kPatchTile + pl) * LD + ql] = load_px(img + src.clamped(base + c));
+    for (int c = 0; c < C; ++c) {
+      const int64_t el = src.clamped(base + c);
+      tile[(c * kPatchTile + pl) * LD + ql] = load_px(img + el);
+      if (Pair) tile[kTile + (c * kPatchTile + pl) * LD + ql] = load_px(a.pair + el);
+    }
   }
   __syncthreads();
   const int pl = (int)threadIdx.x / (kPatchTile / 4), quad = (int)threadIdx.x % (kPatchTile / 4);
   const int p = y0 + pl, q = x0 + 4 * quad;
   if (p >= a.ph || q >= a.pw) return;
-  float v[C][4], w[C][4];
+  float v[C][4], u[C][4], w[C][4];      // u: what the noise is added to
 #pragma unroll
   for (int c = 0; c < C; ++c)
 #pragma unroll
-    for (int k = 0; k < 4; ++k) v[c][k] = tile[(c * kPatchTile + pl) * LD + 4 * quad + k];   // past pw: unused
-  const double sg = (double)a.sigma[s];
+    for (int k = 0; k < 4; ++k) {
+      v[c][k] = tile[(c * kPatchTile + pl) * LD + 4 * quad + k];   // past pw: unused
+      u[c][k] = Pair ? tile[kTile + (c * kPatchTile + pl) * LD + 4 * quad + k] : v[c][k];
+    }
+  const double sg = Pair && !a.sigma ? 0.0 : (double)a.sigma[s];
   const uint64_t id = (uint64_t)a.ids[s];
   const NoiseKey key{(uint32_t)id, (uint32_t)(id >> 32), (uint32_t)a.seed, (uint32_t)(a.seed >> 32)};
   const uint32_t e0 = (uint32_t)(((int64_t)p * a.pw + q) * C);      // < ph pw C < 2^31
-  if ((e0 & 3u) == 0) {
+  if (Pair && sg == 0.0) {              // uniform over the block
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) w[c][k] = u[c][k];
+  } else if ((e0 & 3u) == 0) {
 #pragma unroll
     for (int blk = 0; blk < C; ++blk) {
       double z[4];
@@ -622,7 +643,7 @@ __global__ __launch_bounds__(kIoThreads) void patch_batch_kernel(Arena src, Patc
 #pragma unroll
       for (int l = 0; l < 4; ++l) {
         const int el = 4 * blk + l;           // element k C + c of the lane
-        w[el % C][el / C] = v[el % C][el / C] + (float)(sg * z[l]);
+        w[el % C][el / C] = u[el % C][el / C] + (float)(sg * z[l]);
       }
     }
   } else {
@@ -630,7 +651,7 @@ __global__ __launch_bounds__(kIoThreads) void patch_batch_kernel(Arena src, Patc
     for (int k = 0; k < 4; ++k)
 #pragma unroll
       for (int c = 0; c < C; ++c)
-        w[c][k] = q + k < a.pw ? v[c][k] + (float)(sg * normal_at(e0 + k * C + c, key)) : 0.0f;
+        w[c][k] = q + k < a.pw ? u[c][k] + (float)(sg * normal_at(e0 + k * C + c, key)) : 0.0f;
   }
   const int64_t plane = (int64_t)a.ph * a.pw;
   const int64_t at = (int64_t)s * C * plane + (int64_t)p * a.pw + q;
@@ -984,27 +1005,29 @@ int grr_patch_batch_supported(int C, int n_img, int64_t arena_elems, int n, int 
   return rows < (1ll << 31) && rows * pw <= ((1ll << 31) - 1) / C ? 1 : 0;    // n C ph pw < 2^31
 }
 
-grr_status grr_patch_batch(const uint8_t* arena, int64_t arena_elems, int C, const int64_t* img_table, int n_img,
-                           const int32_t* table, const int64_t* sample_ids, const float* sigma, int n, uint64_t seed,
-                           int ph, int pw, float* clean, float* noisy, void* stream) {
-  clear_error();
-  GRR_REQUIRE(arena && img_table && table && sample_ids && sigma && clean && noisy && arena_elems > 0 && n_img > 0 &&
-                  C > 0 && n > 0 && ph > 0 && pw > 0,
-              GRR_ERR_INVALID_ARG, "grr_patch_batch: bad args");
+// grr_patch_batch (input_arena null) and grr_patch_pair_batch after clear_error: the checks, then the launch.
+static grr_status patch_launch(const char* what, bool pair, const uint8_t* arena, const uint8_t* input_arena,
+                               int64_t arena_elems, int C, const int64_t* img_table, int n_img, const int32_t* table,
+                               const int64_t* sample_ids, const float* sigma, int n, uint64_t seed, int ph, int pw,
+                               float* clean, float* noisy, void* stream) {
+  GRR_REQUIRE(arena && (input_arena || !pair) && img_table && table && sample_ids && (sigma || pair) && clean && noisy &&
+                  arena_elems > 0 && n_img > 0 && C > 0 && n > 0 && ph > 0 && pw > 0,
+              GRR_ERR_INVALID_ARG, "%s: bad args", what);
   GRR_REQUIRE(grr_image_arena_supported(C, n_img, arena_elems), GRR_ERR_UNSUPPORTED,
-              "grr_patch_batch: needs C <= 4, n_img <= arena_elems < 2^62 (got C %d, %d images, %lld elements)", C,
-              n_img, (long long)arena_elems);
+              "%s: needs C <= 4, n_img <= arena_elems < 2^62 (got C %d, %d images, %lld elements)", what, C, n_img,
+              (long long)arena_elems);
   GRR_REQUIRE(grr_patch_batch_supported(C, n_img, arena_elems, n, ph, pw), GRR_ERR_UNSUPPORTED,
-              "grr_patch_batch: patch batch n C ph pw must be below 2^31 (got %d x %d x %d x %d)", n, C, ph, pw);
+              "%s: patch batch n C ph pw must be below 2^31 (got %d x %d x %d x %d)", what, n, C, ph, pw);
   GRR_REQUIRE((uintptr_t)clean % 4 == 0 && (uintptr_t)noisy % 4 == 0 && (uintptr_t)table % 4 == 0 &&
                   (uintptr_t)sigma % 4 == 0,
-              GRR_ERR_INVALID_ARG, "grr_patch_batch: float32 and int32 operands must be 4-byte aligned");
+              GRR_ERR_INVALID_ARG, "%s: float32 and int32 operands must be 4-byte aligned", what);
   GRR_REQUIRE((uintptr_t)img_table % 8 == 0 && (uintptr_t)sample_ids % 8 == 0, GRR_ERR_INVALID_ARG,
-              "grr_patch_batch: the image table and the sample ids must be 8-byte aligned");
+              "%s: the image table and the sample ids must be 8-byte aligned", what);
   const Arena src{const_cast<uint8_t*>(arena), arena_elems, img_table, n_img};
   PatchArgs a{};
   a.clean = clean;
   a.noisy = noisy;
+  a.pair = input_arena;
   a.table = table;
   a.ids = sample_ids;
   a.sigma = sigma;
@@ -1017,13 +1040,38 @@ grr_status grr_patch_batch(const uint8_t* arena, int64_t arena_elems, int C, con
   a.vec = pw % 4 == 0 && (uintptr_t)clean % 16 == 0 && (uintptr_t)noisy % 16 == 0;
   const dim3 grid((uint32_t)((int64_t)n * a.tiles_y * a.tiles_x));   // <= n ph pw < 2^31
   hipStream_t s = (hipStream_t)stream;
-  switch (C) {
-    case 1: hipLaunchKernelGGL(patch_batch_kernel<1>, grid, dim3(kIoThreads), 0, s, src, a); break;
-    case 2: hipLaunchKernelGGL(patch_batch_kernel<2>, grid, dim3(kIoThreads), 0, s, src, a); break;
-    case 3: hipLaunchKernelGGL(patch_batch_kernel<3>, grid, dim3(kIoThreads), 0, s, src, a); break;
-    default: hipLaunchKernelGGL(patch_batch_kernel<4>, grid, dim3(kIoThreads), 0, s, src, a); break;
+  switch ((pair ? 4 : 0) + C - 1) {
+    case 0: hipLaunchKernelGGL((patch_batch_kernel<1, false>), grid, dim3(kIoThreads), 0, s, src, a); break;
+    case 1: hipLaunchKernelGGL((patch_batch_kernel<2, false>), grid, dim3(kIoThreads), 0, s, src, a); break;
+    case 2: hipLaunchKernelGGL((patch_batch_kernel<3, false>), grid, dim3(kIoThreads), 0, s, src, a); break;
+    case 3: hipLaunchKernelGGL((patch_batch_kernel<4, false>), grid, dim3(kIoThreads), 0, s, src, a); break;
+    case 4: hipLaunchKernelGGL((patch_batch_kernel<1, true>), grid, dim3(kIoThreads), 0, s, src, a); break;
+    case 5: hipLaunchKernelGGL((patch_batch_kernel<2, true>), grid, dim3(kIoThreads), 0, s, src, a); break;
+    case 6: hipLaunchKernelGGL((patch_batch_kernel<3, true>), grid, dim3(kIoThreads), 0, s, src, a); break;
+    default: hipLaunchKernelGGL((patch_batch_kernel<4, true>), grid, dim3(kIoThreads), 0, s, src, a); break;
   }
-  return launch_status("grr_patch_batch");
+  return launch_status(what);
+}
+
+grr_status grr_patch_batch(const uint8_t* arena, int64_t arena_elems, int C, const int64_t* img_table, int n_img,
+                           const int32_t* table, const int64_t* sample_ids, const float* sigma, int n, uint64_t seed,
+                           int ph, int pw, float* clean, float* noisy, void* stream) {
+  clear_error();
+  return patch_launch("grr_patch_batch", false, arena, nullptr, arena_elems, C, img_table, n_img, table, sample_ids,
+                      sigma, n, seed, ph, pw, clean, noisy, stream);
+}
+
+int grr_patch_pair_batch_supported(int C, int n_img, int64_t arena_elems, int n, int ph, int pw) {
+  return grr_patch_batch_supported(C, n_img, arena_elems, n, ph, pw);     // two tiles of LDS fit at every C <= 4
+}
+
+grr_status grr_patch_pair_batch(const uint8_t* input_arena, const uint8_t* target_arena, int64_t arena_elems, int C,
+                                const int64_t* img_table, int n_img, const int32_t* table, const int64_t* sample_ids,
+                                const float* sigma, int n, uint64_t seed, int ph, int pw, float* target, float* input,
+                                void* stream) {
+  clear_error();
+  return patch_launch("grr_patch_pair_batch", true, target_arena, input_arena, arena_elems, C, img_table, n_img, table,
+                      sample_ids, sigma, n, seed, ph, pw, target, input, stream);
 }
 
 }  // extern "C"

@@ -2056,48 +2056,56 @@ def patch_batch(pack, rows, sample_ids, sigma, seed: int, ph: int, pw: int) -> T
     indices inside the pack, modes 0..7, the odd quarter turns only with ph == pw -- and uploaded.  Three device
     tensors (int32 [n, 4], int64 [n], float32 [n], contiguous, on the arena's device) are taken as they are: the
     kernel clamps what it reads from them."""
-    import numpy as np
     src = pack if isinstance(pack, PatchSource) else patch_source(pack)
-    pack, n_img, c = src.pack, src.n_img, src.c
-    arena = pack.arena
+    table, ids, sg = _patch_tables("patch_batch", src.pack.arena, src.n_img, src.c, src.hw, rows, sample_ids, sigma,
+                                   seed, ph, pw)
+    return _patch_batch(src.pack, src.n_img, src.c, table, ids, sg, seed, ph, pw)
+
+
+def _patch_tables(name: str, arena: Tensor, n_img: int, c: int, hw, rows, sample_ids, sigma, seed: int, ph: int,
+                  pw: int, no_sigma: bool = False) -> Tuple[Tensor, Tensor, Optional[Tensor]]:
+    """The host checks patch_batch and patch_pair_batch share, and the three device tables (int32 [n, 4],
+    int64 [n], float32 [n]); no_sigma: ``sigma`` may be None, and stays None."""
+    import numpy as np
     if not 0 <= int(seed) < (1 << 64):
-        raise ValueError(f"patch_batch: seed must fit 64 bits, got {seed}")
+        raise ValueError(f"{name}: seed must fit 64 bits, got {seed}")
+    absent = no_sigma and sigma is None
     if isinstance(rows, Tensor) and rows.is_cuda:
         n = rows.shape[0] if rows.dim() == 2 else 0
         for t, dtype, shape in ((rows, torch.int32, (n, 4)), (sample_ids, torch.int64, (n,)), (sigma, torch.float32, (n,))):
+            if absent and dtype == torch.float32:
+                continue
             if not isinstance(t, Tensor) or t.dtype != dtype or tuple(t.shape) != shape or t.device != arena.device \
                     or not t.is_contiguous():
-                raise ValueError("patch_batch: device tables are int32 [n, 4], int64 [n] and float32 [n], contiguous "
+                raise ValueError(f"{name}: device tables are int32 [n, 4], int64 [n] and float32 [n], contiguous "
                                  "and on the arena's device")
         if not isinstance(ph, int) or not isinstance(pw, int) or not patch_batch_ok(c, n_img, arena.numel(), n, ph, pw):
-            raise ValueError(f"patch_batch: patch batch {n} x {c} x {ph} x {pw} must have 1..2^31-1 elements")
-        return _patch_batch(pack, n_img, c, rows, sample_ids, sigma, seed, ph, pw)
+            raise ValueError(f"{name}: patch batch {n} x {c} x {ph} x {pw} must have 1..2^31-1 elements")
+        return rows, sample_ids, sigma
     rows = np.asarray(rows)
     if rows.ndim != 2 or rows.shape[1] != 4 or rows.shape[0] < 1 or rows.dtype.kind not in "iu":
-        raise ValueError("patch_batch: rows are integers [n, 4] (img, row, col, mode)")
+        raise ValueError(f"{name}: rows are integers [n, 4] (img, row, col, mode)")
     n = rows.shape[0]
     rows = rows.astype(np.int64)
     ids = np.asarray(sample_ids)
-    sg = np.asarray(sigma, dtype=np.float32)
+    sg = np.zeros(n, np.float32) if absent else np.asarray(sigma, dtype=np.float32)
     if ids.shape != (n,) or ids.dtype.kind not in "iu" or sg.shape != (n,):
-        raise ValueError(f"patch_batch: sample_ids (integers) and sigma must have one entry per row ({n})")
+        raise ValueError(f"{name}: sample_ids (integers) and sigma must have one entry per row ({n})")
     if not (np.isfinite(sg).all() and (sg >= 0).all()):
-        raise ValueError("patch_batch: sigma must be finite and non-negative")
+        raise ValueError(f"{name}: sigma must be finite and non-negative")
     if not isinstance(ph, int) or not isinstance(pw, int) or not patch_batch_ok(c, n_img, arena.numel(), n, ph, pw):
-        raise ValueError(f"patch_batch: patch batch {n} x {c} x {ph} x {pw} must have 1..2^31-1 elements")
+        raise ValueError(f"{name}: patch batch {n} x {c} x {ph} x {pw} must have 1..2^31-1 elements")
     if ((rows[:, 0] < 0) | (rows[:, 0] >= n_img)).any():
-        raise ValueError(f"patch_batch: image indices must lie in [0, {n_img})")
-    hw = src.hw[rows[:, 0]]
-    if ((rows[:, 1:3] < 0) | (rows[:, 1:3] >= hw)).any():
-        raise ValueError("patch_batch: (row, col) must lie inside the row's image")
+        raise ValueError(f"{name}: image indices must lie in [0, {n_img})")
+    if ((rows[:, 1:3] < 0) | (rows[:, 1:3] >= hw[rows[:, 0]])).any():
+        raise ValueError(f"{name}: (row, col) must lie inside the row's image")
     if ((rows[:, 3] < 0) | (rows[:, 3] > 7)).any():
-        raise ValueError("patch_batch: modes must lie in 0..7")
+        raise ValueError(f"{name}: modes must lie in 0..7")
     if ph != pw and (rows[:, 3] & 2).any():
-        raise ValueError(f"patch_batch: the odd quarter turns (modes 2, 3, 6, 7) need a square patch, got {ph} x {pw}")
+        raise ValueError(f"{name}: the odd quarter turns (modes 2, 3, 6, 7) need a square patch, got {ph} x {pw}")
     dev = arena.device
-    return _patch_batch(pack, n_img, c, torch.from_numpy(rows.astype(np.int32)).to(dev),
-                        torch.from_numpy(ids.astype(np.int64)).to(dev),
-                        torch.from_numpy(np.ascontiguousarray(sg)).to(dev), seed, ph, pw)
+    return (torch.from_numpy(rows.astype(np.int32)).to(dev), torch.from_numpy(ids.astype(np.int64)).to(dev),
+            None if absent else torch.from_numpy(np.ascontiguousarray(sg)).to(dev))
 
 
 def _patch_batch(pack, n_img: int, c: int, table: Tensor, ids: Tensor, sigma: Tensor, seed: int, ph: int,
@@ -2110,6 +2118,82 @@ def _patch_batch(pack, n_img: int, c: int, table: Tensor, ids: Tensor, sigma: Te
             pack.table.data_ptr(), n_img, table.data_ptr(), ids.data_ptr(), sigma.data_ptr(), n, int(seed), ph, pw,
             clean.data_ptr(), noisy.data_ptr(), _stream(arena.device))
     return clean, noisy
+
+
+# ... and from a degraded and a clean arena under one image table (training.PairedImageRestoration)
+def patch_pair_batch_ok(c: int, n_img: int, arena_elems: int, n: int, ph: int, pw: int) -> bool:
+    """grr_patch_pair_batch_supported in plain Python (tests/test_pair_abi.py checks the two agree): patch_batch_ok's
+    bounds; each of the two outputs has n C ph pw < 2^31 elements."""
+    return patch_batch_ok(c, n_img, arena_elems, n, ph, pw)
+
+
+class PatchPairSource:
+    """Two uint8 image packs that patch_pair_batch's checks have passed (patch_pair_source): ``input`` the
+    degraded pictures, ``target`` their ground truth, one host table and one C; the image count, the channels
+    and the images' (H, W) as an int64 array."""
+    __slots__ = ("input", "target", "n_img", "c", "hw")
+
+    def __init__(self, input_pack, target_pack, n_img: int, c: int, hw):
+        self.input, self.target, self.n_img, self.c, self.hw = input_pack, target_pack, n_img, c, hw
+
+
+def patch_pair_source(input_pack, target_pack) -> PatchPairSource:
+    """Check the two packs for patch_pair_batch -- each as patch_source checks its pack, then: one device, one C,
+    one host table (image i of ``input_pack`` is the degraded image i of ``target_pack``; a ValueError names the
+    first image that differs) -- and return their PatchPairSource.  The same pack twice is legal.  The packs'
+    tensors and host tables must not change afterwards."""
+    import numpy as np
+    name = "patch_pair_batch"
+    checked = []
+    for pack in (input_pack, target_pack):
+        n_img, c = _check_pack(name, pack)
+        if pack.arena.dtype != torch.uint8:
+            raise ValueError(f"{name}: the arenas must be uint8, got {pack.arena.dtype}")
+        checked.append((n_img, c, tuple(tuple(int(v) for v in row) for row in pack.host_table)))
+    (n_img, c, host_in), (n_tgt, c_tgt, host_tgt) = checked
+    if input_pack.arena.device != target_pack.arena.device:
+        raise ValueError(f"{name}: the two arenas must be on one device (got {input_pack.arena.device} and "
+                         f"{target_pack.arena.device})")
+    if c != c_tgt:
+        raise ValueError(f"{name}: image 0 has {c} channel(s) in the input pack and {c_tgt} in the target pack")
+    for i, (a, b) in enumerate(zip(host_in, host_tgt)):
+        if a != b:
+            raise ValueError(f"{name}: image {i} is (offset, H, W) = {a} in the input pack and {b} in the target "
+                             "pack: the packs must share one image table")
+    if n_img != n_tgt:
+        raise ValueError(f"{name}: image {min(n_img, n_tgt)} exists in one pack only ({n_img} input images, {n_tgt} "
+                         "target images)")
+    if input_pack.arena.numel() != target_pack.arena.numel():
+        raise ValueError(f"{name}: the arenas hold {input_pack.arena.numel()} and {target_pack.arena.numel()} "
+                         f"elements after image {n_img - 1}: one length")
+    hw = np.asarray(host_in, dtype=np.int64).reshape(n_img, 3)[:, 1:3].copy()
+    return PatchPairSource(input_pack, target_pack, n_img, c, hw)
+
+
+def patch_pair_batch(source: PatchPairSource, rows, sample_ids, sigma, seed: int, ph: int,
+                     pw: int) -> Tuple[Tensor, Tensor]:
+    """(target, input), float32 [n, C, ph, pw] each, of a patch_pair_source: target is patch_batch's clean patch
+    of the target pack, input the same patch (same origin, mirror fill and T_mode) of the input pack, plus
+    patch_batch's noise where ``sigma`` is given.  sigma None, or a zero entry, leaves the degraded pixels bit for
+    bit.  rows, sample_ids, sigma, seed: as patch_batch takes and checks them."""
+    if not isinstance(source, PatchPairSource):
+        raise ValueError("patch_pair_batch: source is what patch_pair_source returns")
+    table, ids, sg = _patch_tables("patch_pair_batch", source.target.arena, source.n_img, source.c, source.hw, rows,
+                                   sample_ids, sigma, seed, ph, pw, no_sigma=True)
+    return _patch_pair_batch(source, table, ids, sg, seed, ph, pw)
+
+
+def _patch_pair_batch(source: PatchPairSource, table: Tensor, ids: Tensor, sigma: Optional[Tensor], seed: int, ph: int,
+                      pw: int) -> Tuple[Tensor, Tensor]:
+    """patch_pair_batch after its checks, on device tables."""
+    arena, n = source.target.arena, table.shape[0]
+    target = torch.empty((n, source.c, ph, pw), dtype=torch.float32, device=arena.device)
+    inp = torch.empty_like(target)
+    _launch("patch_pair_batch", target.numel() * 10, "grr_patch_pair_batch", source.input.arena.data_ptr(),
+            arena.data_ptr(), arena.numel(), source.c, source.target.table.data_ptr(), source.n_img, table.data_ptr(),
+            ids.data_ptr(), None if sigma is None else sigma.data_ptr(), n, int(seed), ph, pw, target.data_ptr(),
+            inp.data_ptr(), _stream(arena.device))
+    return target, inp
 
 
 def u8_sse_segments(a: Tensor, b: Tensor, offsets) -> List[int]:

@@ -45,6 +45,8 @@ Metrics: ``psnr_u8`` from the exact integer SSE (``kernels.u8_sse``) and ``ssim_
 SSIM, from the exact integer sum of the per-pixel values quantised to 2^-32 (``kernels.u8_ssim``; float64 per
 pixel on the device).  ``evaluate`` returns the PSNRs, ``evaluate_metrics`` both, from one body; with
 ``across_images`` each metric of all images is one launch on the restored and the clean arena.
+``evaluate_pairs`` scores degraded / clean pairs of uint8 pictures with the same kernels and synthesises nothing:
+each input is restored as it is and compared with its target.
 
 Single process: several ranks are ``tiling.tiled_forward``'s business.
 """
@@ -461,11 +463,8 @@ def ssim_u8(a, b) -> float:
 METRICS = ("psnr", "ssim")
 
 
-def _evaluate(who: str, model: Callable, images, sigma: float, factor: int, seed: int, across_images: bool, ensemble,
-              metrics, tiling_args: dict) -> dict:
-    """The one body of evaluate and evaluate_metrics: {metric: (mean, per-image values)} for the metrics asked
-    for.  The draws, the restorations and the launches of one metric do not depend on which others are asked
-    for."""
+def _evaluate_args(who: str, model: Callable, ensemble, metrics, tiling_args: dict):
+    """(modes, metrics, device, tile, halo, micro_batch) of an evaluate call, checked; tiling_args is emptied."""
     modes = _ensemble_modes(who, ensemble)
     metrics = (metrics,) if isinstance(metrics, str) else tuple(metrics)
     if not metrics or any(m not in METRICS for m in metrics) or len(set(metrics)) != len(metrics):
@@ -475,6 +474,15 @@ def _evaluate(who: str, model: Callable, images, sigma: float, factor: int, seed
     micro_batch = tiling_args.pop("micro_batch", MICRO_BATCH)
     if tiling_args:
         raise TypeError(f"{who}: unexpected arguments {sorted(tiling_args)}")
+    return modes, metrics, device, tile, halo, micro_batch
+
+
+def _evaluate(who: str, model: Callable, images, sigma: float, factor: int, seed: int, across_images: bool, ensemble,
+              metrics, tiling_args: dict) -> dict:
+    """The one body of evaluate and evaluate_metrics: {metric: (mean, per-image values)} for the metrics asked
+    for.  The draws, the restorations and the launches of one metric do not depend on which others are asked
+    for."""
+    modes, metrics, device, tile, halo, micro_batch = _evaluate_args(who, model, ensemble, metrics, tiling_args)
     if "ssim" in metrics:       # before any draw
         for i in range(len(images)):
             shape = np.shape(images[i])
@@ -531,9 +539,14 @@ def _evaluate_across(model, images, sigma, factor, rs, tile, halo, micro_batch, 
     pack = pack_images([_noisy(clean, sigma, rs) for clean in cleans], device)     # all draws first, in image order
     restored = _restore_pack(model, pack, plan_images(pack.shapes(), factor, tile, halo, micro_batch, modes), True,
                              modes)
-    clean_u8 = pack_images([_clean_u8(c) for c in cleans], restored.arena.device)
+    return _score_packs("evaluate", restored, pack_images([_clean_u8(c) for c in cleans], restored.arena.device), metrics)
+
+
+def _score_packs(who: str, restored: ImagePack, clean_u8: ImagePack, metrics) -> dict:
+    """{metric: per-image values} of a restored uint8 pack against the pack of what it should be: one launch per
+    metric."""
     if clean_u8.host_table != restored.host_table:
-        raise ValueError(f"evaluate: the model returns {restored.c} channel(s) for {clean_u8.c}; no PSNR")
+        raise ValueError(f"{who}: the model returns {restored.c} channel(s) for {clean_u8.c}; no PSNR")
     values = {}
     if "psnr" in metrics:
         offsets = [off for off, _, _ in restored.host_table] + [restored.arena.numel()]
@@ -543,3 +556,57 @@ def _evaluate_across(model, images, sigma, factor, rs, tile, halo, micro_batch, 
         qs = kernels.u8_ssim_images(restored, clean_u8)
         values["ssim"] = [_ssim(q, kernels.ssim_count(restored.c, h, w)) for q, (_, h, w) in zip(qs, restored.host_table)]
     return values
+
+
+def evaluate_pairs(model: Callable, inputs, targets, factor: int = 16, across_images: bool = False, ensemble=1,
+                   metrics=("psnr",), **tiling_args) -> dict:
+    """Score ``model`` on degraded / clean picture pairs: inputs[i] and targets[i] are uint8 H x W x C images of
+    one shape (numpy arrays or tensors, host or device).  Nothing is synthesised: each input goes to the device as
+    uint8, is restored as ``restore_image(..., quantise=True)`` restores it, and the uint8 result is scored against
+    the target with the exact-integer kernels (psnr_u8, ssim_u8).  Returns {metric: (mean, per-image values)} for
+    the names in ``metrics``, as evaluate_metrics does.  tiling_args: tile, halo, micro_batch, device.
+
+    ``across_images``: the inputs are restored by restore_images' path in shared window batches and every metric of
+    all images is one launch on the restored and the target arena; the same floats for a batch-independent model.
+    ``ensemble`` as in restore_image, on either branch.  A length or shape mismatch, an image that is not uint8,
+    an unknown metric and, with "ssim", a side below 11 are ValueErrors before any launch."""
+    who = "evaluate_pairs"
+    modes, metrics, device, tile, halo, micro_batch = _evaluate_args(who, model, ensemble, metrics, tiling_args)
+    if len(inputs) != len(targets) or len(inputs) < 1:
+        raise ValueError(f"{who}: {len(inputs)} input(s) for {len(targets)} target(s); one target per input, at least one")
+    pairs = []
+    for i in range(len(inputs)):
+        pair = []
+        for what, image in (("input", inputs[i]), ("target", targets[i])):
+            try:
+                t, _ = _checked_image(image)
+            except ValueError as e:
+                raise ValueError(f"{who}: {what} {i}: {e}") from None
+            if t.dtype != torch.uint8:
+                raise ValueError(f"{who}: {what} {i} is {t.dtype}; pairs are uint8 pictures")
+            pair.append(t)
+        if pair[0].shape != pair[1].shape:
+            raise ValueError(f"{who}: input {i} is {tuple(pair[0].shape)} and its target {tuple(pair[1].shape)}: a "
+                             "pair has one shape")
+        if "ssim" in metrics and min(pair[0].shape[:2]) < kernels.SSIM_WINDOW:
+            raise ValueError(f"{who}: pair {i} is {tuple(pair[0].shape)}; SSIM needs both sides at least "
+                             f"{kernels.SSIM_WINDOW}")
+        plan(pair[0].shape[0], pair[0].shape[1], factor, tile, halo)        # raises what the restoration would
+        pairs.append(pair)
+    if device is None:
+        device = next((t.device for pair in pairs for t in pair if t.is_cuda), None)
+    if across_images:
+        pack = pack_images([p[0] for p in pairs], device)
+        restored = _restore_pack(model, pack, plan_images(pack.shapes(), factor, tile, halo, micro_batch, modes), True,
+                                 modes)
+        values = _score_packs(who, restored, pack_images([p[1] for p in pairs], restored.arena.device), metrics)
+    else:
+        values = {m: [] for m in metrics}
+        for img, target in pairs:
+            restored = _restore_device(model, img, device, factor, tile, halo, micro_batch, True, modes)
+            target = target.to(restored.device)
+            if "psnr" in metrics:
+                values["psnr"].append(psnr_u8(restored, target))
+            if "ssim" in metrics:
+                values["ssim"].append(ssim_u8(restored, target))
+    return {m: (float(np.mean(values[m])), values[m]) for m in metrics}

@@ -27,6 +27,10 @@ is kept for real data.  Samples are (noisy, clean) HWC float32 like the referenc
 lib/dataloader_v2.py:70-242); a stage with ``device_resident: true`` reads it through ``DevicePatchLoader``,
 which keeps the decoded pictures on the GPU and makes each planar batch there (csrc/image_ops.hip:
 grr_patch_batch).
+``PairedImageRestoration`` is the same patch plan over degraded / clean file pairs (real camera noise, JPEG
+artefacts, blur, rain): nothing is synthesised unless a noise mode asks for it.  Its device-resident stage holds
+two arenas under one image table (grr_patch_pair_batch), ``TestPairsCSV`` lists pairs for the periodic validation
+and ``validate_pairs`` scores them with restore.evaluate_pairs.
 """
 from __future__ import annotations
 
@@ -204,6 +208,7 @@ class ImageSuperResolution(Dataset):
     with use_data_aug is refused (the odd quarter turns change the shape; the reference's collation would fail)."""
 
     IMG_SIZE, OVERLAP, MAX_SIZE = 512, 96, 800
+    DIST_MODES = ("addictive_noise", "vary_addictive_noise", "addictive_noise_scale")
 
     def __init__(self, csv_path, dist_mode, lambda_noise, use_data_aug=False, patch_size=(64, 64),
                  max_num_patchs=100000, root_folder="", logger=None, device=None, seed=2204, n_channels=3):
@@ -214,7 +219,7 @@ class ImageSuperResolution(Dataset):
         if use_data_aug and self.patch_size[0] != self.patch_size[1]:
             raise ValueError(f"ImageSuperResolution: use_data_aug needs a square patch (the odd quarter turns change "
                              f"the shape), got {self.patch_size}")
-        if dist_mode not in ("addictive_noise", "vary_addictive_noise", "addictive_noise_scale"):
+        if dist_mode not in self.DIST_MODES:
             raise ValueError(f"unknown dist_mode {dist_mode!r}")
         self.img_infos = pd.read_csv(csv_path, index_col="index")
         self.max_num_patchs = max_num_patchs
@@ -282,8 +287,10 @@ class ImageSuperResolution(Dataset):
 
     def load_image(self, img: int) -> np.ndarray:
         """File ``img`` of ``paths`` as uint8 H x W x n_channels."""
+        return self._load(self.paths[img])
+
+    def _load(self, path: str) -> np.ndarray:
         from PIL import Image
-        path = self.paths[img]
         a = np.array(Image.open(path))
         if a.ndim == 2 and self.n_channels == 1:
             a = a[:, :, None]
@@ -296,19 +303,77 @@ class ImageSuperResolution(Dataset):
         """The sample's sides: the patch cut to multiples of 16 (:208-212)."""
         return (self.patch_size[0] // 16) * 16, (self.patch_size[1] // 16) * 16
 
-    def __getitem__(self, idx):
-        row, col, need_padding, img_i = self.patchs_data[idx]
+    def _cut(self, image: np.ndarray, row: int, col: int, need_padding: bool) -> np.ndarray:
+        """The sample's uint8 patch of a decoded picture (:199-212), before the augmentation."""
         ph, pw = self.patch_size
-        patch = self.load_image(img_i)[row:row + ph, col:col + pw, :]
+        patch = image[row:row + ph, col:col + pw, :]
         if need_padding:
             patch = np.pad(patch, ((0, ph - patch.shape[0]), (0, pw - patch.shape[1]), (0, 0)), mode="symmetric")
         h_, w_ = (patch.shape[0] // 16) * 16, (patch.shape[1] // 16) * 16
-        patch = patch[0:h_, 0:w_]
+        return patch[0:h_, 0:w_]
+
+    def __getitem__(self, idx):
+        row, col, need_padding, img_i = self.patchs_data[idx]
+        patch = self._cut(self.load_image(img_i), row, col, need_padding)
         if self.use_data_augmentation:
             patch = data_augmentation(patch, self.random_state.randint(0, 7))
         patch = patch.astype(np.float32) / 255.0
         dist = _noisy(patch, self.random_state, self.dist_mode, self.lambda_noise)
         return torch.from_numpy(dist), torch.from_numpy(patch)
+
+
+class PairedImageRestoration(ImageSuperResolution):
+    """Degraded / clean file pairs under ImageSuperResolution's crop and patch plan (csv columns index, path,
+    target_path, height, width, nchannels; ``path`` is the degraded file, ``target_path`` its ground truth of the
+    same size, dtype and channels).  The plan is the parent's, unchanged -- 512 crops every 416 pixels, one random
+    patch per crop per pass, the permutation -- so equal seeds and sizes select the same (image, row, col) rows.
+    ``dist_mode``: "none" (default) leaves the degraded picture as it is; the parent's three additive modes add
+    their noise on top of it.  ``__getitem__`` makes the parent's draws in the parent's order (the mode when
+    augmenting, then the noise unless "none") and returns (input, target) float32 HWC, both cut and turned alike."""
+
+    DIST_MODES = ("none",) + ImageSuperResolution.DIST_MODES
+
+    def __init__(self, csv_path, dist_mode="none", lambda_noise=None, use_data_aug=False, patch_size=(64, 64),
+                 max_num_patchs=100000, root_folder="", logger=None, device=None, seed=2204, n_channels=3):
+        super().__init__(csv_path, dist_mode, lambda_noise, use_data_aug=use_data_aug, patch_size=patch_size,
+                         max_num_patchs=max_num_patchs, root_folder=root_folder, logger=logger, device=device,
+                         seed=seed, n_channels=n_channels)
+
+    def create_all_images(self):
+        if "target_path" not in self.img_infos.columns:
+            raise ValueError("PairedImageRestoration: the csv needs a target_path column (index, path, target_path, "
+                             f"height, width, nchannels), got {list(self.img_infos.columns)}")
+        super().create_all_images()
+        self.target_paths = [os.path.join(self.root_folder, p) for p in self.img_infos["target_path"].tolist()]
+
+    def load_target(self, img: int, like: Optional[np.ndarray] = None) -> np.ndarray:
+        """The ground truth of file ``img`` as uint8 H x W x n_channels; it must have the dtype, shape and channels
+        of its input (``like``: that input where the caller has decoded it already, else it is decoded here)."""
+        from PIL import Image
+        path = self.target_paths[img]
+        a = np.array(Image.open(path))
+        if a.ndim == 2 and self.n_channels == 1:
+            a = a[:, :, None]
+        if like is None:
+            like = self.load_image(img)
+        if a.dtype != like.dtype or a.shape != like.shape:
+            raise ValueError(f"PairedImageRestoration: target {path} is {a.dtype} {a.shape}, its input "
+                             f"{self.paths[img]} is {like.dtype} {like.shape}: a pair has one dtype, size and channel "
+                             "count")
+        return a
+
+    def __getitem__(self, idx):
+        row, col, need_padding, img_i = self.patchs_data[idx]
+        degraded = self.load_image(img_i)
+        inp = self._cut(degraded, row, col, need_padding)
+        tgt = self._cut(self.load_target(img_i, degraded), row, col, need_padding)
+        if self.use_data_augmentation:
+            mode = self.random_state.randint(0, 7)
+            inp, tgt = data_augmentation(inp, mode), data_augmentation(tgt, mode)
+        inp, tgt = inp.astype(np.float32) / 255.0, tgt.astype(np.float32) / 255.0
+        if self.dist_mode != "none":
+            inp = _noisy(inp, self.random_state, self.dist_mode, self.lambda_noise)
+        return torch.from_numpy(inp), torch.from_numpy(tgt)
 
 
 class DevicePatchLoader:
@@ -325,7 +390,13 @@ class DevicePatchLoader:
     two modes use lambda_noise (on the device they are one distribution).  Position p of the epoch's selection has
     sample id (e << 32) | p and the kernel's noise is a function of (dataset.seed, sample id, element), so a sample
     is a function of (dataset seed, epoch, position) alone: batch size, rank count and the resume point cannot
-    change it."""
+    change it.
+
+    A PairedImageRestoration dataset yields (input, target): the degraded and the clean files are decoded in one
+    pass into two arenas under one image table and a batch is one kernels.patch_pair_batch call.  The draws are the
+    same ones -- dist_mode "none" draws no level and its sigma is zero, so the kernel computes no noise -- and a
+    sample stays a function of (dataset seed, epoch, position).  The device holds both arenas: twice the bytes of
+    the unpaired loader over the same pictures."""
     channels_first = True
     CHUNK_BYTES = 256 << 20      # decoded pictures staged on the host per transfer
 
@@ -340,7 +411,8 @@ class DevicePatchLoader:
         self.dataset, self.sampler, self.batch_size, self.drop_last = dataset, sampler, int(batch_size), bool(drop_last)
         self.device = device
         self.shared = shared
-        self.source = None           # kernels.PatchSource: the arena, checked once
+        self.paired = isinstance(dataset, PairedImageRestoration)
+        self.source = None           # kernels.PatchSource (PatchPairSource if paired): the arena(s), checked once
         self._draws = (None, None, None)
 
     def __len__(self):
@@ -350,36 +422,40 @@ class DevicePatchLoader:
     def _pack(self, used: Sequence[int], dev):
         """The files ``used`` of the dataset in one uint8 arena on ``dev``, sized from the csv's heights and
         widths: decoded one by one and sent in chunks of about CHUNK_BYTES, so the host never holds more than two
-        chunks of decoded pictures."""
+        chunks of decoded pictures.  Returns the packs: one, or for a paired dataset (input, target), every file
+        decoded once and both arenas under one image table."""
         from . import restore
         ds, c = self.dataset, self.dataset.n_channels
         shapes = [(int(ds.img_infos.iloc[i]["height"]), int(ds.img_infos.iloc[i]["width"])) for i in used]
         host_table, total = restore._host_table(shapes, c)
-        arena = torch.empty(total, dtype=torch.uint8, device=dev)
-        held, held_bytes, at = [], 0, 0
+        arenas = [torch.empty(total, dtype=torch.uint8, device=dev) for _ in range(2 if self.paired else 1)]
+        held, held_bytes, at = [[] for _ in arenas], 0, 0
 
         def flush():
             nonlocal held, held_bytes, at
-            if held:
-                arena[at:at + held_bytes].copy_(torch.cat(held))
+            if held_bytes:
+                for arena, parts in zip(arenas, held):
+                    arena[at:at + held_bytes].copy_(torch.cat(parts))
                 at += held_bytes
-                held, held_bytes = [], 0
+                held, held_bytes = [[] for _ in arenas], 0
         for i, shape in zip(used, shapes):
             a = ds.load_image(i)
             if a.shape[:2] != shape:
                 raise ValueError(f"ImageSuperResolution: {ds.paths[i]} is {a.shape[0]} x {a.shape[1]}, the csv says "
                                  f"{shape[0]} x {shape[1]}")
-            held.append(torch.from_numpy(np.ascontiguousarray(a)).reshape(-1))
+            for parts, picture in zip(held, (a, ds.load_target(i, a)) if self.paired else (a,)):
+                parts.append(torch.from_numpy(np.ascontiguousarray(picture)).reshape(-1))
             held_bytes += a.size
             if held_bytes >= self.CHUNK_BYTES:
                 flush()
         flush()
         table = torch.tensor(host_table, dtype=torch.int64).to(dev)
-        return restore.ImagePack(arena, table, host_table, c, ("numpy",) * len(used))
+        return tuple(restore.ImagePack(arena, table, host_table, c, ("numpy",) * len(used)) for arena in arenas)
 
     def prepare(self):
         """Decode and pack the pictures now (otherwise the first batch does) and check the pack once; returns the
-        restore.ImagePack.  Serial PIL decodes: for a training set of thousands of files this takes minutes."""
+        restore.ImagePack, or for a paired dataset the (input, target) packs.  Serial PIL decodes: for a training
+        set of thousands of files this takes minutes."""
         if self.source is None:
             from . import kernels
             dev = self.device if self.device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -389,11 +465,14 @@ class DevicePatchLoader:
             slot[used] = np.arange(len(used))
             self._slot = slot
             key = (tuple(ds.paths[i] for i in used), ds.n_channels, str(dev))
+            if self.paired:      # both arenas under one key: a curriculum decodes each file once
+                key += (tuple(ds.target_paths[i] for i in used),)
             store = self.shared if self.shared is not None else {}
             if key not in store:
-                store[key] = kernels.patch_source(self._pack(used, dev))
+                packs = self._pack(used, dev)
+                store[key] = kernels.patch_pair_source(*packs) if self.paired else kernels.patch_source(*packs)
             self.source = store[key]
-        return self.source.pack
+        return (self.source.input, self.source.target) if self.paired else self.source.pack
 
     def epoch_draws(self, epoch: int) -> Tuple[np.ndarray, np.ndarray]:
         """(modes int64 [n], sigma float32 [n]) of the epoch, in dataset order."""
@@ -404,6 +483,8 @@ class DevicePatchLoader:
             modes = rs.randint(0, 8, n) if ds.use_data_augmentation else np.zeros(n, np.int64)
             if ds.dist_mode == "vary_addictive_noise":
                 levels = rs.choice(ds.lambda_noise[0], p=ds.lambda_noise[1], size=n)
+            elif ds.dist_mode == "none":
+                levels = np.zeros(n)
             else:
                 levels = np.full(n, ds.lambda_noise)
             sigma = (np.asarray(levels, dtype=np.float64) / 255.0).astype(np.float32)
@@ -411,7 +492,8 @@ class DevicePatchLoader:
         return self._draws[1], self._draws[2]
 
     def batch(self, positions: Sequence[int]):
-        """(noisy, clean) of the samples at these positions of the current epoch's selection."""
+        """(noisy, clean) -- (input, target) of a paired dataset -- of the samples at these positions of the current
+        epoch's selection."""
         from . import kernels
         ds = self.dataset
         epoch = int(ds.epoch)
@@ -421,7 +503,12 @@ class DevicePatchLoader:
         plan = ds.plan[pos]
         rows = np.stack([self._slot[plan[:, 0]], plan[:, 1], plan[:, 2], modes[pos]], axis=1)
         h, w = ds.out_size()
-        clean, noisy = kernels.patch_batch(self.source, rows, (np.int64(epoch) << 32) | pos, sigma[pos], ds.seed, h, w)
+        ids = (np.int64(epoch) << 32) | pos
+        if self.paired:
+            target, inp = kernels.patch_pair_batch(self.source, rows, ids, None if ds.dist_mode == "none" else sigma[pos],
+                                                   ds.seed, h, w)
+            return inp, target
+        clean, noisy = kernels.patch_batch(self.source, rows, ids, sigma[pos], ds.seed, h, w)
         return noisy, clean
 
     def __iter__(self):
@@ -435,7 +522,8 @@ class DevicePatchLoader:
             yield self.batch(held)
 
 
-DATASETS = {c.__name__: c for c in (AddictiveGaussianNoiseImagePair, SyntheticNoisyPatches, ImageSuperResolution)}
+DATASETS = {c.__name__: c for c in (AddictiveGaussianNoiseImagePair, SyntheticNoisyPatches, ImageSuperResolution,
+                                    PairedImageRestoration)}
 
 
 # ---------------------------------------------------------------------------
@@ -471,7 +559,39 @@ class SyntheticTestImages:
         return synthetic_clean_patch(np.random.RandomState(self.seed * 7919 + idx), self.h, self.w, self.c)
 
 
-VAL_DATASETS = {c.__name__: c for c in (TestImagesCSV, SyntheticTestImages)}
+class TestPairsCSV:
+    """Whole degraded / clean test pictures listed in a csv (columns index, path, target_path): item i is the
+    (input, target) pair as uint8 H x W x C arrays, as restore.evaluate_pairs takes them."""
+    __test__ = False        # a dataset, not a pytest class
+
+    def __init__(self, csv_path, root_folder="", **_ignored):
+        import pandas as pd
+        infos = pd.read_csv(csv_path, index_col="index")
+        for column in ("path", "target_path"):
+            if column not in infos.columns:
+                raise ValueError(f"TestPairsCSV: {csv_path} needs the columns path and target_path, got "
+                                 f"{list(infos.columns)}")
+        self.paths = [os.path.join(root_folder, p) for p in infos["path"].tolist()]
+        self.target_paths = [os.path.join(root_folder, p) for p in infos["target_path"].tolist()]
+
+    def __len__(self):
+        return len(self.paths)
+
+    def __getitem__(self, idx):
+        from PIL import Image
+        pair = []
+        for path in (self.paths[idx], self.target_paths[idx]):
+            a = np.array(Image.open(path))
+            if a.dtype != np.uint8:
+                raise ValueError(f"TestPairsCSV: {path} is {a.dtype}; only 8-bit pictures are supported")
+            pair.append(a[:, :, None] if a.ndim == 2 else a)
+        if pair[0].shape != pair[1].shape:
+            raise ValueError(f"TestPairsCSV: {self.paths[idx]} is {pair[0].shape} and its target "
+                             f"{self.target_paths[idx]} is {pair[1].shape}")
+        return pair[0], pair[1]
+
+
+VAL_DATASETS = {c.__name__: c for c in (TestImagesCSV, SyntheticTestImages, TestPairsCSV)}
 
 
 def _img_as_ubyte(x: np.ndarray) -> np.ndarray:
@@ -532,14 +652,42 @@ def validate(model: nn.Module, images, sigma: float = 25.0, factor: int = 16, se
     return float(acc[0] / acc[1])
 
 
+def validate_pairs(model: nn.Module, pairs, factor: int = 16, device=None, **tiling_args) -> float:
+    """Mean PSNR of ``model`` over degraded / clean pairs (``pairs[i]`` = (input, target), uint8 H x W x C, a
+    TestPairsCSV for instance): restore.evaluate_pairs on this rank's share.  Nothing is drawn: each input is
+    restored as it is and scored against its target from the exact integer SSE.  tiling_args: tile, halo,
+    micro_batch, ensemble, across_images.
+
+    Several ranks: each takes sharding.shard_range's share of the pairs and the PSNR sum and count are all-reduced,
+    as validate does."""
+    from . import restore
+    rank, world = sharding.world()
+    if device is None:
+        device = next(model.parameters()).device
+    s, e = sharding.shard_range(len(pairs), rank, world)
+    mine = [pairs[i] for i in range(s, e)]
+    psnrs = restore.evaluate_pairs(model, [p[0] for p in mine], [p[1] for p in mine], factor=factor, device=device,
+                                   **tiling_args)["psnr"][1] if mine else []
+    acc = torch.tensor([float(np.sum(psnrs)), float(len(psnrs))], dtype=torch.float64)
+    if world > 1:
+        if torch.distributed.get_backend() == "nccl":
+            acc = acc.to(device)
+        torch.distributed.all_reduce(acc)
+    return float(acc[0] / acc[1])
+
+
 def create_val_dataset(conf: dict):
-    """``datasets.val`` of the YAML ({type, dataset_args, sigma, factor}), or None."""
+    """``datasets.val`` of the YAML ({type, dataset_args, sigma, factor}), or None.  A paired set (TestPairsCSV)
+    takes {type, dataset_args, factor, tile, halo, micro_batch}: validate_pairs' arguments, no sigma."""
     vconf = conf.get("datasets", {}).get("val")
     if not vconf:
         return None, {}
     cls = VAL_DATASETS.get(vconf["type"])
     if cls is None:
         raise ValueError(f"Validation dataset {vconf['type']} is not found.")
+    if cls is TestPairsCSV:
+        args = {k: int(vconf[k]) for k in ("tile", "halo", "micro_batch") if vconf.get(k) is not None}
+        return cls(**vconf.get("dataset_args", {})), dict(args, factor=int(vconf.get("factor", 16)))
     return cls(**vconf.get("dataset_args", {})), {"sigma": float(vconf.get("sigma", 25.0)),
                                                    "factor": int(vconf.get("factor", 16))}
 
@@ -611,9 +759,9 @@ class TrainStage:
         self.sampler = ResumeableSampler(self.dataset, self.batch_size, rank, world)
         if ds_conf.get("device_resident"):
             # batches made on the device from a packed arena; dataloader_args' num_workers is ignored
-            if ds_conf["type"] != "ImageSuperResolution":
-                raise ValueError(f"training stage {index}: device_resident needs type ImageSuperResolution, got "
-                                 f"{ds_conf['type']}")
+            if ds_conf["type"] not in ("ImageSuperResolution", "PairedImageRestoration"):
+                raise ValueError(f"training stage {index}: device_resident needs type ImageSuperResolution or "
+                                 f"PairedImageRestoration, got {ds_conf['type']}")
             self.loader = DevicePatchLoader(self.dataset, self.sampler, self.batch_size, self.drop_last,
                                             shared=shared)
         else:
@@ -859,7 +1007,8 @@ def run(conf: dict, device=None, max_iters: Optional[int] = None) -> Trainer:
                     save()
                     saved_at = trainer.i
                 if val_every and trainer.i % val_every == 0:
-                    psnr = validate(trainer.model, val_set, device=device, **val_args)
+                    check = validate_pairs if isinstance(val_set, TestPairsCSV) else validate
+                    psnr = check(trainer.model, val_set, device=device, **val_args)
                     trainer.val_history.append((trainer.i, psnr))
                     if rank == 0:
                         LOG.info("FINISH VAL EPOCH %d - iter=%d - psnr_testing=%.4f", epoch, trainer.i, psnr)

@@ -855,6 +855,30 @@ grr_status grr_patch_batch(const uint8_t* arena, int64_t arena_elems, int C, con
                            const int32_t* table, const int64_t* sample_ids, const float* sigma, int n, uint64_t seed,
                            int ph, int pw, float* clean, float* noisy, void* stream);
 
+/* ---- the same batch for degraded / clean picture pairs (training.PairedImageRestoration: real camera noise,
+ * JPEG artefacts, blur, rain, published as file pairs).  input_arena and target_arena are two uint8 arenas of
+ * arena_elems elements each that share the one image table: image i of input_arena is the degraded version of
+ * image i of target_arena, with the same H, W and C.  table, sample_ids, n, seed, ph, pw: as grr_patch_batch takes
+ * them.  target, input: float32 [n, C, ph, pw], planar.
+ *
+ * target[s] is grr_patch_batch's clean patch of target_arena.  input[s] is the same patch -- same origin, same
+ * mirror fill, same T_mode -- of input_arena, float(v) / 255.0f as well.  sigma: float32 [n] on the device, or NULL.
+ * With sigma, input additionally gets grr_patch_batch's noise, input = degraded + (float)((double)sigma[s] * z), z
+ * the same function of (seed, sample_ids[s], element); with sigma == NULL or sigma[s] == 0 input is the degraded
+ * pixels bit for bit, and no random number is computed.  input_arena == target_arena is legal: the call is then
+ * grr_patch_batch with the outputs named differently (target = clean, input = noisy, bit for bit).
+ *
+ * One kernel body with grr_patch_batch; its clamping holds for both arenas (one element index, clamped once,
+ * addresses both).  A sample does not depend on the batch it is in.  No atomics. */
+
+/* 1 where grr_patch_pair_batch takes the call: the bounds of grr_patch_batch_supported (each output has
+ * n C ph pw < 2^31 elements). */
+int grr_patch_pair_batch_supported(int C, int n_img, int64_t arena_elems, int n, int ph, int pw);
+grr_status grr_patch_pair_batch(const uint8_t* input_arena, const uint8_t* target_arena, int64_t arena_elems, int C,
+                                const int64_t* img_table, int n_img, const int32_t* table, const int64_t* sample_ids,
+                                const float* sigma /* NULL: no noise */, int n, uint64_t seed, int ph, int pw,
+                                float* target, float* input, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,7 @@
 """Restore image files with a trained model (irdu_amd.restore; single process, one GPU).
 
     python restore.py -yaml_path CONF.yaml --ckpt CHECKPOINT.pt --input FILE_OR_DIR --output DIR \\
-           [--sigma S --seed N [--ssim]] [--tile T --halo H --factor F] [--batch-images]
+           [--sigma S --seed N [--ssim] | --reference DIR [--ssim]] [--tile T --halo H --factor F] [--batch-images]
            [--self-ensemble | --ensemble-modes 0,1,4,5]
 
 The model is ``training.build_model(conf["model"])``; the checkpoint is the training loop's dict (its
@@ -16,8 +16,12 @@ the same.  With --self-ensemble every window is restored under all 8 flips and q
 turned back, are averaged (``ensemble=8``; about 8 times the work); --ensemble-modes takes a subset of the modes
 0..7 (m = 2k + f: k quarter turns counter-clockwise, then an upside-down flip if f), ascending and separated by
 commas.  Both work with --batch-images; the lines printed and the files written keep their formats.  With --ssim
-(only with --sigma) each line also carries the SSIM of the restored image against the input (``irdu_amd.ssim_u8``:
-11 x 11 Gaussian window, both sides at least 11 pixels) and the mean SSIM follows the mean PSNR.
+(with --sigma or --reference) each line also carries the SSIM of the restored image against the input, or the
+reference (``irdu_amd.ssim_u8``: 11 x 11 Gaussian window, both sides at least 11 pixels) and the mean SSIM follows
+the mean PSNR.  With --reference DIR (not with --sigma) the inputs are degraded pictures that have a ground truth:
+each is restored as it is and scored against the file of the same stem in DIR, which must have the input's size
+and channels; PSNR per file and the mean are printed as with --sigma.  A reference that is missing, ambiguous or of
+another size is reported before anything runs.  It works with --batch-images and the ensemble options.
 """
 import argparse
 import os
@@ -39,15 +43,49 @@ def input_files(path: str):
     return [path]
 
 
-def main(argv=None) -> None:
+def reference_files(files, ref_dir: str):
+    """The reference of each input file: the one image file of ``ref_dir`` with the input's stem (any of
+    EXTENSIONS).  SystemExit naming the input where there is none, or more than one."""
+    if not os.path.isdir(ref_dir):
+        raise SystemExit(f"--reference: {ref_dir} is not a directory")
+    by_stem = {}
+    for f in sorted(os.listdir(ref_dir)):
+        if f.lower().endswith(EXTENSIONS):
+            by_stem.setdefault(os.path.splitext(f)[0], []).append(os.path.join(ref_dir, f))
+    refs = []
+    for path in files:
+        stem = os.path.splitext(os.path.basename(path))[0]
+        found = by_stem.get(stem, [])
+        if len(found) != 1:
+            raise SystemExit(f"--reference: {path} has {'no' if not found else len(found)} reference(s) named "
+                             f"{stem}.* in {ref_dir}" + (f" ({', '.join(found)})" if found else ""))
+        refs.append(found[0])
+    return refs
+
+
+def check_references(files, refs) -> None:
+    """SystemExit for the first reference whose size or channels differ from its input's (headers only)."""
+    from PIL import Image
+    for path, ref in zip(files, refs):
+        with Image.open(path) as a, Image.open(ref) as b:
+            if a.size != b.size or len(a.getbands()) != len(b.getbands()):
+                raise SystemExit(f"--reference: {ref} is {b.size[1]}x{b.size[0]}x{len(b.getbands())}, its input {path} "
+                                 f"is {a.size[1]}x{a.size[0]}x{len(a.getbands())}")
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("-yaml_path", type=str, required=True, help="option YAML file (its model: section is used)")
     ap.add_argument("--ckpt", type=str, default=None, help="training checkpoint (dict with a 'model' entry)")
     ap.add_argument("--input", type=str, required=True, help="an image file, or a directory of them")
     ap.add_argument("--output", type=str, required=True, help="directory for the restored images (PNG)")
-    ap.add_argument("--sigma", type=float, default=None, help="treat inputs as clean: add this noise, report PSNR")
+    scored = ap.add_mutually_exclusive_group()
+    scored.add_argument("--sigma", type=float, default=None, help="treat inputs as clean: add this noise, report PSNR")
+    scored.add_argument("--reference", type=str, default=None, metavar="DIR",
+                        help="inputs are degraded: restore them as they are, report PSNR against the file of the same "
+                             "stem in DIR")
     ap.add_argument("--seed", type=int, default=2204)
-    ap.add_argument("--ssim", action="store_true", help="with --sigma: report the SSIM beside the PSNR")
+    ap.add_argument("--ssim", action="store_true", help="with --sigma or --reference: report the SSIM beside the PSNR")
     ap.add_argument("--tile", type=int, default=None)
     ap.add_argument("--halo", type=int, default=None)
     ap.add_argument("--factor", type=int, default=16)
@@ -59,14 +97,20 @@ def main(argv=None) -> None:
     group.add_argument("--ensemble-modes", type=str, default=None, metavar="M,M,...",
                        help="average over these modes of 0..7 only, ascending (e.g. 0,1,4,5)")
     args = ap.parse_args(argv)
-    if args.ssim and args.sigma is None:
-        ap.error("--ssim needs --sigma: there is nothing to compare a restored image with otherwise")
-    ensemble = 8 if args.self_ensemble else 1
+    if args.ssim and args.sigma is None and args.reference is None:
+        ap.error("--ssim needs --sigma or --reference: there is nothing to compare a restored image with otherwise")
+    args.ensemble = 8 if args.self_ensemble else 1
     if args.ensemble_modes is not None:
         try:
-            ensemble = tuple(int(m) for m in args.ensemble_modes.split(","))
+            args.ensemble = tuple(int(m) for m in args.ensemble_modes.split(","))
         except ValueError:
             ap.error(f"--ensemble-modes: expected integers separated by commas, got {args.ensemble_modes!r}")
+    return args
+
+
+def main(argv=None) -> None:
+    args = parse_args(argv)
+    ensemble = args.ensemble
 
     import numpy as np
     import torch
@@ -79,6 +123,11 @@ def main(argv=None) -> None:
     except ValueError as e:
         raise SystemExit(str(e))
     files = input_files(args.input)
+    refs = {}
+    if args.reference is not None:
+        found = reference_files(files, args.reference)
+        check_references(files, found)
+        refs = dict(zip(files, found))
     conf = training.parse_options(args.yaml_path)
     if not torch.cuda.is_available():
         raise SystemExit("restore.py needs a GPU: the HIP engine has no CPU path")
@@ -109,16 +158,20 @@ def main(argv=None) -> None:
 
     def finish(path, img, out):
         out_path = os.path.join(args.output, os.path.splitext(os.path.basename(path))[0] + ".png")
-        if args.sigma is None:
+        if args.sigma is None and args.reference is None:
             print(f"{path} -> {out_path}  {img.shape[0]}x{img.shape[1]}x{img.shape[2]}")
         else:
             if out.shape != img.shape:
                 raise SystemExit(f"{path}: the model returns {out.shape[2]} channels for {img.shape[2]}; no PSNR")
-            psnrs.append(irdu_amd.psnr_u8(out, img))
-            line = f"{path} -> {out_path}  sigma {args.sigma:g}  PSNR {psnrs[-1]:.4f} dB"
+            truth = img if args.reference is None else read(refs[path])
+            if truth.shape != out.shape:
+                raise SystemExit(f"--reference: {refs[path]} decodes to {truth.shape}, the restored {path} is {out.shape}")
+            psnrs.append(irdu_amd.psnr_u8(out, truth))
+            against = f"sigma {args.sigma:g}" if args.reference is None else f"reference {refs[path]}"
+            line = f"{path} -> {out_path}  {against}  PSNR {psnrs[-1]:.4f} dB"
             if args.ssim:
                 try:
-                    ssims.append(irdu_amd.ssim_u8(out, img))
+                    ssims.append(irdu_amd.ssim_u8(out, truth))
                 except ValueError as e:
                     raise SystemExit(f"{path}: {e}")
                 line += f"  SSIM {ssims[-1]:.4f}"
