@@ -654,10 +654,11 @@ grr_status grr_win_bwd_edge_weights(const float* feat, int64_t feat_bstride, con
               GRR_ERR_INVALID_ARG, "grr_win_bwd_edge_weights: bad args");
   GRR_REQUIRE(F <= GRR_MAX_NODE_FTS, GRR_ERR_UNSUPPORTED, "grr_win_bwd_edge_weights: F=%d > %d", F,
               GRR_MAX_NODE_FTS);
+  // before the first launch: the softmax reverse overwrites gw in place
+  GRR_REQUIRE((int64_t)B * G <= 65535, GRR_ERR_UNSUPPORTED, "grr_win_bwd_edge_weights: B*G > 65535");
   const int64_t npix = (int64_t)B * G * H * W;
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(win_softmax_bwd_kernel, dim3(grid_1d(npix)), dim3(NTB), 0, s, w, gw, K, (int64_t)H * W, npix);
-  GRR_REQUIRE((int64_t)B * G <= 65535, GRR_ERR_UNSUPPORTED, "grr_win_bwd_edge_weights: B*G > 65535");
   grr_status st = launch_status("grr_win_bwd_edge_weights");
   if (st != GRR_OK) return st;
   const dim3 grid = plane_grid(H, W, B * G);
