@@ -43,6 +43,7 @@ from . import restore  # noqa: F401  (whole-image restoration of 8-bit / float i
 from .restore import RestorePlan, evaluate, plan, psnr_u8, restore_image  # noqa: F401
 from .restore import ImagePack, pack_images, plan_images, restore_images  # noqa: F401  (lists of images)
 from .restore import evaluate_metrics, ssim_u8  # noqa: F401  (SSIM beside the PSNR)
+from .restore import psnr_y_u8, ssim_y_u8  # noqa: F401  (the two on the Y channel of RGB images)
 from .training import PairedImageRestoration  # noqa: F401  (degraded / clean file pairs)
 from .restore import evaluate_pairs  # noqa: F401
 

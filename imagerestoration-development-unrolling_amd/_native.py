@@ -179,6 +179,12 @@ SIGNATURES = {
     "grr_u8_ssim_supported": [I, I, I],
     "grr_u8_ssim": [P, P, I, I, I, P, P],
     "grr_u8_ssim_images": [P, P, L, I, P, I, I, I, P, P],
+    # ... and the PSNR's SSE, on the luma of RGB images
+    "grr_u8_luma_supported": [I, I, I],
+    "grr_u8_luma_sse": [P, P, I, I, P, P],
+    "grr_u8_luma_sse_images": [P, P, L, P, I, P, P],
+    "grr_u8_luma_ssim": [P, P, I, I, P, P],
+    "grr_u8_luma_ssim_images": [P, P, L, P, I, I, I, P, P],
     # training batches from an image arena (training.DevicePatchLoader)
     "grr_patch_batch_supported": [I, I, L, I, I, I],
     "grr_patch_batch": [P, L, I, P, I, P, P, P, I, ctypes.c_uint64, I, I, P, P, P],

@@ -31,6 +31,20 @@
 // The arena's image table is device data: the offset is clamped into [0, arena_elems), H and W into
 // [1, max_h] x [1, max_w], and every byte index into [0, arena_elems), so a bad table gives a wrong number,
 // never an access outside the arenas.  An image with a side below 11 contributes nothing.
+//
+// Luma (Y of ITU-R BT.601 "studio range" YCbCr: MATLAB's rgb2ycbcr, BasicSR's to_y_channel, not rounded to uint8)
+// of two uint8 H x W x 3 images, channels R, G, B interleaved:
+//
+//   grr_u8_luma_sse, grr_u8_luma_sse_images    sum D^2 as two exact 64-bit words
+//   grr_u8_luma_ssim, grr_u8_luma_ssim_images  the sum q above of the single plane Y
+//
+// Y = Ny / 255000 with the integer Ny = 4080000 + 65481 R + 128553 G + 24966 B <= 59 925 000.  The SSE is the
+// integer sum of D^2, D = Ny(a) - Ny(b) = 65481 dR + 128553 dG + 24966 dB, |D| <= 55 845 000 < 2^26: D^2 < 2^52,
+// and the sum over fewer than 2^30 pixels can reach 2^82, so the kernel adds D^2 mod 2^32 and D^2 >> 32 apart
+// (below 2^62 and 2^50) and the caller joins them: out[0] + (out[1] << 32).  The SSIM stages one float64
+// Y = double(Ny) / 255000.0 per pixel -- the integer is exact and the division rounds once, so the device and
+// every host form the same bits -- and runs the body above over pixel columns: u8_ssim_kernel takes what a staged
+// column is (BytePx<C>: one interleaved byte; LumaPx: the luma of three) as a template parameter.
 #include <algorithm>
 
 #include "grr_common.h"
@@ -41,7 +55,7 @@ namespace grr {
 namespace {
 
 constexpr int kSsimThreads = 256;
-constexpr int kSsimCols = 256;      // output byte columns of a tile (one per lane); kernels.SSIM_TILE[1]
+constexpr int kSsimCols = 256;      // output columns of a tile (one per lane); kernels.SSIM_TILE[1], LUMA_SSIM_TILE[1]
 constexpr int kSsimRows = 32;       // output rows of a tile; kernels.SSIM_TILE[0]
 constexpr int kSsimTaps = 11;
 constexpr int kSsimMaxImages = 65535;   // one grid row (blockIdx.y) per image
@@ -81,22 +95,50 @@ struct SsimArena {
   __device__ __forceinline__ int64_t clamped(int64_t e) const { return e < elems - 1 ? e : elems - 1; }   // e >= 0
 };
 
-// byte col of a row that starts at byte row0 and is rowlen long; 0 beyond the row (no valid column reads it)
-template <typename Src>
-__device__ __forceinline__ uint32_t ssim_byte(const uint8_t* __restrict__ p, const Src& src, int64_t row0, int64_t col,
-                                              int64_t rowlen) {
-  return col < rowlen ? (uint32_t)p[src.clamped(row0 + col)] : 0u;
+// What a staged column of a row is.  kStep: the columns between two taps of one output column; kBytes: the bytes a
+// column is made of; cols(W): the columns of a row; load: the column's integer, which is in flight while the row
+// before it is filtered; value: its float64, formed once per column when it is staged.
+
+// every interleaved byte of an H x W x C image: the SSIM of each channel
+template <int C>
+struct BytePx {
+  static constexpr int kStep = C, kBytes = 1;
+  static __host__ __device__ __forceinline__ int64_t cols(int W) { return (int64_t)W * C; }
+  template <typename Src>
+  static __device__ __forceinline__ uint32_t load(const uint8_t* __restrict__ p, const Src& src, int64_t e) {
+    return (uint32_t)p[src.clamped(e)];
+  }
+  static __device__ __forceinline__ double value(uint32_t v) { return (double)v; }
+};
+
+// the luma of every pixel of an H x W x 3 image: Ny <= 59 925 000 in flight, double(Ny) / 255000.0 staged
+constexpr uint32_t kLumaBase = 4080000u, kLumaR = 65481u, kLumaG = 128553u, kLumaB = 24966u;
+struct LumaPx {
+  static constexpr int kStep = 1, kBytes = 3;
+  static __host__ __device__ __forceinline__ int64_t cols(int W) { return W; }
+  template <typename Src>
+  static __device__ __forceinline__ uint32_t load(const uint8_t* __restrict__ p, const Src& src, int64_t e) {
+    return kLumaBase + kLumaR * p[src.clamped(e)] + kLumaG * p[src.clamped(e + 1)] + kLumaB * p[src.clamped(e + 2)];
+  }
+  static __device__ __forceinline__ double value(uint32_t v) { return (double)v / 255000.0; }
+};
+
+// column col of a row that starts at byte row0 and has ncols columns; 0 beyond the row (no valid column reads it)
+template <typename Px, typename Src>
+__device__ __forceinline__ uint32_t ssim_col(const uint8_t* __restrict__ p, const Src& src, int64_t row0, int64_t col,
+                                             int64_t ncols) {
+  return col < ncols ? Px::load(p, src, row0 + col * Px::kBytes) : 0u;
 }
 
-template <int C, typename Src>
+template <typename Px, typename Src>
 __global__ __launch_bounds__(kSsimThreads) void u8_ssim_kernel(const uint8_t* __restrict__ a,
                                                                const uint8_t* __restrict__ b, Src src, SsimTaps taps,
                                                                unsigned long long* out) {
-  constexpr int kExtra = (kSsimTaps - 1) * C;             // bytes a tile's row needs beyond its 256 columns
-  __shared__ double lds[2][2][kSsimCols + kExtra];        // [buffer][a, b][byte column of the tile]
+  constexpr int kExtra = (kSsimTaps - 1) * Px::kStep;     // columns a tile's row needs beyond its 256
+  __shared__ double lds[2][2][kSsimCols + kExtra];        // [buffer][a, b][column of the tile]
   const SsimImage im = src.image(blockIdx.y);
   if (im.H < kSsimTaps || im.W < kSsimTaps) return;       // whole block: before any barrier
-  const int64_t rowlen = (int64_t)im.W * C, vcols = rowlen - kExtra;
+  const int64_t ncols = Px::cols(im.W), rowlen = ncols * Px::kBytes, vcols = ncols - kExtra;
   const int vrows = im.H - (kSsimTaps - 1);
   const int64_t tcols = (vcols + kSsimCols - 1) / kSsimCols, trows = (vrows + kSsimRows - 1) / kSsimRows;
   if ((int64_t)blockIdx.x >= tcols * trows) return;       // the grid is the largest image's
@@ -107,15 +149,15 @@ __global__ __launch_bounds__(kSsimThreads) void u8_ssim_kernel(const uint8_t* __
   const bool active = j0 + t < vcols;
   const bool extra = t < kExtra;
 
-  // the bytes this lane stages for the row in flight: column j0 + t and, for the first 10 C lanes, j0 + 256 + t
+  // what this lane stages for the row in flight: column j0 + t and, for the first kExtra lanes, j0 + 256 + t
   uint32_t pa0, pb0, pa1 = 0, pb1 = 0;
   {
     const int64_t row0 = im.off + (int64_t)r0 * rowlen;
-    pa0 = ssim_byte(a, src, row0, j0 + t, rowlen);
-    pb0 = ssim_byte(b, src, row0, j0 + t, rowlen);
+    pa0 = ssim_col<Px>(a, src, row0, j0 + t, ncols);
+    pb0 = ssim_col<Px>(b, src, row0, j0 + t, ncols);
     if (extra) {
-      pa1 = ssim_byte(a, src, row0, j0 + kSsimCols + t, rowlen);
-      pb1 = ssim_byte(b, src, row0, j0 + kSsimCols + t, rowlen);
+      pa1 = ssim_col<Px>(a, src, row0, j0 + kSsimCols + t, ncols);
+      pb1 = ssim_col<Px>(b, src, row0, j0 + kSsimCols + t, ncols);
     }
   }
 
@@ -133,19 +175,19 @@ __global__ __launch_bounds__(kSsimThreads) void u8_ssim_kernel(const uint8_t* __
       if (r < rin_end) {
         double* la = lds[(r - r0) & 1][0];
         double* lb = lds[(r - r0) & 1][1];
-        la[t] = (double)pa0;
-        lb[t] = (double)pb0;
+        la[t] = Px::value(pa0);
+        lb[t] = Px::value(pb0);
         if (extra) {
-          la[kSsimCols + t] = (double)pa1;
-          lb[kSsimCols + t] = (double)pb1;
+          la[kSsimCols + t] = Px::value(pa1);
+          lb[kSsimCols + t] = Px::value(pb1);
         }
         if (r + 1 < rin_end) {
           const int64_t row0 = im.off + (int64_t)(r + 1) * rowlen;
-          pa0 = ssim_byte(a, src, row0, j0 + t, rowlen);
-          pb0 = ssim_byte(b, src, row0, j0 + t, rowlen);
+          pa0 = ssim_col<Px>(a, src, row0, j0 + t, ncols);
+          pb0 = ssim_col<Px>(b, src, row0, j0 + t, ncols);
           if (extra) {
-            pa1 = ssim_byte(a, src, row0, j0 + kSsimCols + t, rowlen);
-            pb1 = ssim_byte(b, src, row0, j0 + kSsimCols + t, rowlen);
+            pa1 = ssim_col<Px>(a, src, row0, j0 + kSsimCols + t, ncols);
+            pb1 = ssim_col<Px>(b, src, row0, j0 + kSsimCols + t, ncols);
           }
         }
         // this buffer was last read two rows ago, before the previous row's barrier
@@ -153,10 +195,10 @@ __global__ __launch_bounds__(kSsimThreads) void u8_ssim_kernel(const uint8_t* __
         double hx = 0.0, hy = 0.0, hxx = 0.0, hyy = 0.0, hxy = 0.0;
 #pragma unroll
         for (int k = 0; k < kSsimTaps; ++k) {
-          const double x = la[t + k * C], y = lb[t + k * C], g = taps.g[k];
+          const double x = la[t + k * Px::kStep], y = lb[t + k * Px::kStep], g = taps.g[k];
           hx = __builtin_fma(g, x, hx);
           hy = __builtin_fma(g, y, hy);
-          hxx = __builtin_fma(g, x * x, hxx);      // the products of two bytes are exact
+          hxx = __builtin_fma(g, x * x, hxx);      // a product of two bytes is exact, of two lumas rounded once
           hyy = __builtin_fma(g, y * y, hyy);
           hxy = __builtin_fma(g, x * y, hxy);
         }
@@ -191,17 +233,112 @@ template <typename Src>
 void ssim_launch(int C, dim3 grid, hipStream_t s, const uint8_t* a, const uint8_t* b, const Src& src,
                  unsigned long long* out) {
   switch (C) {
-    case 1: hipLaunchKernelGGL((u8_ssim_kernel<1, Src>), grid, dim3(kSsimThreads), 0, s, a, b, src, kTaps, out); break;
-    case 2: hipLaunchKernelGGL((u8_ssim_kernel<2, Src>), grid, dim3(kSsimThreads), 0, s, a, b, src, kTaps, out); break;
-    case 3: hipLaunchKernelGGL((u8_ssim_kernel<3, Src>), grid, dim3(kSsimThreads), 0, s, a, b, src, kTaps, out); break;
-    default: hipLaunchKernelGGL((u8_ssim_kernel<4, Src>), grid, dim3(kSsimThreads), 0, s, a, b, src, kTaps, out); break;
+    case 1: hipLaunchKernelGGL((u8_ssim_kernel<BytePx<1>, Src>), grid, dim3(kSsimThreads), 0, s, a, b, src, kTaps, out); break;
+    case 2: hipLaunchKernelGGL((u8_ssim_kernel<BytePx<2>, Src>), grid, dim3(kSsimThreads), 0, s, a, b, src, kTaps, out); break;
+    case 3: hipLaunchKernelGGL((u8_ssim_kernel<BytePx<3>, Src>), grid, dim3(kSsimThreads), 0, s, a, b, src, kTaps, out); break;
+    default: hipLaunchKernelGGL((u8_ssim_kernel<BytePx<4>, Src>), grid, dim3(kSsimThreads), 0, s, a, b, src, kTaps, out); break;
   }
 }
 
-// tiles of an h x w image with both sides >= 11
+void luma_ssim_launch(dim3 grid, hipStream_t s, const uint8_t* a, const uint8_t* b, const SsimOne& src,
+                      unsigned long long* out) {
+  hipLaunchKernelGGL((u8_ssim_kernel<LumaPx, SsimOne>), grid, dim3(kSsimThreads), 0, s, a, b, src, kTaps, out);
+}
+void luma_ssim_launch(dim3 grid, hipStream_t s, const uint8_t* a, const uint8_t* b, const SsimArena& src,
+                      unsigned long long* out) {
+  hipLaunchKernelGGL((u8_ssim_kernel<LumaPx, SsimArena>), grid, dim3(kSsimThreads), 0, s, a, b, src, kTaps, out);
+}
+
+// tiles of an h x w image with both sides >= 11 and C columns per pixel (the luma: 1)
 int64_t ssim_tiles(int h, int w, int C) {
   const int64_t vcols = (int64_t)(w - (kSsimTaps - 1)) * C, vrows = h - (kSsimTaps - 1);
   return ((vcols + kSsimCols - 1) / kSsimCols) * ((vrows + kSsimRows - 1) / kSsimRows);
+}
+
+// ---------------------------------------------------------------------------
+// Luma SSE.  A 256-thread workgroup takes kLumaSsePx consecutive pixels per step, lane t the pixels
+// t + 256 k, k < kLumaSseLanePx, so adjacent lanes read adjacent pixels; gridDim.x workgroups stride over the
+// image.  Six single-byte loads per pixel: an image starts at any byte.  D in 32 bits, D^2 in 64, the two halves
+// added apart: per lane, per wave (shuffles), per workgroup (LDS), then one 64-bit vector atomic per workgroup and
+// half.  All integer adds: the same sums whatever the grid and whatever order the atomics land in.
+constexpr int kLumaSseThreads = 256;
+constexpr int kLumaSseLanePx = 8;                                   // kernels.LUMA_SSE_BLOCK[1]
+constexpr int kLumaSsePx = kLumaSseThreads * kLumaSseLanePx;        // kernels.LUMA_SSE_BLOCK[0]
+constexpr int kLumaSseMaxBlocks = 1024;                             // kernels.LUMA_SSE_MAX_BLOCKS: stride beyond
+
+struct LumaSpan {
+  int64_t off;   // first byte of the image in a and in b
+  int64_t n;     // pixels
+};
+
+// grr_u8_luma_sse: one image of n pixels at a and b
+struct LumaSseOne {
+  int64_t n;
+  __device__ __forceinline__ LumaSpan image(int) const { return LumaSpan{0, n}; }
+};
+
+// grr_u8_luma_sse_images: image blockIdx.y of the device image table [n_img, 3] (element offset, H, W).  The
+// offset is clamped into [0, elems), H and W into [1, 2^31) and the pixel count to what the arena holds from the
+// offset on, so every byte read lies inside the arenas and the loop ends with the arena.
+struct LumaSseArena {
+  const int64_t* img_table;
+  int64_t elems;
+  __device__ __forceinline__ LumaSpan image(int i) const {
+    const int64_t* it = img_table + (int64_t)i * 3;
+    const int64_t lim = (1ll << 31) - 1;
+    const int64_t off = it[0] < 0 ? 0 : (it[0] > elems - 1 ? elems - 1 : it[0]);
+    const int64_t h = it[1] < 1 ? 1 : (it[1] > lim ? lim : it[1]), w = it[2] < 1 ? 1 : (it[2] > lim ? lim : it[2]);
+    const int64_t fit = (elems - off) / 3, n = h * w;
+    return LumaSpan{off, n < fit ? n : fit};
+  }
+};
+
+template <typename Src>
+__global__ __launch_bounds__(kLumaSseThreads) void u8_luma_sse_kernel(const uint8_t* __restrict__ a,
+                                                                      const uint8_t* __restrict__ b, Src src,
+                                                                      unsigned long long* out) {
+  const LumaSpan im = src.image(blockIdx.y);
+  const uint8_t* __restrict__ pa = a + im.off;
+  const uint8_t* __restrict__ pb = b + im.off;
+  unsigned long long lo = 0, hi = 0;      // sum (D^2 mod 2^32) < 2^62, sum (D^2 >> 32) < 2^50 over n < 2^30 pixels
+  for (int64_t base = (int64_t)blockIdx.x * kLumaSsePx; base < im.n; base += (int64_t)gridDim.x * kLumaSsePx) {
+#pragma unroll
+    for (int k = 0; k < kLumaSseLanePx; ++k) {
+      const int64_t px = base + k * kLumaSseThreads + threadIdx.x;
+      if (px < im.n) {
+        const uint8_t* x = pa + 3 * px;
+        const uint8_t* y = pb + 3 * px;
+        const int d = (int)kLumaR * ((int)x[0] - (int)y[0]) + (int)kLumaG * ((int)x[1] - (int)y[1]) +
+                      (int)kLumaB * ((int)x[2] - (int)y[2]);                       // |d| <= 55 845 000
+        const unsigned long long d2 = (unsigned long long)((long long)d * (long long)d);
+        lo += d2 & 0xffffffffull;
+        hi += d2 >> 32;
+      }
+    }
+  }
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) {
+    lo += __shfl_down(lo, off, kWave);
+    hi += __shfl_down(hi, off, kWave);
+  }
+  // the waves' sums through LDS: both words of an image share a cache line, and atomics on one line run one after
+  // another chip-wide, so a workgroup sends one pair, not one per wave
+  __shared__ unsigned long long part[2][kLumaSseThreads / kWave];
+  if ((threadIdx.x & (kWave - 1)) == 0) {
+    part[0][threadIdx.x / kWave] = lo;
+    part[1][threadIdx.x / kWave] = hi;
+  }
+  __syncthreads();      // every lane arrives: nothing above returns
+  if (threadIdx.x == 0) {
+    lo = hi = 0;
+#pragma unroll
+    for (int w = 0; w < kLumaSseThreads / kWave; ++w) {
+      lo += part[0][w];
+      hi += part[1][w];
+    }
+    if (lo) atomicAdd(out + 2 * (int64_t)blockIdx.y, lo);
+    if (hi) atomicAdd(out + 2 * (int64_t)blockIdx.y + 1, hi);
+  }
 }
 
 }  // namespace
@@ -251,6 +388,87 @@ grr_status grr_u8_ssim_images(const uint8_t* a, const uint8_t* b, int64_t arena_
   ssim_launch(C, dim3((uint32_t)tiles, (uint32_t)n_img), s, a, b, SsimArena{img_table, arena_elems, max_h, max_w},
               reinterpret_cast<unsigned long long*>(out));
   return launch_status("grr_u8_ssim_images");
+}
+
+int grr_u8_luma_supported(int H, int W, int need_window) {
+  const int least = need_window ? kSsimTaps : 1;
+  return H >= least && W >= least && (int64_t)H * W * 3 < (1ll << 31) ? 1 : 0;
+}
+
+grr_status grr_u8_luma_sse(const uint8_t* a, const uint8_t* b, int H, int W, uint64_t* out, void* stream) {
+  clear_error();
+  GRR_REQUIRE(a && b && out && H > 0 && W > 0 && (uintptr_t)out % 8 == 0, GRR_ERR_INVALID_ARG,
+              "grr_u8_luma_sse: bad args");
+  GRR_REQUIRE(grr_u8_luma_supported(H, W, 0), GRR_ERR_UNSUPPORTED,
+              "grr_u8_luma_sse: needs H W 3 < 2^31 (got %d x %d x 3)", H, W);
+  hipStream_t s = (hipStream_t)stream;
+  GRR_REQUIRE(hipMemsetAsync(out, 0, 2 * sizeof(uint64_t), s) == hipSuccess, GRR_ERR_HIP,
+              "grr_u8_luma_sse: zeroing the sums failed");
+  const int64_t n = (int64_t)H * W;
+  const int blocks = (int)std::min<int64_t>((n + kLumaSsePx - 1) / kLumaSsePx, kLumaSseMaxBlocks);
+  hipLaunchKernelGGL((u8_luma_sse_kernel<LumaSseOne>), dim3(blocks), dim3(kLumaSseThreads), 0, s, a, b, LumaSseOne{n},
+                     reinterpret_cast<unsigned long long*>(out));
+  return launch_status("grr_u8_luma_sse");
+}
+
+grr_status grr_u8_luma_sse_images(const uint8_t* a, const uint8_t* b, int64_t arena_elems, const int64_t* img_table,
+                                  int n_img, uint64_t* out, void* stream) {
+  clear_error();
+  GRR_REQUIRE(a && b && img_table && out && arena_elems > 0 && n_img > 0 && (uintptr_t)out % 8 == 0 &&
+                  (uintptr_t)img_table % 8 == 0,
+              GRR_ERR_INVALID_ARG, "grr_u8_luma_sse_images: bad args");
+  GRR_REQUIRE(grr_image_arena_supported(3, n_img, arena_elems), GRR_ERR_UNSUPPORTED,
+              "grr_u8_luma_sse_images: needs n_img <= arena_elems < 2^62 (got %d images, %lld elements)", n_img,
+              (long long)arena_elems);
+  GRR_REQUIRE(n_img <= kSsimMaxImages, GRR_ERR_UNSUPPORTED,
+              "grr_u8_luma_sse_images: at most %d images per call, one grid row each (got %d)", kSsimMaxImages, n_img);
+  hipStream_t s = (hipStream_t)stream;
+  GRR_REQUIRE(hipMemsetAsync(out, 0, 2 * sizeof(uint64_t) * n_img, s) == hipSuccess, GRR_ERR_HIP,
+              "grr_u8_luma_sse_images: zeroing the sums failed");
+  // workgroups per image from the mean image: one step each, at most 256
+  const int64_t px = arena_elems / 3 / n_img;
+  const int bx = (int)std::min<int64_t>(std::max<int64_t>((px + kLumaSsePx - 1) / kLumaSsePx, 1), 256);
+  hipLaunchKernelGGL((u8_luma_sse_kernel<LumaSseArena>), dim3(bx, n_img), dim3(kLumaSseThreads), 0, s, a, b,
+                     LumaSseArena{img_table, arena_elems}, reinterpret_cast<unsigned long long*>(out));
+  return launch_status("grr_u8_luma_sse_images");
+}
+
+grr_status grr_u8_luma_ssim(const uint8_t* a, const uint8_t* b, int H, int W, int64_t* out, void* stream) {
+  clear_error();
+  GRR_REQUIRE(a && b && out && H > 0 && W > 0 && (uintptr_t)out % 8 == 0, GRR_ERR_INVALID_ARG,
+              "grr_u8_luma_ssim: bad args");
+  GRR_REQUIRE(grr_u8_luma_supported(H, W, 1), GRR_ERR_UNSUPPORTED,
+              "grr_u8_luma_ssim: needs H and W >= 11 and H W 3 < 2^31 (got %d x %d x 3)", H, W);
+  hipStream_t s = (hipStream_t)stream;
+  GRR_REQUIRE(hipMemsetAsync(out, 0, sizeof(int64_t), s) == hipSuccess, GRR_ERR_HIP,
+              "grr_u8_luma_ssim: zeroing the sum failed");
+  luma_ssim_launch(dim3((uint32_t)ssim_tiles(H, W, 1)), s, a, b, SsimOne{H, W}, reinterpret_cast<unsigned long long*>(out));
+  return launch_status("grr_u8_luma_ssim");
+}
+
+grr_status grr_u8_luma_ssim_images(const uint8_t* a, const uint8_t* b, int64_t arena_elems, const int64_t* img_table,
+                                   int n_img, int max_h, int max_w, int64_t* out, void* stream) {
+  clear_error();
+  GRR_REQUIRE(a && b && img_table && out && arena_elems > 0 && n_img > 0 && max_h > 0 && max_w > 0 &&
+                  (uintptr_t)out % 8 == 0 && (uintptr_t)img_table % 8 == 0,
+              GRR_ERR_INVALID_ARG, "grr_u8_luma_ssim_images: bad args");
+  GRR_REQUIRE(grr_image_arena_supported(3, n_img, arena_elems), GRR_ERR_UNSUPPORTED,
+              "grr_u8_luma_ssim_images: needs n_img <= arena_elems < 2^62 (got %d images, %lld elements)", n_img,
+              (long long)arena_elems);
+  GRR_REQUIRE(n_img <= kSsimMaxImages, GRR_ERR_UNSUPPORTED,
+              "grr_u8_luma_ssim_images: at most %d images per call, one grid row each (got %d)", kSsimMaxImages, n_img);
+  const bool any = max_h >= kSsimTaps && max_w >= kSsimTaps;      // else no image has a valid pixel: all sums are 0
+  const int64_t tiles = any ? ssim_tiles(max_h, max_w, 1) : 0;
+  GRR_REQUIRE(tiles < (1ll << 31), GRR_ERR_UNSUPPORTED,
+              "grr_u8_luma_ssim_images: max_h x max_w must be below 2^31 tiles of %d x %d (got %d x %d)", kSsimRows,
+              kSsimCols, max_h, max_w);
+  hipStream_t s = (hipStream_t)stream;
+  GRR_REQUIRE(hipMemsetAsync(out, 0, sizeof(int64_t) * n_img, s) == hipSuccess, GRR_ERR_HIP,
+              "grr_u8_luma_ssim_images: zeroing the sums failed");
+  if (!any) return GRR_OK;
+  luma_ssim_launch(dim3((uint32_t)tiles, (uint32_t)n_img), s, a, b, SsimArena{img_table, arena_elems, max_h, max_w},
+                   reinterpret_cast<unsigned long long*>(out));
+  return launch_status("grr_u8_luma_ssim_images");
 }
 
 }  // extern "C"

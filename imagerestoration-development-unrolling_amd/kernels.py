@@ -2275,30 +2275,134 @@ def u8_ssim(a: Tensor, b: Tensor) -> int:
     return int(out.item())
 
 
+def _check_pack_pair(name: str, a_pack, b_pack, ok, channels: Optional[int] = None) -> Tuple[int, int, tuple]:
+    """(n_img, C, host table) of two uint8 packs that describe the same images on one device, every image passing
+    ok(C, H, W) (and C == channels where given); errors before any launch otherwise."""
+    n_img, c = _check_pack(name, a_pack, placed=False)
+    _check_pack(name, b_pack, placed=False)
+    a, b = a_pack.arena, b_pack.arena
+    if a.dtype != torch.uint8 or b.dtype != torch.uint8:
+        raise ValueError(f"{name}: expected uint8 arenas, got {a.dtype} and {b.dtype}")
+    host = tuple(tuple(int(v) for v in row) for row in a_pack.host_table)
+    if host != tuple(tuple(int(v) for v in row) for row in b_pack.host_table) or b_pack.c != c or a.numel() != b.numel():
+        raise ValueError(f"{name}: the two packs must hold the same images (equal host tables, C and arena "
+                         "lengths)")
+    if channels is not None and c != channels:
+        raise ValueError(f"{name}: the luma is defined for H x W x {channels} images (R, G, B), got C {c}")
+    for i, (_, h, w) in enumerate(host):
+        if not ok(c, h, w):
+            raise ValueError(f"{name}: image {i} needs both sides at least {SSIM_WINDOW} (got {h} x {w} x {c})")
+    if n_img > MAX_SSIM_IMAGES:
+        raise ValueError(f"{name}: 1..{MAX_SSIM_IMAGES} images per call (got {n_img})")
+    _check_placed(name, a_pack)
+    _check_placed(name, b_pack)
+    if a.device != b.device:
+        raise ValueError(f"{name}: the two packs must be on one device")
+    return n_img, c, host
+
+
 def u8_ssim_images(a_pack, b_pack) -> List[int]:
     """[u8_ssim of image i of the two packs for each i] in one launch: exact Python ints, one device-to-host copy
     of the sums (synchronises).  The packs (restore.ImagePack: uint8 arenas) describe the same images: equal host
     tables, one device; every image has both sides at least 11."""
-    n_img, c = _check_pack("u8_ssim_images", a_pack, placed=False)
-    _check_pack("u8_ssim_images", b_pack, placed=False)
+    n_img, c, host = _check_pack_pair("u8_ssim_images", a_pack, b_pack, ssim_ok)
     a, b = a_pack.arena, b_pack.arena
-    if a.dtype != torch.uint8 or b.dtype != torch.uint8:
-        raise ValueError(f"u8_ssim_images: expected uint8 arenas, got {a.dtype} and {b.dtype}")
-    host = tuple(tuple(int(v) for v in row) for row in a_pack.host_table)
-    if host != tuple(tuple(int(v) for v in row) for row in b_pack.host_table) or b_pack.c != c or a.numel() != b.numel():
-        raise ValueError("u8_ssim_images: the two packs must hold the same images (equal host tables, C and arena "
-                         "lengths)")
-    for i, (_, h, w) in enumerate(host):
-        if not ssim_ok(c, h, w):
-            raise ValueError(f"u8_ssim_images: image {i} needs both sides at least {SSIM_WINDOW} (got {h} x {w} x {c})")
-    if n_img > MAX_SSIM_IMAGES:
-        raise ValueError(f"u8_ssim_images: 1..{MAX_SSIM_IMAGES} images per call (got {n_img})")
-    _check_placed("u8_ssim_images", a_pack)
-    _check_placed("u8_ssim_images", b_pack)
-    if a.device != b.device:
-        raise ValueError("u8_ssim_images: the two packs must be on one device")
     out = torch.empty(n_img, dtype=torch.int64, device=a.device)
     _launch("u8_ssim_images", 2 * a.numel(), "grr_u8_ssim_images", a.data_ptr(), b.data_ptr(), a.numel(), c,
             a_pack.table.data_ptr(), n_img, max(h for _, h, _ in host), max(w for _, _, w in host), out.data_ptr(),
             _stream(a.device), flops=_ssim_flops(sum(ssim_count(c, h, w) for _, h, w in host)))
+    return [int(v) for v in out.tolist()]
+
+
+# ---------------------------------------------------------------------------
+# PSNR and SSIM on the luma of uint8 H x W x 3 images, channels R, G, B (csrc/metric_ops.hip; include/grr.h has the
+# definition): Y = Ny / LUMA_SCALE, Ny = 4080000 + 65481 R + 128553 G + 24966 B, the Y of ITU-R BT.601 "studio
+# range" YCbCr, not rounded.  u8_luma_sse returns S = sum (Ny(a) - Ny(b))^2, an exact Python int that can exceed 64
+# bits (the kernel returns it in two words); PSNR_Y = 10 log10(255^2 LUMA_SCALE^2 N / S) (restore.psnr_y_u8).
+# u8_luma_ssim returns sum q of the single plane Y over the luma_ssim_count(H, W) valid positions, as u8_ssim does
+# per channel.
+LUMA_SCALE = 255000
+LUMA_WEIGHTS = (65481, 128553, 24966)     # of R, G, B in Ny; their sum is 219000
+LUMA_SSIM_TILE = (32, 256)    # a workgroup's output rows and output pixel columns
+LUMA_SSE_BLOCK = (2048, 8)    # the pixels a workgroup and a lane take per step
+LUMA_SSE_MAX_BLOCKS = 1024    # workgroups of a single-image call: beyond them each strides over the image
+
+
+def luma_ok(h: int, w: int, need_window: bool = False) -> bool:
+    """grr_u8_luma_supported in plain Python (tests/test_luma_abi.py checks the two agree): both sides at least 1,
+    at least 11 where the SSIM window is needed, H W 3 < 2^31."""
+    least = SSIM_WINDOW if need_window else 1
+    return h >= least and w >= least and h * w * 3 < (1 << 31)
+
+
+def luma_ssim_count(h: int, w: int) -> int:
+    """N: the values the luma SSIM of an H x W x 3 image is the mean of."""
+    return (h - SSIM_WINDOW + 1) * (w - SSIM_WINDOW + 1)
+
+
+def _check_luma_pair(name: str, a, b, need_window: bool) -> Tuple[int, int]:
+    """(H, W) of two H x W x 3 uint8 device images of one shape; errors before any launch otherwise."""
+    for t in (a, b):
+        if not isinstance(t, Tensor) or t.dtype != torch.uint8 or t.dim() != 3:
+            raise ValueError(f"{name}: expected H x W x 3 uint8 tensors, got "
+                             f"{tuple(getattr(t, 'shape', ()))} {getattr(t, 'dtype', type(t))}")
+    h, w, c = a.shape
+    if c != 3:
+        raise ValueError(f"{name}: the luma is defined for H x W x 3 images (R, G, B), got {tuple(a.shape)}")
+    if a.shape != b.shape or not luma_ok(h, w, need_window):
+        raise ValueError(f"{name}: shapes {tuple(a.shape)} / {tuple(b.shape)} must match, with both sides at "
+                         f"least {SSIM_WINDOW if need_window else 1} and below 2^31 elements")
+    if not (a.is_cuda and b.is_cuda and a.device == b.device):
+        raise RuntimeError(f"{name}: tensors must be on one GPU; the HIP engine has no CPU path")
+    return h, w
+
+
+def _luma_sse_of(words) -> int:
+    """sum (D^2 mod 2^32) + (sum (D^2 >> 32) << 32)."""
+    return int(words[0]) + (int(words[1]) << 32)
+
+
+def u8_luma_sse(a: Tensor, b: Tensor) -> int:
+    """S = sum over the pixels of (Ny(a) - Ny(b))^2 of two H x W x 3 uint8 device images, exact (a Python int, up
+    to 82 bits; synchronises)."""
+    h, w = _check_luma_pair("u8_luma_sse", a, b, False)
+    a, b = a.contiguous(), b.contiguous()
+    out = torch.empty(2, dtype=torch.int64, device=a.device)
+    _launch("u8_luma_sse", 2 * a.numel(), "grr_u8_luma_sse", a.data_ptr(), b.data_ptr(), h, w, out.data_ptr(),
+            _stream(a.device))
+    return _luma_sse_of(out.tolist())
+
+
+def u8_luma_sse_images(a_pack, b_pack) -> List[int]:
+    """[u8_luma_sse of image i of the two packs for each i] in one launch: exact Python ints, one device-to-host
+    copy of the sums (synchronises).  The packs (restore.ImagePack: uint8 arenas, C = 3) describe the same images:
+    equal host tables, one device."""
+    n_img, _, host = _check_pack_pair("u8_luma_sse_images", a_pack, b_pack, lambda c, h, w: luma_ok(h, w), 3)
+    a, b = a_pack.arena, b_pack.arena
+    out = torch.empty((n_img, 2), dtype=torch.int64, device=a.device)
+    _launch("u8_luma_sse_images", 2 * a.numel(), "grr_u8_luma_sse_images", a.data_ptr(), b.data_ptr(), a.numel(),
+            a_pack.table.data_ptr(), n_img, out.data_ptr(), _stream(a.device))
+    return [_luma_sse_of(row) for row in out.tolist()]
+
+
+def u8_luma_ssim(a: Tensor, b: Tensor) -> int:
+    """sum of rint(2^32 s) over the valid pixels of the luma planes of two H x W x 3 uint8 device images, exact (a
+    Python int; synchronises).  Equal images give luma_ssim_count(H, W) << 32."""
+    h, w = _check_luma_pair("u8_luma_ssim", a, b, True)
+    a, b = a.contiguous(), b.contiguous()
+    out = torch.empty(1, dtype=torch.int64, device=a.device)
+    _launch("u8_luma_ssim", 2 * a.numel(), "grr_u8_luma_ssim", a.data_ptr(), b.data_ptr(), h, w, out.data_ptr(),
+            _stream(a.device), flops=_ssim_flops(luma_ssim_count(h, w)))
+    return int(out.item())
+
+
+def u8_luma_ssim_images(a_pack, b_pack) -> List[int]:
+    """[u8_luma_ssim of image i of the two packs for each i] in one launch: exact Python ints, one device-to-host
+    copy of the sums (synchronises).  Packs as for u8_luma_sse_images; every image has both sides at least 11."""
+    n_img, _, host = _check_pack_pair("u8_luma_ssim_images", a_pack, b_pack, lambda c, h, w: luma_ok(h, w, True), 3)
+    a, b = a_pack.arena, b_pack.arena
+    out = torch.empty(n_img, dtype=torch.int64, device=a.device)
+    _launch("u8_luma_ssim_images", 2 * a.numel(), "grr_u8_luma_ssim_images", a.data_ptr(), b.data_ptr(), a.numel(),
+            a_pack.table.data_ptr(), n_img, max(h for _, h, _ in host), max(w for _, _, w in host), out.data_ptr(),
+            _stream(a.device), flops=_ssim_flops(sum(luma_ssim_count(h, w) for _, h, w in host)))
     return [int(v) for v in out.tolist()]

@@ -460,7 +460,61 @@ def ssim_u8(a, b) -> float:
     return _ssim(kernels.u8_ssim(ta, tb), kernels.ssim_count(ta.shape[2], ta.shape[0], ta.shape[1]))
 
 
-METRICS = ("psnr", "ssim")
+def _psnr_y(sse: int, n: int) -> float:
+    """10 log10(255^2 LUMA_SCALE^2 n / sse) from the exact integer luma SSE over n pixels: one true division of
+    Python ints, the correctly rounded float64 of the exact quotient, then log10; inf for sse == 0."""
+    if sse == 0:
+        return float("inf")
+    return float(10.0 * np.log10((255 ** 2 * kernels.LUMA_SCALE ** 2 * n) / sse))
+
+
+def _luma_pair(who: str, a, b, need_window: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """_u8_pair for two H x W x 3 images; everything is checked on the host, before any copy or launch."""
+    for t in (a, b):
+        if not (isinstance(t, (np.ndarray, torch.Tensor)) and t.dtype in (np.uint8, torch.uint8)):
+            raise ValueError(f"{who}: expected uint8 images, got {getattr(t, 'dtype', type(t).__name__)}")
+    shape = tuple(a.shape)
+    if shape != tuple(b.shape):
+        raise ValueError(f"{who}: shapes differ ({shape} vs {tuple(b.shape)})")
+    if len(shape) != 3 or shape[2] != 3:
+        raise ValueError(f"{who}: the luma is defined for H x W x 3 images (R, G, B), got {shape}")
+    if not kernels.luma_ok(shape[0], shape[1], need_window):
+        raise ValueError(f"{who}: expected H x W x 3 images with both sides at least "
+                         f"{kernels.SSIM_WINDOW if need_window else 1} and below 2^31 elements, got {shape}")
+    return _u8_pair(who, a, b)
+
+
+def psnr_y_u8(a, b) -> float:
+    """PSNR on the Y channel of two uint8 H x W x 3 RGB images of one shape (numpy or tensor, host or device): Y of
+    ITU-R BT.601 "studio range" YCbCr as MATLAB's rgb2ycbcr and BasicSR's to_y_channel define it, not rounded to
+    uint8, Y = 16 + (65.481 R + 128.553 G + 24.966 B) / 255; 10 log10(255^2 N / sum (Ya - Yb)^2) from the exact
+    integer sum (kernels.u8_luma_sse), so it does not depend on any summation order; inf for equal images.
+    ValueError for an image that is not 3-channel."""
+    ta, tb = _luma_pair("psnr_y_u8", a, b, False)
+    return _psnr_y(kernels.u8_luma_sse(ta, tb), ta.shape[0] * ta.shape[1])
+
+
+def ssim_y_u8(a, b) -> float:
+    """ssim_u8's SSIM of the single plane Y (psnr_y_u8's luma, float64) of two uint8 H x W x 3 RGB images: the mean
+    over the (H - 10)(W - 10) valid positions, within 2^-32 of the float64 mean, the same on every run; exactly 1.0
+    for equal images.  ValueError for an image that is not 3-channel or has a side below 11."""
+    ta, tb = _luma_pair("ssim_y_u8", a, b, True)
+    return _ssim(kernels.u8_luma_ssim(ta, tb), kernels.luma_ssim_count(ta.shape[0], ta.shape[1]))
+
+
+METRICS = ("psnr", "ssim", "psnr_y", "ssim_y")
+_SCORE = {"psnr": psnr_u8, "ssim": ssim_u8, "psnr_y": psnr_y_u8, "ssim_y": ssim_y_u8}      # per image, by name
+
+
+def _check_metric_shape(who: str, what: str, shape, metrics) -> None:
+    """ValueError naming the image where a metric asked for has no value on an image of this shape."""
+    shape = tuple(shape)
+    window = "ssim" in metrics or "ssim_y" in metrics
+    if window and (len(shape) != 3 or min(shape[:2]) < kernels.SSIM_WINDOW):
+        raise ValueError(f"{who}: {what} is {shape}; SSIM needs an H x W x C image with both sides at "
+                         f"least {kernels.SSIM_WINDOW}")
+    if ("psnr_y" in metrics or "ssim_y" in metrics) and (len(shape) != 3 or shape[2] != 3):
+        raise ValueError(f"{who}: {what} is {shape}; the Y-channel metrics need an H x W x 3 image (R, G, B)")
 
 
 def _evaluate_args(who: str, model: Callable, ensemble, metrics, tiling_args: dict):
@@ -483,12 +537,9 @@ def _evaluate(who: str, model: Callable, images, sigma: float, factor: int, seed
     for.  The draws, the restorations and the launches of one metric do not depend on which others are asked
     for."""
     modes, metrics, device, tile, halo, micro_batch = _evaluate_args(who, model, ensemble, metrics, tiling_args)
-    if "ssim" in metrics:       # before any draw
+    if set(metrics) - {"psnr"}:       # before any draw
         for i in range(len(images)):
-            shape = np.shape(images[i])
-            if len(shape) != 3 or min(shape[:2]) < kernels.SSIM_WINDOW:
-                raise ValueError(f"{who}: image {i} is {tuple(shape)}; SSIM needs an H x W x C image with both sides at "
-                                 f"least {kernels.SSIM_WINDOW}")
+            _check_metric_shape(who, f"image {i}", np.shape(images[i]), metrics)
     rs = np.random.RandomState(seed=seed)
     if across_images:
         values = _evaluate_across(model, images, sigma, factor, rs, tile, halo, micro_batch, device, modes, metrics)
@@ -499,10 +550,8 @@ def _evaluate(who: str, model: Callable, images, sigma: float, factor: int, seed
             img, _ = _checked_image(_noisy(clean, sigma, rs))
             restored = _restore_device(model, img, device, factor, tile, halo, micro_batch, True, modes)
             clean_u8 = torch.from_numpy(_clean_u8(clean)).to(restored.device)
-            if "psnr" in metrics:
-                values["psnr"].append(psnr_u8(restored, clean_u8))
-            if "ssim" in metrics:
-                values["ssim"].append(ssim_u8(restored, clean_u8))
+            for m in metrics:
+                values[m].append(_SCORE[m](restored, clean_u8))
     return {m: (float(np.mean(values[m])), values[m]) for m in metrics}
 
 
@@ -524,8 +573,11 @@ def evaluate_metrics(model: Callable, images, sigma: float = 25.0, factor: int =
     """``evaluate`` for several metrics of the same restorations: {"psnr": (mean, per-image), "ssim": (mean,
     per-image)} for the names in ``metrics``.  The "psnr" entry is evaluate's result bit for bit (one body, the
     same draws); "ssim" is ssim_u8 of each restored image against rint(clean x 255).  With ``across_images`` the
-    SSIM of all images is one kernels.u8_ssim_images launch on the restored and the clean arena.  An unknown
-    metric name, and with "ssim" an image with a side below 11, is a ValueError before any draw."""
+    SSIM of all images is one kernels.u8_ssim_images launch on the restored and the clean arena.  "psnr_y" and
+    "ssim_y" are psnr_y_u8 and ssim_y_u8, the two on the Y channel of RGB images, with one
+    kernels.u8_luma_sse_images / u8_luma_ssim_images launch each across images; a metric's value does not depend on
+    which others are asked for.  An unknown metric name, with "ssim" or "ssim_y" an image with a side below 11 and
+    with a "_y" metric an image that is not 3-channel is a ValueError before any draw."""
     return _evaluate("evaluate_metrics", model, images, sigma, factor, seed, across_images, ensemble, metrics,
                      tiling_args)
 
@@ -555,6 +607,12 @@ def _score_packs(who: str, restored: ImagePack, clean_u8: ImagePack, metrics) ->
     if "ssim" in metrics:
         qs = kernels.u8_ssim_images(restored, clean_u8)
         values["ssim"] = [_ssim(q, kernels.ssim_count(restored.c, h, w)) for q, (_, h, w) in zip(qs, restored.host_table)]
+    if "psnr_y" in metrics:
+        sses = kernels.u8_luma_sse_images(restored, clean_u8)
+        values["psnr_y"] = [_psnr_y(sse, h * w) for sse, (_, h, w) in zip(sses, restored.host_table)]
+    if "ssim_y" in metrics:
+        qs = kernels.u8_luma_ssim_images(restored, clean_u8)
+        values["ssim_y"] = [_ssim(q, kernels.luma_ssim_count(h, w)) for q, (_, h, w) in zip(qs, restored.host_table)]
     return values
 
 
@@ -563,13 +621,15 @@ def evaluate_pairs(model: Callable, inputs, targets, factor: int = 16, across_im
     """Score ``model`` on degraded / clean picture pairs: inputs[i] and targets[i] are uint8 H x W x C images of
     one shape (numpy arrays or tensors, host or device).  Nothing is synthesised: each input goes to the device as
     uint8, is restored as ``restore_image(..., quantise=True)`` restores it, and the uint8 result is scored against
-    the target with the exact-integer kernels (psnr_u8, ssim_u8).  Returns {metric: (mean, per-image values)} for
-    the names in ``metrics``, as evaluate_metrics does.  tiling_args: tile, halo, micro_batch, device.
+    the target with the exact-integer kernels (psnr_u8, ssim_u8, psnr_y_u8, ssim_y_u8).  Returns {metric: (mean,
+    per-image values)} for the names in ``metrics``, as evaluate_metrics does.  tiling_args: tile, halo, micro_batch,
+    device.
 
     ``across_images``: the inputs are restored by restore_images' path in shared window batches and every metric of
     all images is one launch on the restored and the target arena; the same floats for a batch-independent model.
     ``ensemble`` as in restore_image, on either branch.  A length or shape mismatch, an image that is not uint8,
-    an unknown metric and, with "ssim", a side below 11 are ValueErrors before any launch."""
+    an unknown metric, with "ssim" or "ssim_y" a side below 11 and with "psnr_y" or "ssim_y" a pair that is not
+    3-channel are ValueErrors before any launch."""
     who = "evaluate_pairs"
     modes, metrics, device, tile, halo, micro_batch = _evaluate_args(who, model, ensemble, metrics, tiling_args)
     if len(inputs) != len(targets) or len(inputs) < 1:
@@ -588,9 +648,7 @@ def evaluate_pairs(model: Callable, inputs, targets, factor: int = 16, across_im
         if pair[0].shape != pair[1].shape:
             raise ValueError(f"{who}: input {i} is {tuple(pair[0].shape)} and its target {tuple(pair[1].shape)}: a "
                              "pair has one shape")
-        if "ssim" in metrics and min(pair[0].shape[:2]) < kernels.SSIM_WINDOW:
-            raise ValueError(f"{who}: pair {i} is {tuple(pair[0].shape)}; SSIM needs both sides at least "
-                             f"{kernels.SSIM_WINDOW}")
+        _check_metric_shape(who, f"pair {i}", pair[0].shape, metrics)
         plan(pair[0].shape[0], pair[0].shape[1], factor, tile, halo)        # raises what the restoration would
         pairs.append(pair)
     if device is None:
@@ -605,8 +663,6 @@ def evaluate_pairs(model: Callable, inputs, targets, factor: int = 16, across_im
         for img, target in pairs:
             restored = _restore_device(model, img, device, factor, tile, halo, micro_batch, True, modes)
             target = target.to(restored.device)
-            if "psnr" in metrics:
-                values["psnr"].append(psnr_u8(restored, target))
-            if "ssim" in metrics:
-                values["ssim"].append(ssim_u8(restored, target))
+            for m in metrics:
+                values[m].append(_SCORE[m](restored, target))
     return {m: (float(np.mean(values[m])), values[m]) for m in metrics}

@@ -652,22 +652,28 @@ def validate(model: nn.Module, images, sigma: float = 25.0, factor: int = 16, se
     return float(acc[0] / acc[1])
 
 
-def validate_pairs(model: nn.Module, pairs, factor: int = 16, device=None, **tiling_args) -> float:
+VAL_PAIR_METRICS = ("psnr", "psnr_y")
+
+
+def validate_pairs(model: nn.Module, pairs, factor: int = 16, device=None, metric: str = "psnr", **tiling_args) -> float:
     """Mean PSNR of ``model`` over degraded / clean pairs (``pairs[i]`` = (input, target), uint8 H x W x C, a
     TestPairsCSV for instance): restore.evaluate_pairs on this rank's share.  Nothing is drawn: each input is
-    restored as it is and scored against its target from the exact integer SSE.  tiling_args: tile, halo,
-    micro_batch, ensemble, across_images.
+    restored as it is and scored against its target from the exact integer SSE.  ``metric``: "psnr", or "psnr_y"
+    for the PSNR on the Y channel of RGB pairs (restore.psnr_y_u8), the number deraining and super-resolution
+    tables print.  tiling_args: tile, halo, micro_batch, ensemble, across_images.
 
     Several ranks: each takes sharding.shard_range's share of the pairs and the PSNR sum and count are all-reduced,
     as validate does."""
     from . import restore
+    if metric not in VAL_PAIR_METRICS:
+        raise ValueError(f"validate_pairs: metric is one of {VAL_PAIR_METRICS}, got {metric!r}")
     rank, world = sharding.world()
     if device is None:
         device = next(model.parameters()).device
     s, e = sharding.shard_range(len(pairs), rank, world)
     mine = [pairs[i] for i in range(s, e)]
     psnrs = restore.evaluate_pairs(model, [p[0] for p in mine], [p[1] for p in mine], factor=factor, device=device,
-                                   **tiling_args)["psnr"][1] if mine else []
+                                   metrics=(metric,), **tiling_args)[metric][1] if mine else []
     acc = torch.tensor([float(np.sum(psnrs)), float(len(psnrs))], dtype=torch.float64)
     if world > 1:
         if torch.distributed.get_backend() == "nccl":
@@ -678,7 +684,8 @@ def validate_pairs(model: nn.Module, pairs, factor: int = 16, device=None, **til
 
 def create_val_dataset(conf: dict):
     """``datasets.val`` of the YAML ({type, dataset_args, sigma, factor}), or None.  A paired set (TestPairsCSV)
-    takes {type, dataset_args, factor, tile, halo, micro_batch}: validate_pairs' arguments, no sigma."""
+    takes {type, dataset_args, factor, tile, halo, micro_batch, metric}: validate_pairs' arguments, no sigma; without
+    ``metric`` validate_pairs' default, the RGB PSNR, is scored."""
     vconf = conf.get("datasets", {}).get("val")
     if not vconf:
         return None, {}
@@ -687,6 +694,10 @@ def create_val_dataset(conf: dict):
         raise ValueError(f"Validation dataset {vconf['type']} is not found.")
     if cls is TestPairsCSV:
         args = {k: int(vconf[k]) for k in ("tile", "halo", "micro_batch") if vconf.get(k) is not None}
+        if vconf.get("metric") is not None:
+            if vconf["metric"] not in VAL_PAIR_METRICS:
+                raise ValueError(f"datasets.val.metric is one of {VAL_PAIR_METRICS}, got {vconf['metric']!r}")
+            args["metric"] = str(vconf["metric"])
         return cls(**vconf.get("dataset_args", {})), dict(args, factor=int(vconf.get("factor", 16)))
     return cls(**vconf.get("dataset_args", {})), {"sigma": float(vconf.get("sigma", 25.0)),
                                                    "factor": int(vconf.get("factor", 16))}

@@ -824,6 +824,45 @@ grr_status grr_u8_ssim(const uint8_t* a, const uint8_t* b, int H, int W, int C, 
 grr_status grr_u8_ssim_images(const uint8_t* a, const uint8_t* b, int64_t arena_elems, int C, const int64_t* img_table,
                               int n_img, int max_h, int max_w, int64_t* out, void* stream);
 
+/* ---- PSNR and SSIM on the luma of two uint8 H x W x 3 images, channels R, G, B interleaved (csrc/metric_ops.hip):
+ * the Y of ITU-R BT.601 "studio range" YCbCr, as MATLAB's rgb2ycbcr, skimage.color.rgb2ycbcr and BasicSR's
+ * to_y_channel define it, not rounded to uint8: Y = 16 + (65.481 R + 128.553 G + 24.966 B) / 255 = Ny / 255000 with
+ * the integer Ny = 4080000 + 65481 R + 128553 G + 24966 B <= 59 925 000, so Y lies in [16, 235].
+ *
+ * SSE: per pixel D = Ny(a) - Ny(b) = 65481 dR + 128553 dG + 24966 dB, an exact integer with |D| <= 55 845 000 < 2^26;
+ * S = sum D^2 over the N = H W pixels; PSNR_Y = 10 log10(255^2 255000^2 N / S).  D^2 < 2^52 and N < 2^30, so S can
+ * reach 2^82: the entry points return two words per image, out[0] = sum (D^2 mod 2^32) < 2^62 and
+ * out[1] = sum (D^2 >> 32) < 2^50, and S = out[0] + (out[1] << 32).  Integer adds throughout: exact, the same on
+ * every run and independent of the grid.
+ *
+ * SSIM: the index of the section above on the single plane Y, each Y the float64 double(Ny) / 255000.0 (the integer
+ * is exact, the division rounds once): the same taps, order, C1, C2, valid (H - 10)(W - 10) positions and
+ * quantisation; the entry points return sum q over those N positions, SSIM_Y = sum q / (2^32 N).  Equal images give
+ * exactly N 2^32.  No luma of a grey or RGBA image is defined: the entry points take 3 channels only. */
+
+/* 1 where the luma entry points take an H x W x 3 image: H, W >= 1 (need_window != 0, the SSIM: >= 11) and
+ * H W 3 < 2^31. */
+int grr_u8_luma_supported(int H, int W, int need_window);
+/* out[0], out[1] = the two words of S over the image pair a, b (HWC, C = 3, contiguous, any byte address); out: two
+ * 8-byte aligned uint64 on the device, overwritten.  GRR_ERR_UNSUPPORTED where grr_u8_luma_supported(H, W, 0)
+ * is 0. */
+grr_status grr_u8_luma_sse(const uint8_t* a, const uint8_t* b, int H, int W, uint64_t* out, void* stream);
+/* out[i][0], out[i][1] = the two words of S of image i of the arenas a and b, which share arena_elems and the image
+ * table (int64 [n_img, 3] on the device, 8-byte aligned, rows (element offset, H, W)), all images of 3 channels, in
+ * one launch.  The table is clamped -- offset into [0, arena_elems), H and W into [1, 2^31), the pixel count to
+ * what the arena holds from the offset on -- so a bad table gives wrong sums, never an access outside the arenas.
+ * out: n_img x 2 8-byte aligned uint64 on the device, overwritten.  n_img <= 65535 (one grid row per image), else
+ * GRR_ERR_UNSUPPORTED. */
+grr_status grr_u8_luma_sse_images(const uint8_t* a, const uint8_t* b, int64_t arena_elems, const int64_t* img_table,
+                                  int n_img, uint64_t* out, void* stream);
+/* *out = sum q of the luma planes of the image pair a, b; out: one 8-byte aligned int64 on the device, overwritten.
+ * GRR_ERR_UNSUPPORTED where grr_u8_luma_supported(H, W, 1) is 0. */
+grr_status grr_u8_luma_ssim(const uint8_t* a, const uint8_t* b, int H, int W, int64_t* out, void* stream);
+/* out[i] = sum q of the luma planes of image i of the arenas a and b: grr_u8_ssim_images' arguments, clamping and
+ * limits with C = 3 understood. */
+grr_status grr_u8_luma_ssim_images(const uint8_t* a, const uint8_t* b, int64_t arena_elems, const int64_t* img_table,
+                                   int n_img, int max_h, int max_w, int64_t* out, void* stream);
+
 /* ---- training batches cut from an arena of uint8 images (training.DevicePatchLoader; the reference's
  * lib/dataloader_v2.py:ImageSuperResolution does this per sample on the host).  arena, arena_elems, C, img_table,
  * n_img: as grr_tiles_gather takes them, uint8 only.  table: int32 [n, 4] on the device, rows (img, row, col,

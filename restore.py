@@ -1,7 +1,8 @@
 """Restore image files with a trained model (irdu_amd.restore; single process, one GPU).
 
     python restore.py -yaml_path CONF.yaml --ckpt CHECKPOINT.pt --input FILE_OR_DIR --output DIR \\
-           [--sigma S --seed N [--ssim] | --reference DIR [--ssim]] [--tile T --halo H --factor F] [--batch-images]
+           [--sigma S --seed N [--ssim] [--y-channel] | --reference DIR [--ssim] [--y-channel]]
+           [--tile T --halo H --factor F] [--batch-images]
            [--self-ensemble | --ensemble-modes 0,1,4,5]
 
 The model is ``training.build_model(conf["model"])``; the checkpoint is the training loop's dict (its
@@ -21,7 +22,11 @@ reference (``irdu_amd.ssim_u8``: 11 x 11 Gaussian window, both sides at least 11
 the mean PSNR.  With --reference DIR (not with --sigma) the inputs are degraded pictures that have a ground truth:
 each is restored as it is and scored against the file of the same stem in DIR, which must have the input's size
 and channels; PSNR per file and the mean are printed as with --sigma.  A reference that is missing, ambiguous or of
-another size is reported before anything runs.  It works with --batch-images and the ensemble options.
+another size is reported before anything runs.  It works with --batch-images and the ensemble options.  With
+--y-channel (with --sigma or --reference; RGB files and a 3-channel model) the scores are taken on the Y channel of
+YCbCr, as the tables of deraining, deblurring and super-resolution papers are: ITU-R BT.601 luma in [16, 235], not
+rounded (MATLAB's rgb2ycbcr, BasicSR's test_y_channel; ``irdu_amd.psnr_y_u8`` / ``ssim_y_u8``).  The lines then read
+PSNR-Y and SSIM-Y in place of PSNR and SSIM; the files written are the same.
 """
 import argparse
 import os
@@ -86,6 +91,9 @@ def parse_args(argv=None):
                              "stem in DIR")
     ap.add_argument("--seed", type=int, default=2204)
     ap.add_argument("--ssim", action="store_true", help="with --sigma or --reference: report the SSIM beside the PSNR")
+    ap.add_argument("--y-channel", action="store_true",
+                    help="with --sigma or --reference: score on the Y channel of YCbCr (BT.601 luma of RGB images): "
+                         "PSNR-Y, and with --ssim SSIM-Y, in place of the RGB values")
     ap.add_argument("--tile", type=int, default=None)
     ap.add_argument("--halo", type=int, default=None)
     ap.add_argument("--factor", type=int, default=16)
@@ -99,6 +107,8 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.ssim and args.sigma is None and args.reference is None:
         ap.error("--ssim needs --sigma or --reference: there is nothing to compare a restored image with otherwise")
+    if args.y_channel and args.sigma is None and args.reference is None:
+        ap.error("--y-channel needs --sigma or --reference: there is nothing to compare a restored image with otherwise")
     args.ensemble = 8 if args.self_ensemble else 1
     if args.ensemble_modes is not None:
         try:
@@ -129,6 +139,17 @@ def main(argv=None) -> None:
         check_references(files, found)
         refs = dict(zip(files, found))
     conf = training.parse_options(args.yaml_path)
+    if args.y_channel:      # before anything runs
+        model_args = conf.get("model", {}).get("args", {})
+        for key in ("n_channels_in", "n_channels_out"):
+            if model_args.get(key) is not None and int(model_args[key]) != 3:
+                raise SystemExit(f"--y-channel: the model of {args.yaml_path} has {key} {model_args[key]}; the Y channel "
+                                 "is defined for 3-channel (RGB) models")
+        for path in files:
+            with Image.open(path) as im:
+                if len(im.getbands()) != 3:
+                    raise SystemExit(f"--y-channel: {path} has {len(im.getbands())} channel(s) ({im.mode}); the Y "
+                                     "channel is defined for 3-channel (RGB) images")
     if not torch.cuda.is_available():
         raise SystemExit("restore.py needs a GPU: the HIP engine has no CPU path")
     irdu_amd.load_native()
@@ -144,6 +165,8 @@ def main(argv=None) -> None:
     os.makedirs(args.output, exist_ok=True)
     rs = np.random.RandomState(seed=args.seed)
     psnrs, ssims = [], []
+    psnr_of, ssim_of, tag = ((irdu_amd.psnr_y_u8, irdu_amd.ssim_y_u8, "-Y") if args.y_channel else
+                             (irdu_amd.psnr_u8, irdu_amd.ssim_u8, ""))
 
     def read(path):
         img = np.array(Image.open(path))
@@ -166,15 +189,18 @@ def main(argv=None) -> None:
             truth = img if args.reference is None else read(refs[path])
             if truth.shape != out.shape:
                 raise SystemExit(f"--reference: {refs[path]} decodes to {truth.shape}, the restored {path} is {out.shape}")
-            psnrs.append(irdu_amd.psnr_u8(out, truth))
+            try:
+                psnrs.append(psnr_of(out, truth))
+            except ValueError as e:
+                raise SystemExit(f"{path}: {e}")
             against = f"sigma {args.sigma:g}" if args.reference is None else f"reference {refs[path]}"
-            line = f"{path} -> {out_path}  {against}  PSNR {psnrs[-1]:.4f} dB"
+            line = f"{path} -> {out_path}  {against}  PSNR{tag} {psnrs[-1]:.4f} dB"
             if args.ssim:
                 try:
-                    ssims.append(irdu_amd.ssim_u8(out, truth))
+                    ssims.append(ssim_of(out, truth))
                 except ValueError as e:
                     raise SystemExit(f"{path}: {e}")
-                line += f"  SSIM {ssims[-1]:.4f}"
+                line += f"  SSIM{tag} {ssims[-1]:.4f}"
             print(line)
         Image.fromarray(out[:, :, 0] if out.shape[2] == 1 else out).save(out_path)
 
@@ -194,9 +220,9 @@ def main(argv=None) -> None:
                                          tile=tile, halo=halo, ensemble=ensemble)
             finish(path, img, out)
     if psnrs:
-        print(f"mean PSNR over {len(psnrs)} image(s): {float(np.mean(psnrs)):.4f} dB")
+        print(f"mean PSNR{tag} over {len(psnrs)} image(s): {float(np.mean(psnrs)):.4f} dB")
     if ssims:
-        print(f"mean SSIM over {len(ssims)} image(s): {float(np.mean(ssims)):.4f}")
+        print(f"mean SSIM{tag} over {len(ssims)} image(s): {float(np.mean(ssims)):.4f}")
 
 
 if __name__ == "__main__":
