@@ -21,7 +21,15 @@ sigma 25/255, device events around runs of 200 launches on preallocated outputs,
 One JSON line ("bench": "pair_kernel") with each kernel's median, fastest and slowest round in microseconds per
 launch.
 
-    python bench_data.py [--paired | --pair-kernel] [--steps 60] [--warmup 10] [--images 12] [--side 1200] [--workers 4] [--files 8600]
+With --bicubic S only the synthesis of a bicubic super-resolution training set's degraded pictures is timed, on the
+same synthetic pictures held in memory (no files, no model): "device" is kernels.u8_bicubic_degrade_images on the clean
+arena (two launches: down into a low-resolution arena, up into the degraded one), device events around each of 20
+rounds after a warm-up; "host" is the alternative the loader would otherwise run serially as it decodes, Pillow's
+resize(BICUBIC) down and back up of every picture, one wall-clock pass.  One JSON line ("bench": "bicubic") with both,
+the two kernels' algorithmic bytes (each input byte read once, each output byte written once) over the device time,
+and grr_stream_copy's rate on a buffer of the arena's size in the same process for scale.
+
+    python bench_data.py [--paired | --pair-kernel | --bicubic S] [--steps 60] [--warmup 10] [--images 12] [--side 1200] [--workers 4] [--files 8600]
 """
 from __future__ import annotations
 
@@ -141,6 +149,69 @@ def pair_kernel(rounds: int = 15, launches: int = 200) -> None:
     print(json.dumps(line), flush=True)
 
 
+def synthetic_pictures(n: int, side: int, seed: int = 7):
+    """write_pictures' pictures as arrays: n RGB pictures, side x (side + 64) and every third one 640 x 720."""
+    rs = np.random.RandomState(seed)
+    pics = []
+    for k in range(n):
+        h, w = (side, side + 64) if k % 3 else (640, 720)
+        yy, xx = np.mgrid[0:h, 0:w]
+        base = np.stack([(yy * (k + 1) + xx * 2) % 256, (yy + xx * (k + 2)) % 256, (yy * 3 + xx) % 256], axis=2)
+        pics.append(np.clip(base * 0.6 + rs.randint(0, 103, size=(h, w, 3)), 0, 255).astype(np.uint8))
+    return pics
+
+
+def bicubic(scale: int, images: int, side: int, rounds: int = 20) -> None:
+    from PIL import Image
+    import irdu_amd
+    irdu_amd.load_native()
+    from irdu_amd import _native, kernels, restore
+    dev = torch.device("cuda:0")
+    pics = synthetic_pictures(images, side)
+    pack = restore.pack_images(pics, dev)
+    low = kernels.u8_resize_images(pack, scale, False)                      # also the warm-up of both directions
+    degraded = kernels.u8_bicubic_degrade_images(pack, scale)
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(rounds):
+        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        start.record()
+        kernels.u8_bicubic_degrade_images(pack, scale)
+        end.record()
+        torch.cuda.synchronize()
+        ms.append(start.elapsed_time(end))
+    # the float4 copy at the arena's size, for scale: bytes read plus bytes written over its time
+    n_floats = pack.arena.numel() // 4
+    a = torch.empty(n_floats, dtype=torch.float32, device=dev)
+    b = torch.empty_like(a)
+    stream = torch.cuda.current_stream().cuda_stream
+    copy_ms = []
+    for r in range(rounds + 1):
+        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        start.record()
+        _native.call("grr_stream_copy", b.data_ptr(), a.data_ptr(), n_floats, stream)
+        end.record()
+        torch.cuda.synchronize()
+        if r:
+            copy_ms.append(start.elapsed_time(end))
+    assert degraded.host_table == pack.host_table
+    t0 = time.perf_counter()
+    for pic in pics:
+        im = Image.fromarray(pic)
+        small = im.resize((-(-im.width // scale), -(-im.height // scale)), Image.BICUBIC)
+        np.asarray(small.resize(im.size, Image.BICUBIC))
+    host_s = time.perf_counter() - t0
+    # down reads the clean arena and writes the low one; up reads the low one and writes the degraded one
+    nbytes = 2 * pack.arena.numel() + 2 * low.arena.numel()
+    med = float(np.median(ms))
+    print(json.dumps({"bench": "bicubic", "scale": scale, "images": images, "arena_mb": round(pack.arena.numel() / 2 ** 20, 1),
+                      "low_mb": round(low.arena.numel() / 2 ** 20, 2), "rounds": rounds,
+                      "device_ms": {"median": round(med, 3), "min": round(min(ms), 3), "max": round(max(ms), 3)},
+                      "device_gbps": round(nbytes / med / 1e6, 1),
+                      "stream_copy_gbps": round(8 * n_floats / float(np.median(copy_ms)) / 1e6, 1),
+                      "host_pillow_s": round(host_s, 3), "host_over_device": round(host_s * 1e3 / med, 1)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     # the DataLoader's workers hold up to 2 batches each in flight when the clock starts: enough timed batches
@@ -158,9 +229,14 @@ def main():
                     help="degraded / clean file pairs: PairedImageRestoration on both paths (no many-files run)")
     ap.add_argument("--pair-kernel", action="store_true",
                     help="only time grr_patch_pair_batch (no sigma) against grr_patch_batch (sigma > 0) on one shape")
+    ap.add_argument("--bicubic", type=int, default=None, metavar="S",
+                    help="only time the synthesis of the degraded pictures at scale S: the device kernels against "
+                         "Pillow's resize down and up on the host")
     args = ap.parse_args()
     if args.pair_kernel:
         return pair_kernel()
+    if args.bicubic is not None:
+        return bicubic(args.bicubic, args.images, args.side)
     import irdu_amd
     irdu_amd.load_native()
     from irdu_amd import kernels, training

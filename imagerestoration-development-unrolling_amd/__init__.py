@@ -46,5 +46,7 @@ from .restore import evaluate_metrics, ssim_u8  # noqa: F401  (SSIM beside the P
 from .restore import psnr_y_u8, ssim_y_u8  # noqa: F401  (the two on the Y channel of RGB images)
 from .training import PairedImageRestoration  # noqa: F401  (degraded / clean file pairs)
 from .restore import evaluate_pairs  # noqa: F401
+from .training import BicubicSuperResolution  # noqa: F401  (bicubic super-resolution pairs made from clean files)
+from .restore import bicubic_degrade_u8, bicubic_down_u8, bicubic_up_u8, evaluate_sr  # noqa: F401
 
 __version__ = "0.1.0"

@@ -191,6 +191,10 @@ SIGNATURES = {
     # ... from a degraded and a clean arena under one image table (training.PairedImageRestoration)
     "grr_patch_pair_batch_supported": [I, I, L, I, I, I],
     "grr_patch_pair_batch": [P, P, L, I, P, I, P, P, P, I, ctypes.c_uint64, I, I, P, P, P],
+    # exact bicubic resize of uint8 images by an integer scale (resize_ops.hip); the tap tables are host arrays
+    "grr_u8_resize_supported": [I, I, I, I, I],
+    "grr_u8_resize": [P, I, I, I, P, I, I, I, I, I, P, P, P, P],
+    "grr_u8_resize_images": [P, L, P, P, L, P, I, I, I, I, I, I, I, P, P, P, P],
 }
 _RESTYPES = {"grr_version": c_int, "grr_last_error": ctypes.c_char_p, "grr_lnb_workspace_bytes": c_int64,
              "grr_conv1x1_workspace_bytes": c_int64, "grr_wgrad_workspace_bytes": c_int64,

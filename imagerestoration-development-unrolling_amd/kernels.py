@@ -2406,3 +2406,185 @@ def u8_luma_ssim_images(a_pack, b_pack) -> List[int]:
             a_pack.table.data_ptr(), n_img, max(h for _, h, _ in host), max(w for _, _, w in host), out.data_ptr(),
             _stream(a.device), flops=_ssim_flops(sum(luma_ssim_count(h, w) for _, h, w in host)))
     return [int(v) for v in out.tolist()]
+
+
+# ---------------------------------------------------------------------------
+# Exact bicubic resize of uint8 images by an integer scale (csrc/resize_ops.hip; include/grr.h has the definition):
+# MATLAB imresize's convention with fixed-point weights, every tap set summing to 2^30.  The tap sets are computed
+# here from exact rationals and handed to the library as host arrays, as the mode lists above are.
+RESIZE_SCALES = (2, 8)        # the smallest and the largest scale
+RESIZE_ONE = 1 << 30          # the sum of a tap set
+RESIZE_TILE = 32              # a workgroup's output rows and columns
+MAX_RESIZE_IMAGES = 65535     # grr_u8_resize_images: one grid row per image
+
+
+def _cubic(x):
+    from fractions import Fraction
+    x = abs(x)
+    if x <= 1:
+        return Fraction(3, 2) * x ** 3 - Fraction(5, 2) * x ** 2 + 1
+    if x < 2:
+        return Fraction(-1, 2) * x ** 3 + Fraction(5, 2) * x ** 2 - 4 * x + 2
+    return Fraction(0)
+
+
+_RESIZE_TAPS = {}
+
+
+def resize_taps(s: int, up: bool) -> tuple:
+    """The quantised tap sets of scale ``s``: a tuple of phases -- one for down, whose offsets count from i s; s for
+    up, phase p = y mod s, whose offsets count from y // s -- each a tuple of (offset, q) pairs with
+    sum q = 2^30 and the zero taps dropped (8 / 9 / 16 / 32 taps down for s = 2 / 3 / 4 / 8, at most 4 up).
+    Exact: the raw weights are Fractions, normalised by their sum, rounded half to even at 2^-30, and the remainder
+    goes to the largest tap (the lowest index among equals).  Cached."""
+    from fractions import Fraction
+    key = (int(s), bool(up))
+    if key not in _RESIZE_TAPS:
+        s = key[0]
+        if not RESIZE_SCALES[0] <= s <= RESIZE_SCALES[1]:
+            raise ValueError(f"resize_taps: the scale is an integer of {RESIZE_SCALES[0]}..{RESIZE_SCALES[1]}, got {s}")
+        sets = []
+        for p in range(s if key[1] else 1):
+            if key[1]:
+                u, reach, width = Fraction(2 * p + 1, 2 * s) - Fraction(1, 2), 2, 1
+            else:
+                u, reach, width = Fraction(s - 1, 2), 2 * s, s
+            offsets = [j for j in range(-3 * width, 4 * width) if abs(u - j) < reach]
+            raw = [_cubic((u - j) / width) for j in offsets]
+            total = sum(raw)
+            q = [round(w / total * RESIZE_ONE) for w in raw]         # Fraction.__round__: half to even
+            q[q.index(max(q))] += RESIZE_ONE - sum(q)
+            sets.append(tuple((o, v) for o, v in zip(offsets, q) if v))
+        _RESIZE_TAPS[key] = tuple(sets)
+    return _RESIZE_TAPS[key]
+
+
+_RESIZE_TAP_ARGS = {}
+
+
+def _resize_tap_args(s: int, up: bool) -> tuple:
+    """(n_phase, first, count, taps) as the entry points take them: per phase a run of consecutive offsets from its
+    first tap to its last, a dropped zero in between passed as 0.  The ctypes arrays are cached (and so alive)."""
+    key = (int(s), bool(up))
+    if key not in _RESIZE_TAP_ARGS:
+        first, count, flat = [], [], []
+        for phase in resize_taps(*key):
+            by_offset = dict(phase)
+            lo, hi = min(by_offset), max(by_offset)
+            first.append(lo)
+            count.append(hi - lo + 1)
+            flat.extend(by_offset.get(o, 0) for o in range(lo, hi + 1))
+        arr = lambda v: (ctypes.c_int32 * len(v))(*v)
+        _RESIZE_TAP_ARGS[key] = (len(first), arr(first), arr(count), arr(flat))
+    return _RESIZE_TAP_ARGS[key]
+
+
+def resize_ok(c: int, h: int, w: int, s: int, up) -> bool:
+    """grr_u8_resize_supported in plain Python (tests/test_resize_abi.py checks the two agree): 1 <= C <= 4,
+    2 <= s <= 8, sides >= 1, and the input's and the output's element counts (down: ceil(H / s) ceil(W / s) C, up:
+    s H s W C) below 2^31."""
+    if not (1 <= c <= 4 and RESIZE_SCALES[0] <= s <= RESIZE_SCALES[1] and h >= 1 and w >= 1):
+        return False
+    out = s * h * s * w if up else -(-h // s) * -(-w // s)
+    return h * w * c < (1 << 31) and out * c < (1 << 31)
+
+
+def resize_out_hw(name: str, h: int, w: int, s: int, up, out_hw=None) -> Tuple[int, int]:
+    """The output sides of an h x w image: down ceil(h / s) x ceil(w / s); up s h x s w, or ``out_hw`` where each
+    side n of it has s (n_in - 1) < n <= s n_in.  ValueError otherwise."""
+    if not up:
+        want = (-(-h // s), -(-w // s))
+        if out_hw is not None and tuple(int(v) for v in out_hw) != want:
+            raise ValueError(f"{name}: {h} x {w} at scale {s} shrinks to {want[0]} x {want[1]}, got {tuple(out_hw)}")
+        return want
+    if out_hw is None:
+        return s * h, s * w
+    ho, wo = (int(v) for v in out_hw)
+    if not (s * (h - 1) < ho <= s * h and s * (w - 1) < wo <= s * w):
+        raise ValueError(f"{name}: {h} x {w} at scale {s} grows to sides in (s (n - 1), s n], got {ho} x {wo}")
+    return ho, wo
+
+
+def _check_scale(name: str, s) -> int:
+    if isinstance(s, bool) or not isinstance(s, int) or not RESIZE_SCALES[0] <= s <= RESIZE_SCALES[1]:
+        raise ValueError(f"{name}: the scale is an integer of {RESIZE_SCALES[0]}..{RESIZE_SCALES[1]}, got {s!r}")
+    return s
+
+
+def _resize_bytes(shapes, out_shapes, c: int) -> int:
+    """Algorithmic bytes of a resize: every input byte read once and every output byte written once."""
+    return sum(h * w * c for h, w in shapes) + sum(h * w * c for h, w in out_shapes)
+
+
+def u8_resize(img: Tensor, s: int, up, out_hw=None) -> Tensor:
+    """The exact bicubic resize of an H x W x C uint8 device image (include/grr.h): ``up`` false shrinks it to
+    ceil(H / s) x ceil(W / s) with the antialiased kernel, ``up`` true grows it to s H x s W, or to ``out_hw`` with
+    s (n - 1) < side <= s n (the size a down pass came from).  Rows first, then columns, rounded to uint8 after
+    each; both in one launch.  A non-contiguous image is copied first."""
+    name = "u8_resize"
+    s, up = _check_scale(name, s), bool(up)
+    if isinstance(img, Tensor) and img.dtype != torch.uint8:
+        raise ValueError(f"{name}: the image must be uint8, got {img.dtype}")
+    h, w, c = _check_image(name, img)
+    ho, wo = resize_out_hw(name, h, w, s, up, out_hw)
+    if not resize_ok(c, h, w, s, up):
+        raise ValueError(f"{name}: needs fewer than 2^31 input and output elements, got {tuple(img.shape)} at scale {s}")
+    img = img.contiguous()
+    out = torch.empty((ho, wo, c), dtype=torch.uint8, device=img.device)
+    _launch("u8_resize", _resize_bytes([(h, w)], [(ho, wo)], c), "grr_u8_resize", img.data_ptr(), h, w, c,
+            out.data_ptr(), ho, wo, s, int(up), *_resize_tap_args(s, up), _stream(img.device))
+    return out
+
+
+def u8_resize_images(pack, s: int, up, out_shapes=None):
+    """u8_resize of every image of a uint8 image pack into a new pack (a restore.ImagePack of the resized sizes,
+    the images back to back), one launch per 65535 images.  ``out_shapes``: with ``up``, the (h, w) each image
+    grows to (default: s H x s W)."""
+    from .restore import ImagePack, _host_table
+    name = "u8_resize_images"
+    s, up = _check_scale(name, s), bool(up)
+    n_img, c = _check_pack(name, pack)
+    if pack.arena.dtype != torch.uint8:
+        raise ValueError(f"{name}: the arena must be uint8, got {pack.arena.dtype}")
+    shapes = [(int(h), int(w)) for _, h, w in pack.host_table]
+    if out_shapes is not None and len(out_shapes) != n_img:
+        raise ValueError(f"{name}: {len(out_shapes)} output shapes for {n_img} images")
+    outs = []
+    for i, (h, w) in enumerate(shapes):
+        try:
+            outs.append(resize_out_hw(name, h, w, s, up, None if out_shapes is None else out_shapes[i]))
+        except ValueError as e:
+            raise ValueError(f"{e} (image {i})") from None
+        if not resize_ok(c, h, w, s, up):
+            raise ValueError(f"{name}: image {i} needs fewer than 2^31 input and output elements, got {h} x {w} x {c} "
+                             f"at scale {s}")
+    host_table, total = _host_table(outs, c)
+    dev = pack.arena.device
+    arena = torch.empty(total, dtype=torch.uint8, device=dev)
+    table = torch.tensor(host_table, dtype=torch.int64).to(dev)
+    taps = _resize_tap_args(s, up)
+    for at in range(0, n_img, MAX_RESIZE_IMAGES):
+        n = min(MAX_RESIZE_IMAGES, n_img - at)
+        part = outs[at:at + n]
+        _launch("u8_resize_images", _resize_bytes(shapes[at:at + n], part, c), "grr_u8_resize_images",
+                pack.arena.data_ptr(), pack.arena.numel(), pack.table.data_ptr() + at * 24, arena.data_ptr(), total,
+                table.data_ptr() + at * 24, c, n, max(h for h, _ in part), max(w for _, w in part), s, int(up), *taps,
+                _stream(dev))
+    return ImagePack(arena, table, host_table, c, tuple(getattr(pack, "kinds", ())))
+
+
+def u8_bicubic_degrade(img: Tensor, s: int) -> Tensor:
+    """The bicubic super-resolution input of an H x W x C uint8 device image, at its size: u8_resize down by ``s``,
+    then up to H x W.  Two launches; the low-resolution image between them is the only other buffer."""
+    h, w = int(img.shape[0]), int(img.shape[1])
+    return u8_resize(u8_resize(img, s, False), s, True, (h, w))
+
+
+def u8_bicubic_degrade_images(pack, s: int):
+    """u8_bicubic_degrade of every image of a uint8 pack, the results back to back.  Where ``pack``'s images lie back
+    to back as well (as pack_images lays them) the result has its host table and shares its device image table, so
+    the two can form a patch_pair_source.  Two launches per 65535 images."""
+    low = u8_resize_images(pack, s, False)
+    out = u8_resize_images(low, s, True, [(h, w) for _, h, w in pack.host_table])
+    same = out.host_table == tuple(tuple(int(v) for v in row) for row in pack.host_table)
+    return type(out)(out.arena, pack.table, out.host_table, out.c, out.kinds) if same else out

@@ -48,6 +48,11 @@ pixel on the device).  ``evaluate`` returns the PSNRs, ``evaluate_metrics`` both
 ``evaluate_pairs`` scores degraded / clean pairs of uint8 pictures with the same kernels and synthesises nothing:
 each input is restored as it is and compared with its target.
 
+Bicubic super-resolution: ``bicubic_down_u8`` / ``bicubic_up_u8`` / ``bicubic_degrade_u8`` resize uint8 pictures by an
+integer scale on the device with the exact fixed-point bicubic of include/grr.h (``kernels.u8_resize``), and
+``evaluate_sr`` runs the protocol of the super-resolution tables on clean pictures: mod-crop, degrade, restore, shave,
+score.  The filter stays same-size-in, same-size-out: its input is the picture brought back to size by the bicubic.
+
 Single process: several ranks are ``tiling.tiled_forward``'s business.
 """
 from __future__ import annotations
@@ -614,6 +619,97 @@ def _score_packs(who: str, restored: ImagePack, clean_u8: ImagePack, metrics) ->
         qs = kernels.u8_luma_ssim_images(restored, clean_u8)
         values["ssim_y"] = [_ssim(q, kernels.luma_ssim_count(h, w)) for q, (_, h, w) in zip(qs, restored.host_table)]
     return values
+
+
+def _resized_u8(who: str, a, resize):
+    """``resize`` (device uint8 H x W x C -> device uint8) of a uint8 picture, numpy array or tensor, host or device;
+    the result is of the input's kind and, for a tensor, on its device."""
+    try:
+        t, kind = _checked_image(a)
+    except ValueError as e:
+        raise ValueError(f"{who}: {e}") from None
+    if t.dtype != torch.uint8:
+        raise ValueError(f"{who}: expected a uint8 picture, got {t.dtype}")
+    out = resize(_to_device(t, None))
+    if kind == "numpy":
+        return out.cpu().numpy()
+    return out.cpu() if kind == "cpu" else out
+
+
+def bicubic_down_u8(a, s: int):
+    """The uint8 H x W x C picture ``a`` (numpy array or tensor) shrunk to ceil(H / s) x ceil(W / s) by the exact
+    antialiased bicubic (kernels.u8_resize; include/grr.h has the definition), on the GPU."""
+    return _resized_u8("bicubic_down_u8", a, lambda t: kernels.u8_resize(t, s, False))
+
+
+def bicubic_up_u8(a, s: int, h: int = None, w: int = None):
+    """``a`` grown to s H x s W by the exact bicubic, or to h x w with s (H - 1) < h <= s H and likewise w (the
+    size a bicubic_down_u8 came from), on the GPU."""
+    s = kernels._check_scale("bicubic_up_u8", s)
+    return _resized_u8("bicubic_up_u8", a, lambda t: kernels.u8_resize(
+        t, s, True, (s * t.shape[0] if h is None else h, s * t.shape[1] if w is None else w)))
+
+
+def bicubic_degrade_u8(a, s: int):
+    """The bicubic super-resolution input of ``a`` at its own size: bicubic_up_u8(bicubic_down_u8(a, s), s, H, W),
+    without the round trip to the host (kernels.u8_bicubic_degrade).  training.bicubic_degrade_u8 gives the same
+    bytes on the CPU."""
+    return _resized_u8("bicubic_degrade_u8", a, lambda t: kernels.u8_bicubic_degrade(t, s))
+
+
+def evaluate_sr(model: Callable, images, scale: int, shave: int = None, factor: int = 16, ensemble=1,
+                metrics=("psnr_y", "ssim_y"), **tiling_args) -> dict:
+    """Score ``model`` on the bicubic super-resolution protocol (Set5 / Set14 / B100 style) over clean uint8
+    H x W x C pictures (numpy arrays or tensors, host or device).  Per picture: mod-crop it to multiples of ``scale``
+    (top-left), degrade it on the device (kernels.u8_bicubic_degrade: the exact antialiased bicubic down and the
+    bicubic back up), restore the degraded picture as ``restore_image(..., quantise=True)`` does, cut ``shave``
+    (default ``scale``) pixels from each side of the restored and the clean picture and score them with the
+    exact-integer kernels.  Returns {metric: (mean, per-image values)} as evaluate_pairs does; with ``shave=0`` on
+    pictures that need no mod-crop it is evaluate_pairs(model, degraded, clean) bit for bit.  tiling_args: tile,
+    halo, micro_batch, device; ``ensemble`` as in restore_image.
+
+    Everything is checked before any launch: the scale (2..8), the shave, uint8 pictures, a picture smaller than
+    ``scale`` or than the shave leaves, and what the metrics need of the shaved picture (SSIM: both sides at least
+    11; the Y-channel metrics: 3 channels)."""
+    who = "evaluate_sr"
+    modes, metrics, device, tile, halo, micro_batch = _evaluate_args(who, model, ensemble, metrics, tiling_args)
+    scale = kernels._check_scale(who, scale)
+    shave = scale if shave is None else shave
+    if isinstance(shave, bool) or not isinstance(shave, int) or shave < 0:
+        raise ValueError(f"{who}: shave is a non-negative integer, got {shave!r}")
+    if len(images) < 1:
+        raise ValueError(f"{who}: no images")
+    cleans = []
+    for i in range(len(images)):
+        try:
+            t, _ = _checked_image(images[i])
+        except ValueError as e:
+            raise ValueError(f"{who}: image {i}: {e}") from None
+        if t.dtype != torch.uint8:
+            raise ValueError(f"{who}: image {i} is {t.dtype}; the protocol is defined on uint8 pictures")
+        h, w = t.shape[0] // scale * scale, t.shape[1] // scale * scale
+        if min(h, w) < 1 or min(h, w) <= 2 * shave:
+            raise ValueError(f"{who}: image {i} is {tuple(t.shape)}: nothing is left after the crop to multiples of "
+                             f"{scale} and a shave of {shave}")
+        _check_metric_shape(who, f"image {i} after the shave", (h - 2 * shave, w - 2 * shave, t.shape[2]), metrics)
+        plan(h, w, factor, tile, halo)                          # raises what the restoration would
+        cleans.append(t[:h, :w])
+    if device is None:
+        device = next((t.device for t in cleans if t.is_cuda), None)
+    values = {m: [] for m in metrics}
+    for i, t in enumerate(cleans):
+        clean = _to_device(t, device)
+        restored = _restore_device(model, kernels.u8_bicubic_degrade(clean, scale), None, factor, tile, halo,
+                                   micro_batch, True, modes)
+        if restored.shape != clean.shape:
+            raise ValueError(f"{who}: the model returns {restored.shape[2]} channel(s) for {clean.shape[2]}; no score")
+        if shave:       # an ATen slice and copy: a few hundred kilobytes per picture, not a hot path
+            h, w = clean.shape[:2]
+            restored = restored[shave:h - shave, shave:w - shave].contiguous()
+            clean = clean[shave:h - shave, shave:w - shave].contiguous()
+        for m in metrics:
+            values[m].append(_SCORE[m](restored, clean))
+    return {m: (float(np.mean(values[m])), values[m]) for m in metrics}
 
 
 def evaluate_pairs(model: Callable, inputs, targets, factor: int = 16, across_images: bool = False, ensemble=1,

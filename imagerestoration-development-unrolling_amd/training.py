@@ -31,6 +31,10 @@ grr_patch_batch).
 artefacts, blur, rain): nothing is synthesised unless a noise mode asks for it.  Its device-resident stage holds
 two arenas under one image table (grr_patch_pair_batch), ``TestPairsCSV`` lists pairs for the periodic validation
 and ``validate_pairs`` scores them with restore.evaluate_pairs.
+``BicubicSuperResolution`` is that plan over clean files alone for bicubic super-resolution: the input is the picture
+degraded by the exact bicubic down and up at an integer scale (``bicubic_degrade_u8`` on the host; on the device
+csrc/resize_ops.hip makes the degraded arena from the clean one), and ``validate_sr`` scores the protocol on a
+``TestImagesCSV`` set with restore.evaluate_sr.
 """
 from __future__ import annotations
 
@@ -376,6 +380,92 @@ class PairedImageRestoration(ImageSuperResolution):
         return torch.from_numpy(inp), torch.from_numpy(tgt)
 
 
+def _bicubic_pass_u8(a: np.ndarray, s: int, up_to: Optional[int]) -> np.ndarray:
+    """One 1-D pass of the exact bicubic resize along axis 0 of a uint8 [n, ...] array (include/grr.h): down to
+    ceil(n / s) rows (up_to None) or up to ``up_to`` rows.  One int64 multiply-add over the whole output per tap."""
+    from . import kernels
+    n = a.shape[0]
+    is_up = up_to is not None
+    length = up_to if is_up else -(-n // s)
+    sets = kernels.resize_taps(s, is_up)
+    src = a.astype(np.int64)
+    acc = np.zeros((length,) + a.shape[1:], np.int64)
+    y = np.arange(length, dtype=np.int64)
+    for p, taps in enumerate(sets):
+        rows = y[y % s == p] if is_up else y
+        base = rows // s if is_up else rows * s
+        for off, q in taps:
+            t = (base + off) % (2 * n)                                   # numpy's %: non-negative
+            acc[rows] += np.int64(q) * src[np.where(t < n, t, 2 * n - 1 - t)]
+    return np.clip((acc + (1 << 29)) >> 30, 0, 255).astype(np.uint8)
+
+
+def _bicubic_resize_u8(a: np.ndarray, s: int, out_hw) -> np.ndarray:
+    rows = _bicubic_pass_u8(a, s, None if out_hw is None else out_hw[0])
+    cols = _bicubic_pass_u8(rows.transpose(1, 0, 2), s, None if out_hw is None else out_hw[1])
+    return np.ascontiguousarray(cols.transpose(1, 0, 2))
+
+
+def bicubic_degrade_u8(a: np.ndarray, s: int) -> np.ndarray:
+    """The bicubic super-resolution input of a uint8 H x W x C picture on the CPU, at its size: the exact
+    antialiased bicubic down by the integer scale ``s`` (2..8) and the bicubic back up to H x W, rows first and a
+    rounding to uint8 after each 1-D pass (include/grr.h; MATLAB imresize's convention with fixed-point weights).
+    The same integers as kernels.u8_bicubic_degrade, bit for bit: it serves the host DataLoader path and users
+    without a GPU."""
+    a = np.asarray(a)
+    if a.dtype != np.uint8 or a.ndim != 3:
+        raise ValueError(f"bicubic_degrade_u8: expected a uint8 H x W x C picture, got {a.dtype} {a.shape}")
+    if isinstance(s, bool) or not isinstance(s, (int, np.integer)) or not 2 <= s <= 8:
+        raise ValueError(f"bicubic_degrade_u8: the scale is an integer of 2..8, got {s!r}")
+    s = int(s)
+    return _bicubic_resize_u8(_bicubic_resize_u8(a, s, None), s, a.shape[:2])
+
+
+class BicubicSuperResolution(ImageSuperResolution):
+    """Bicubic super-resolution pairs synthesised from clean files under ImageSuperResolution's csv, crop and patch
+    plan and draws: the input of a sample is the same patch of the whole picture degraded by ``scale`` (2..8) --
+    the exact antialiased bicubic down and the bicubic back up to the picture's size, bicubic_degrade_u8 -- and the
+    target the clean patch.  ``dist_mode``: "none" (default), or one of the parent's three additive modes, whose
+    noise is added on top of the degraded patch as in PairedImageRestoration.  ``__getitem__`` is the host path:
+    it degrades the decoded picture with numpy (the last CACHE pictures are kept), makes the parent's draws in the
+    parent's order and returns (input, target) float32 HWC, cut and turned alike.  A DevicePatchLoader decodes only
+    the clean files and makes the degraded arena on the GPU."""
+
+    DIST_MODES = ("none",) + ImageSuperResolution.DIST_MODES
+    CACHE = 4
+
+    def __init__(self, csv_path, scale, dist_mode="none", lambda_noise=None, use_data_aug=False, patch_size=(64, 64),
+                 max_num_patchs=100000, root_folder="", logger=None, device=None, seed=2204, n_channels=3):
+        if isinstance(scale, bool) or not isinstance(scale, int) or not 2 <= scale <= 8:
+            raise ValueError(f"BicubicSuperResolution: scale is an integer of 2..8, got {scale!r}")
+        self.scale = scale
+        self._degraded = {}          # image index -> (clean, degraded), the last CACHE decoded
+        super().__init__(csv_path, dist_mode, lambda_noise, use_data_aug=use_data_aug, patch_size=patch_size,
+                         max_num_patchs=max_num_patchs, root_folder=root_folder, logger=logger, device=device,
+                         seed=seed, n_channels=n_channels)
+
+    def load_pair(self, img: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(degraded, clean) of file ``img`` as uint8 H x W x n_channels."""
+        if img not in self._degraded:
+            while len(self._degraded) >= self.CACHE:
+                self._degraded.pop(next(iter(self._degraded)))
+            clean = self.load_image(img)
+            self._degraded[img] = (bicubic_degrade_u8(clean, self.scale), clean)
+        return self._degraded[img]
+
+    def __getitem__(self, idx):
+        row, col, need_padding, img_i = self.patchs_data[idx]
+        degraded, clean = self.load_pair(img_i)
+        inp, tgt = self._cut(degraded, row, col, need_padding), self._cut(clean, row, col, need_padding)
+        if self.use_data_augmentation:
+            mode = self.random_state.randint(0, 7)
+            inp, tgt = data_augmentation(inp, mode), data_augmentation(tgt, mode)
+        inp, tgt = inp.astype(np.float32) / 255.0, tgt.astype(np.float32) / 255.0
+        if self.dist_mode != "none":
+            inp = _noisy(inp, self.random_state, self.dist_mode, self.lambda_noise)
+        return torch.from_numpy(inp), torch.from_numpy(tgt)
+
+
 class DevicePatchLoader:
     """Batches of an ImageSuperResolution dataset made on the device: yields (noisy, clean) float32
     [B, C, h, w], planar (``channels_first``), in place of a DataLoader.  On first use (or in ``prepare``) every file
@@ -396,7 +486,11 @@ class DevicePatchLoader:
     pass into two arenas under one image table and a batch is one kernels.patch_pair_batch call.  The draws are the
     same ones -- dist_mode "none" draws no level and its sigma is zero, so the kernel computes no noise -- and a
     sample stays a function of (dataset seed, epoch, position).  The device holds both arenas: twice the bytes of
-    the unpaired loader over the same pictures."""
+    the unpaired loader over the same pictures.
+
+    A BicubicSuperResolution dataset yields (input, target) by the paired path as well, but only its clean files are
+    decoded: the degraded arena is made from the clean one on the device (kernels.u8_bicubic_degrade_images, once, in
+    ``prepare``) and shares its image table.  The host never holds a degraded picture."""
     channels_first = True
     CHUNK_BYTES = 256 << 20      # decoded pictures staged on the host per transfer
 
@@ -411,7 +505,8 @@ class DevicePatchLoader:
         self.dataset, self.sampler, self.batch_size, self.drop_last = dataset, sampler, int(batch_size), bool(drop_last)
         self.device = device
         self.shared = shared
-        self.paired = isinstance(dataset, PairedImageRestoration)
+        self.synthetic = isinstance(dataset, BicubicSuperResolution)     # the input arena is made on the device
+        self.paired = self.synthetic or isinstance(dataset, PairedImageRestoration)
         self.source = None           # kernels.PatchSource (PatchPairSource if paired): the arena(s), checked once
         self._draws = (None, None, None)
 
@@ -428,7 +523,8 @@ class DevicePatchLoader:
         ds, c = self.dataset, self.dataset.n_channels
         shapes = [(int(ds.img_infos.iloc[i]["height"]), int(ds.img_infos.iloc[i]["width"])) for i in used]
         host_table, total = restore._host_table(shapes, c)
-        arenas = [torch.empty(total, dtype=torch.uint8, device=dev) for _ in range(2 if self.paired else 1)]
+        from_files = self.paired and not self.synthetic             # both arenas are decoded
+        arenas = [torch.empty(total, dtype=torch.uint8, device=dev) for _ in range(2 if from_files else 1)]
         held, held_bytes, at = [[] for _ in arenas], 0, 0
 
         def flush():
@@ -443,7 +539,7 @@ class DevicePatchLoader:
             if a.shape[:2] != shape:
                 raise ValueError(f"ImageSuperResolution: {ds.paths[i]} is {a.shape[0]} x {a.shape[1]}, the csv says "
                                  f"{shape[0]} x {shape[1]}")
-            for parts, picture in zip(held, (a, ds.load_target(i, a)) if self.paired else (a,)):
+            for parts, picture in zip(held, (a, ds.load_target(i, a)) if from_files else (a,)):
                 parts.append(torch.from_numpy(np.ascontiguousarray(picture)).reshape(-1))
             held_bytes += a.size
             if held_bytes >= self.CHUNK_BYTES:
@@ -465,11 +561,15 @@ class DevicePatchLoader:
             slot[used] = np.arange(len(used))
             self._slot = slot
             key = (tuple(ds.paths[i] for i in used), ds.n_channels, str(dev))
-            if self.paired:      # both arenas under one key: a curriculum decodes each file once
+            if self.synthetic:
+                key += ("bicubic", ds.scale)
+            elif self.paired:    # both arenas under one key: a curriculum decodes each file once
                 key += (tuple(ds.target_paths[i] for i in used),)
             store = self.shared if self.shared is not None else {}
             if key not in store:
                 packs = self._pack(used, dev)
+                if self.synthetic:
+                    packs = (kernels.u8_bicubic_degrade_images(packs[0], ds.scale), packs[0])
                 store[key] = kernels.patch_pair_source(*packs) if self.paired else kernels.patch_source(*packs)
             self.source = store[key]
         return (self.source.input, self.source.target) if self.paired else self.source.pack
@@ -523,7 +623,7 @@ class DevicePatchLoader:
 
 
 DATASETS = {c.__name__: c for c in (AddictiveGaussianNoiseImagePair, SyntheticNoisyPatches, ImageSuperResolution,
-                                    PairedImageRestoration)}
+                                    PairedImageRestoration, BicubicSuperResolution)}
 
 
 # ---------------------------------------------------------------------------
@@ -682,16 +782,60 @@ def validate_pairs(model: nn.Module, pairs, factor: int = 16, device=None, metri
     return float(acc[0] / acc[1])
 
 
+VAL_SR_METRICS = ("psnr", "psnr_y")
+
+
+def validate_sr(model: nn.Module, images, scale: int, shave: Optional[int] = None, factor: int = 16, device=None,
+                metric: str = "psnr_y", **tiling_args) -> float:
+    """Mean PSNR of ``model`` on the bicubic super-resolution protocol over clean test pictures (``images[i]``: uint8
+    H x W x C, or float32 in [0, 1] on the uint8 grid as TestImagesCSV yields them): restore.evaluate_sr on this
+    rank's share -- mod-crop, degrade by ``scale`` on the device, restore, shave ``shave`` (default ``scale``)
+    border pixels, score.  ``metric``: "psnr_y" (default, the tables' number) or "psnr".  Nothing is drawn.
+    tiling_args: tile, halo, micro_batch, ensemble.
+
+    Several ranks: sharded and all-reduced as validate_pairs does."""
+    from . import restore
+    if metric not in VAL_SR_METRICS:
+        raise ValueError(f"validate_sr: metric is one of {VAL_SR_METRICS}, got {metric!r}")
+    rank, world = sharding.world()
+    if device is None:
+        device = next(model.parameters()).device
+    s, e = sharding.shard_range(len(images), rank, world)
+    mine = []
+    for i in range(s, e):
+        a = np.asarray(images[i])
+        a = a[:, :, None] if a.ndim == 2 else a
+        mine.append(a if a.dtype == np.uint8 else np.rint(a.astype(np.float64) * 255.0).astype(np.uint8))
+    psnrs = restore.evaluate_sr(model, mine, scale, shave=shave, factor=factor, device=device, metrics=(metric,),
+                                **tiling_args)[metric][1] if mine else []
+    acc = torch.tensor([float(np.sum(psnrs)), float(len(psnrs))], dtype=torch.float64)
+    if world > 1:
+        if torch.distributed.get_backend() == "nccl":
+            acc = acc.to(device)
+        torch.distributed.all_reduce(acc)
+    return float(acc[0] / acc[1])
+
+
 def create_val_dataset(conf: dict):
     """``datasets.val`` of the YAML ({type, dataset_args, sigma, factor}), or None.  A paired set (TestPairsCSV)
     takes {type, dataset_args, factor, tile, halo, micro_batch, metric}: validate_pairs' arguments, no sigma; without
-    ``metric`` validate_pairs' default, the RGB PSNR, is scored."""
+    ``metric`` validate_pairs' default, the RGB PSNR, is scored.  TestImagesCSV with a ``scale`` key is the bicubic
+    super-resolution protocol: {type, dataset_args, scale, shave, factor, tile, halo, micro_batch, metric},
+    validate_sr's arguments, no sigma."""
     vconf = conf.get("datasets", {}).get("val")
     if not vconf:
         return None, {}
     cls = VAL_DATASETS.get(vconf["type"])
     if cls is None:
         raise ValueError(f"Validation dataset {vconf['type']} is not found.")
+    if cls is TestImagesCSV and vconf.get("scale") is not None:
+        args = {k: int(vconf[k]) for k in ("tile", "halo", "micro_batch", "shave") if vconf.get(k) is not None}
+        if vconf.get("metric") is not None:
+            if vconf["metric"] not in VAL_SR_METRICS:
+                raise ValueError(f"datasets.val.metric is one of {VAL_SR_METRICS}, got {vconf['metric']!r}")
+            args["metric"] = str(vconf["metric"])
+        return cls(**vconf.get("dataset_args", {})), dict(args, scale=int(vconf["scale"]),
+                                                           factor=int(vconf.get("factor", 16)))
     if cls is TestPairsCSV:
         args = {k: int(vconf[k]) for k in ("tile", "halo", "micro_batch") if vconf.get(k) is not None}
         if vconf.get("metric") is not None:
@@ -770,9 +914,9 @@ class TrainStage:
         self.sampler = ResumeableSampler(self.dataset, self.batch_size, rank, world)
         if ds_conf.get("device_resident"):
             # batches made on the device from a packed arena; dataloader_args' num_workers is ignored
-            if ds_conf["type"] not in ("ImageSuperResolution", "PairedImageRestoration"):
-                raise ValueError(f"training stage {index}: device_resident needs type ImageSuperResolution or "
-                                 f"PairedImageRestoration, got {ds_conf['type']}")
+            if ds_conf["type"] not in ("ImageSuperResolution", "PairedImageRestoration", "BicubicSuperResolution"):
+                raise ValueError(f"training stage {index}: device_resident needs type ImageSuperResolution, "
+                                 f"PairedImageRestoration or BicubicSuperResolution, got {ds_conf['type']}")
             self.loader = DevicePatchLoader(self.dataset, self.sampler, self.batch_size, self.drop_last,
                                             shared=shared)
         else:
@@ -1018,7 +1162,8 @@ def run(conf: dict, device=None, max_iters: Optional[int] = None) -> Trainer:
                     save()
                     saved_at = trainer.i
                 if val_every and trainer.i % val_every == 0:
-                    check = validate_pairs if isinstance(val_set, TestPairsCSV) else validate
+                    check = validate_pairs if isinstance(val_set, TestPairsCSV) else \
+                        validate_sr if "scale" in val_args else validate
                     psnr = check(trainer.model, val_set, device=device, **val_args)
                     trainer.val_history.append((trainer.i, psnr))
                     if rank == 0:

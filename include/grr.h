@@ -918,6 +918,58 @@ grr_status grr_patch_pair_batch(const uint8_t* input_arena, const uint8_t* targe
                                 const float* sigma /* NULL: no noise */, int n, uint64_t seed, int ph, int pw,
                                 float* target, float* input, void* stream);
 
+/* ---- bicubic resize of uint8 pictures by an integer scale s, 2 <= s <= 8 (csrc/resize_ops.hip): the degradation
+ * of the bicubic super-resolution protocol -- mod-crop, antialiased bicubic down, bicubic back up -- made on the
+ * device.  The convention is that of MATLAB's imresize (bicubic with a = -0.5, half-pixel centres, antialiasing
+ * when shrinking, symmetric edge, a rounding to uint8 after each 1-D pass) with one change that makes the result
+ * exact and independent of any order of summation: the weights are fixed-point integers.  No floating point
+ * appears in the definition.
+ *
+ * cubic(x) = 1.5 |x|^3 - 2.5 |x|^2 + 1 for |x| <= 1, -0.5 |x|^3 + 2.5 |x|^2 - 4 |x| + 2 for 1 < |x| < 2, else 0.
+ * 1-D down pass, length n -> ceil(n / s): output i has centre u = (i + 1/2) s - 1/2, its taps are all integers j
+ *   with |u - j| < 2 s, raw weight cubic((u - j) / s); relative to i s the taps are the same for every i (one
+ *   phase).
+ * 1-D up pass, length n -> any L with s (n - 1) < L <= s n: output y has phase p = y mod s and base b = y div s;
+ *   u = (p + 1/2) / s - 1/2, taps are the integers j with |u - j| < 2 at input index b + j, raw weight
+ *   cubic(u - j) (s phases).
+ * One tap set is quantised from exact rationals: divide the raw weights by their exact sum, q = round-half-even(
+ *   w 2^30), add 2^30 - sum q to the largest q (the lowest index among equals), drop zero taps.  sum q = 2^30, so
+ *   a constant picture maps to itself.
+ * Applying it: input indices go through sym(r, n) of grr_patch_batch (t = r mod 2n; t < n ? t : 2n - 1 - t,
+ *   periodic where the support exceeds the side), acc = sum q v in 64-bit integers,
+ *   out = clamp((acc + 2^29) >> 30, 0, 255) with an arithmetic shift.
+ * 2-D: rows (axis 0) first, then columns, each pass uint8 -> uint8, per channel.
+ *
+ * The caller computes the quantised tap sets and passes them as host arrays: n_phase (1 for down, s for up), and
+ * per phase p first[p], the offset of its first tap (from i s for down, from b for up), count[p], and count[p]
+ * weights in taps, the phases back to back; a phase's taps are consecutive offsets, so a dropped zero tap between
+ * two others is passed as a zero.  The library copies them into the kernel arguments.  GRR_ERR_INVALID_ARG, before
+ * any launch, for a phase that does not sum to 2^30, has more than 4 s taps, or has a tap outside the offsets the
+ * definition can give (down -2 s .. 3 s, up -2 .. 2).
+ *
+ * src, dst: HWC interleaved uint8 at any byte address; element offsets are 64-bit.  Each output byte is written
+ * once; no atomics; the uint8 picture between the two passes lives in LDS only. */
+
+/* 1 where grr_u8_resize takes the image: 1 <= C <= 4, 2 <= s <= 8, H, W >= 1, and both H W C and the output's
+ * element count (down: ceil(H / s) ceil(W / s) C; up: s H s W C) below 2^31. */
+int grr_u8_resize_supported(int C, int H, int W, int s, int up);
+/* One image.  down (up == 0): Ho == ceil(H / s) and Wo == ceil(W / s); up: s (H - 1) < Ho <= s H and likewise Wo;
+ * else GRR_ERR_SHAPE. */
+grr_status grr_u8_resize(const uint8_t* src, int H, int W, int C, uint8_t* dst, int Ho, int Wo, int s, int up,
+                         int n_phase, const int32_t* first, const int32_t* count, const int32_t* taps, void* stream);
+/* Every image of src_arena into its place in dst_arena, one launch: image i is read at row i of src_table and
+ * written at row i of dst_table (int64 [n_img, 3] each on the device, 8-byte aligned, rows (element offset, H, W)
+ * and (element offset, Ho, Wo); the two arenas have different image sizes, hence two tables).  max_ho, max_wo bound
+ * every image's output sides.  The tables are clamped -- offsets into the arenas, sides into [1, 2^31) and
+ * [1, max_ho] x [1, max_wo], every element index read into [0, src_elems), a write at or past dst_elems dropped --
+ * so a bad table gives wrong pixels, never an access outside the two arenas; that Ho, Wo are the legal output sides
+ * of H, W is the caller's to check on its host copy.  n_img <= 65535 (one grid row per image), else
+ * GRR_ERR_UNSUPPORTED. */
+grr_status grr_u8_resize_images(const uint8_t* src_arena, int64_t src_elems, const int64_t* src_table,
+                                uint8_t* dst_arena, int64_t dst_elems, const int64_t* dst_table, int C, int n_img,
+                                int max_ho, int max_wo, int s, int up, int n_phase, const int32_t* first,
+                                const int32_t* count, const int32_t* taps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,8 @@
 """Restore image files with a trained model (irdu_amd.restore; single process, one GPU).
 
     python restore.py -yaml_path CONF.yaml --ckpt CHECKPOINT.pt --input FILE_OR_DIR --output DIR \\
-           [--sigma S --seed N [--ssim] [--y-channel] | --reference DIR [--ssim] [--y-channel]]
+           [--sigma S --seed N [--ssim] [--y-channel] | --reference DIR [--ssim] [--y-channel]
+            | --scale S [--shave N] [--ssim] [--y-channel] | --upscale S]
            [--tile T --halo H --factor F] [--batch-images]
            [--self-ensemble | --ensemble-modes 0,1,4,5]
 
@@ -27,6 +28,13 @@ another size is reported before anything runs.  It works with --batch-images and
 YCbCr, as the tables of deraining, deblurring and super-resolution papers are: ITU-R BT.601 luma in [16, 235], not
 rounded (MATLAB's rgb2ycbcr, BasicSR's test_y_channel; ``irdu_amd.psnr_y_u8`` / ``ssim_y_u8``).  The lines then read
 PSNR-Y and SSIM-Y in place of PSNR and SSIM; the files written are the same.
+With --scale S (2..8; not with --sigma or --reference) the inputs are clean high-resolution files and the bicubic
+super-resolution protocol runs on each: it is cropped at the top left to multiples of S, degraded on the GPU by the
+exact antialiased bicubic down and the bicubic back up (``irdu_amd.bicubic_degrade_u8``), restored, and scored against
+the cropped input after --shave N border pixels (default S) are cut from both; the restored picture is written at the
+cropped size.  --ssim and --y-channel apply as above (the tables print PSNR-Y / SSIM-Y).  With --upscale S the inputs
+are low-resolution files: each is brought to S times its size by the bicubic (``irdu_amd.bicubic_up_u8``), restored
+and written at that size; nothing is scored.  Both work with --batch-images and the ensemble options.
 """
 import argparse
 import os
@@ -89,10 +97,18 @@ def parse_args(argv=None):
     scored.add_argument("--reference", type=str, default=None, metavar="DIR",
                         help="inputs are degraded: restore them as they are, report PSNR against the file of the same "
                              "stem in DIR")
+    scored.add_argument("--scale", type=int, default=None, metavar="S",
+                        help="inputs are clean: mod-crop, degrade by the bicubic at scale S (2..8), restore, report PSNR "
+                             "against the cropped input")
+    scored.add_argument("--upscale", type=int, default=None, metavar="S",
+                        help="inputs are low-resolution: bring each to S times its size with the bicubic, restore, write")
+    ap.add_argument("--shave", type=int, default=None, metavar="N",
+                    help="with --scale: border pixels cut from both pictures before scoring (default: S)")
     ap.add_argument("--seed", type=int, default=2204)
-    ap.add_argument("--ssim", action="store_true", help="with --sigma or --reference: report the SSIM beside the PSNR")
+    ap.add_argument("--ssim", action="store_true",
+                    help="with --sigma, --reference or --scale: report the SSIM beside the PSNR")
     ap.add_argument("--y-channel", action="store_true",
-                    help="with --sigma or --reference: score on the Y channel of YCbCr (BT.601 luma of RGB images): "
+                    help="with --sigma, --reference or --scale: score on the Y channel of YCbCr (BT.601 luma of RGB images): "
                          "PSNR-Y, and with --ssim SSIM-Y, in place of the RGB values")
     ap.add_argument("--tile", type=int, default=None)
     ap.add_argument("--halo", type=int, default=None)
@@ -105,10 +121,19 @@ def parse_args(argv=None):
     group.add_argument("--ensemble-modes", type=str, default=None, metavar="M,M,...",
                        help="average over these modes of 0..7 only, ascending (e.g. 0,1,4,5)")
     args = ap.parse_args(argv)
-    if args.ssim and args.sigma is None and args.reference is None:
-        ap.error("--ssim needs --sigma or --reference: there is nothing to compare a restored image with otherwise")
-    if args.y_channel and args.sigma is None and args.reference is None:
-        ap.error("--y-channel needs --sigma or --reference: there is nothing to compare a restored image with otherwise")
+    args.scored = args.sigma is not None or args.reference is not None or args.scale is not None
+    if args.ssim and not args.scored:
+        ap.error("--ssim needs --sigma, --reference or --scale: there is nothing to compare a restored image with otherwise")
+    if args.y_channel and not args.scored:
+        ap.error("--y-channel needs --sigma, --reference or --scale: there is nothing to compare a restored image with "
+                 "otherwise")
+    for flag, value in (("--scale", args.scale), ("--upscale", args.upscale)):
+        if value is not None and not 2 <= value <= 8:
+            ap.error(f"{flag}: the scale is an integer of 2..8, got {value}")
+    if args.shave is not None and (args.scale is None or args.shave < 0):
+        ap.error("--shave is a non-negative number of pixels and needs --scale")
+    if args.scale is not None and args.shave is None:
+        args.shave = args.scale
     args.ensemble = 8 if args.self_ensemble else 1
     if args.ensemble_modes is not None:
         try:
@@ -168,11 +193,29 @@ def main(argv=None) -> None:
     psnr_of, ssim_of, tag = ((irdu_amd.psnr_y_u8, irdu_amd.ssim_y_u8, "-Y") if args.y_channel else
                              (irdu_amd.psnr_u8, irdu_amd.ssim_u8, ""))
 
-    def read(path):
+    def decode(path):
         img = np.array(Image.open(path))
         if img.dtype != np.uint8:
             raise SystemExit(f"{path}: only 8-bit images are supported (got {img.dtype})")
         return img[:, :, None] if img.ndim == 2 else img
+
+    def read(path):
+        """The picture the model's input is made of and, when scoring without a reference, compared with."""
+        img = decode(path)
+        if args.scale is not None:          # the protocol's mod-crop
+            h, w = img.shape[0] // args.scale * args.scale, img.shape[1] // args.scale * args.scale
+            if min(h, w) <= 2 * args.shave:
+                raise SystemExit(f"{path}: nothing is left of {img.shape[0]}x{img.shape[1]} after the crop to multiples "
+                                 f"of {args.scale} and a shave of {args.shave}")
+            img = np.ascontiguousarray(img[:h, :w])
+        elif args.upscale is not None:
+            img = irdu_amd.bicubic_up_u8(img, args.upscale)
+        return img
+
+    def input_of(img):
+        if args.sigma is not None:
+            return noisy_of(img)
+        return img if args.scale is None else irdu_amd.bicubic_degrade_u8(img, args.scale)
 
     def noisy_of(img):
         noisy = img.astype(np.float32) / 255.0
@@ -181,23 +224,28 @@ def main(argv=None) -> None:
 
     def finish(path, img, out):
         out_path = os.path.join(args.output, os.path.splitext(os.path.basename(path))[0] + ".png")
-        if args.sigma is None and args.reference is None:
+        if not args.scored:
             print(f"{path} -> {out_path}  {img.shape[0]}x{img.shape[1]}x{img.shape[2]}")
         else:
             if out.shape != img.shape:
                 raise SystemExit(f"{path}: the model returns {out.shape[2]} channels for {img.shape[2]}; no PSNR")
-            truth = img if args.reference is None else read(refs[path])
+            truth = img if args.reference is None else decode(refs[path])
             if truth.shape != out.shape:
                 raise SystemExit(f"--reference: {refs[path]} decodes to {truth.shape}, the restored {path} is {out.shape}")
+            scored = out
+            if args.scale is not None and args.shave:
+                n = args.shave
+                scored, truth = np.ascontiguousarray(out[n:-n, n:-n]), np.ascontiguousarray(truth[n:-n, n:-n])
             try:
-                psnrs.append(psnr_of(out, truth))
+                psnrs.append(psnr_of(scored, truth))
             except ValueError as e:
                 raise SystemExit(f"{path}: {e}")
-            against = f"sigma {args.sigma:g}" if args.reference is None else f"reference {refs[path]}"
+            against = (f"bicubic x{args.scale} shave {args.shave}" if args.scale is not None else
+                       f"sigma {args.sigma:g}" if args.reference is None else f"reference {refs[path]}")
             line = f"{path} -> {out_path}  {against}  PSNR{tag} {psnrs[-1]:.4f} dB"
             if args.ssim:
                 try:
-                    ssims.append(ssim_of(out, truth))
+                    ssims.append(ssim_of(scored, truth))
                 except ValueError as e:
                     raise SystemExit(f"{path}: {e}")
                 line += f"  SSIM{tag} {ssims[-1]:.4f}"
@@ -206,7 +254,7 @@ def main(argv=None) -> None:
 
     if args.batch_images:
         imgs = [read(path) for path in files]
-        inputs = imgs if args.sigma is None else [noisy_of(img) for img in imgs]       # draws in file order
+        inputs = [input_of(img) for img in imgs]                                       # draws in file order
         try:
             outs = irdu_amd.restore_images(model, inputs, factor=args.factor, tile=tile, halo=halo, ensemble=ensemble)
         except ValueError as e:
@@ -216,7 +264,7 @@ def main(argv=None) -> None:
     else:
         for path in files:
             img = read(path)
-            out = irdu_amd.restore_image(model, img if args.sigma is None else noisy_of(img), factor=args.factor,
+            out = irdu_amd.restore_image(model, input_of(img), factor=args.factor,
                                          tile=tile, halo=halo, ensemble=ensemble)
             finish(path, img, out)
     if psnrs:
