@@ -29,7 +29,16 @@ resize(BICUBIC) down and back up of every picture, one wall-clock pass.  One JSO
 the two kernels' algorithmic bytes (each input byte read once, each output byte written once) over the device time,
 and grr_stream_copy's rate on a buffer of the arena's size in the same process for scale.
 
-    python bench_data.py [--paired | --pair-kernel | --bicubic S] [--steps 60] [--warmup 10] [--images 12] [--side 1200] [--workers 4] [--files 8600]
+With --jpeg Q only the synthesis of a JPEG artifact-removal training set's degraded pictures is timed, on the same
+pictures and by the same method: "device" is kernels.u8_jpeg_images on the clean arena (one launch) for gray (the
+pictures' first channel), 4:4:4 and 4:2:0, device events around each of 20 calls after a warm-up; "host" is one serial
+pass of Pillow's save(format="JPEG", quality=Q) and open of every picture; grr_stream_copy is timed in the same
+process.  One JSON line ("bench": "jpeg") with, per mode, the times, the algorithmic GB/s (each byte in once, each
+byte out once) and the kernel / copy time ratio at equal bytes, then one ("bench": "blocking") with
+kernels.u8_blocking against kernels.u8_sse on one 2048 x 2048 x 3 picture, host clock around calls that end in the
+sums' device-to-host copy.
+
+    python bench_data.py [--paired | --pair-kernel | --bicubic S | --jpeg Q] [--steps 60] [--warmup 10] [--images 12] [--side 1200] [--workers 4] [--files 8600]
 """
 from __future__ import annotations
 
@@ -212,6 +221,75 @@ def bicubic(scale: int, images: int, side: int, rounds: int = 20) -> None:
                       "host_pillow_s": round(host_s, 3), "host_over_device": round(host_s * 1e3 / med, 1)}), flush=True)
 
 
+def device_ms(call, rounds: int):
+    """Milliseconds of ``rounds`` calls, each between two device events, after one warm-up call."""
+    ms = []
+    for r in range(rounds + 1):
+        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        start.record()
+        call()
+        end.record()
+        torch.cuda.synchronize()
+        if r:
+            ms.append(start.elapsed_time(end))
+    return ms
+
+
+def spread(ms) -> dict:
+    return {"median": round(float(np.median(ms)), 3), "min": round(min(ms), 3), "max": round(max(ms), 3)}
+
+
+def jpeg(quality: int, images: int, side: int, rounds: int = 20) -> None:
+    import io
+    from PIL import Image
+    import irdu_amd
+    irdu_amd.load_native()
+    from irdu_amd import _native, kernels, restore
+    dev = torch.device("cuda:0")
+    pics = synthetic_pictures(images, side)
+    stream = torch.cuda.current_stream().cuda_stream
+    line = {"bench": "jpeg", "quality": quality, "images": images, "rounds": rounds}
+    for mode, sub, chosen in (("gray", 0, [p[:, :, :1] for p in pics]), ("444", 0, pics), ("420", 2, pics)):
+        pack = restore.pack_images([np.ascontiguousarray(p) for p in chosen], dev)
+        n = pack.arena.numel()
+        qualities = torch.full((len(pack),), quality, dtype=torch.int32, device=dev)     # no upload in the timed call
+        ms = device_ms(lambda: kernels.u8_jpeg_images(pack, qualities, sub), rounds)
+        # the float4 copy of the same bytes, in the same process
+        a = torch.empty(n // 4, dtype=torch.float32, device=dev)
+        b = torch.empty_like(a)
+        copy = device_ms(lambda: _native.call("grr_stream_copy", b.data_ptr(), a.data_ptr(), n // 4, stream), rounds)
+        t0 = time.perf_counter()
+        for pic in chosen:
+            buf = io.BytesIO()
+            Image.fromarray(pic[:, :, 0] if pic.shape[2] == 1 else pic).save(buf, format="JPEG", quality=quality,
+                                                                            subsampling=sub)
+            np.asarray(Image.open(io.BytesIO(buf.getvalue())))
+        host_s = time.perf_counter() - t0
+        med, copy_med = float(np.median(ms)), float(np.median(copy))
+        line[mode] = {"arena_mb": round(n / 2 ** 20, 1), "device_ms": spread(ms),
+                      "device_gbps": round(2 * n / med / 1e6, 1), "stream_copy_ms": spread(copy),
+                      "stream_copy_gbps": round(8 * (n // 4) / copy_med / 1e6, 1),
+                      "kernel_over_copy": round(med / copy_med, 1), "host_pillow_s": round(host_s, 3),
+                      "host_over_device": round(host_s * 1e3 / med, 1)}
+        del pack, a, b
+    print(json.dumps(line), flush=True)
+    # the blocking sums against the SSE on one large picture: host clock, each call ends in its device-to-host copy
+    rs = np.random.RandomState(5)
+    x = torch.from_numpy(rs.randint(0, 256, (2048, 2048, 3)).astype(np.uint8)).to(dev)
+    y = torch.from_numpy(rs.randint(0, 256, (2048, 2048, 3)).astype(np.uint8)).to(dev)
+    out = {"bench": "blocking", "shape": [2048, 2048, 3], "rounds": rounds}
+    for name, call in (("u8_blocking", lambda: kernels.u8_blocking(x)), ("u8_sse", lambda: kernels.u8_sse(x, y))):
+        call()
+        us = []
+        for _ in range(rounds):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            call()
+            us.append((time.perf_counter() - t0) * 1e6)
+        out[name + "_us"] = spread(us)
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     # the DataLoader's workers hold up to 2 batches each in flight when the clock starts: enough timed batches
@@ -232,9 +310,14 @@ def main():
     ap.add_argument("--bicubic", type=int, default=None, metavar="S",
                     help="only time the synthesis of the degraded pictures at scale S: the device kernels against "
                          "Pillow's resize down and up on the host")
+    ap.add_argument("--jpeg", type=int, default=None, metavar="Q",
+                    help="only time the synthesis of the JPEG-degraded pictures at quality Q: the device kernel (gray, "
+                         "4:4:4, 4:2:0) against Pillow's encode and decode on the host, then the blocking kernel")
     args = ap.parse_args()
     if args.pair_kernel:
         return pair_kernel()
+    if args.jpeg is not None:
+        return jpeg(args.jpeg, args.images, args.side)
     if args.bicubic is not None:
         return bicubic(args.bicubic, args.images, args.side)
     import irdu_amd

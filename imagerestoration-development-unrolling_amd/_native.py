@@ -195,6 +195,12 @@ SIGNATURES = {
     "grr_u8_resize_supported": [I, I, I, I, I],
     "grr_u8_resize": [P, I, I, I, P, I, I, I, I, I, P, P, P, P],
     "grr_u8_resize_images": [P, L, P, P, L, P, I, I, I, I, I, I, I, P, P, P, P],
+    # the JPEG round trip of uint8 images (jpeg_ops.hip) and the blocking sums of PSNR-B (metric_ops.hip)
+    "grr_u8_jpeg_supported": [I, I, I, I],
+    "grr_u8_jpeg": [P, I, I, I, P, I, I, P],
+    "grr_u8_jpeg_images": [P, L, I, P, I, I, I, P, P, I, P],
+    "grr_u8_blocking": [P, I, I, I, P, P],
+    "grr_u8_blocking_images": [P, L, I, P, I, I, I, P, P],
 }
 _RESTYPES = {"grr_version": c_int, "grr_last_error": ctypes.c_char_p, "grr_lnb_workspace_bytes": c_int64,
              "grr_conv1x1_workspace_bytes": c_int64, "grr_wgrad_workspace_bytes": c_int64,

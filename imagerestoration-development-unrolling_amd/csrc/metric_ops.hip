@@ -45,6 +45,10 @@
 // Y = double(Ny) / 255000.0 per pixel -- the integer is exact and the division rounds once, so the device and
 // every host form the same bits -- and runs the body above over pixel columns: u8_ssim_kernel takes what a staged
 // column is (BytePx<C>: one interleaved byte; LumaPx: the luma of three) as a template parameter.
+//
+// The blocking sums of PSNR-B of one uint8 H x W x C image (include/grr.h has the definition):
+//
+//   grr_u8_blocking, grr_u8_blocking_images    S_b, N_b, S_n, N_n as four exact 64-bit words per image
 #include <algorithm>
 
 #include "grr_common.h"
@@ -341,6 +345,68 @@ __global__ __launch_bounds__(kLumaSseThreads) void u8_luma_sse_kernel(const uint
   }
 }
 
+// ---------------------------------------------------------------------------
+// The blocking sums of PSNR-B (include/grr.h): over the horizontally and vertically adjacent pairs of one channel,
+// the squared differences and the counts of the pairs that straddle a multiple-of-8 line (S_b, N_b) and of the rest
+// (S_n, N_n).  The workgroup and lane shape is the luma SSE's: 2048 consecutive bytes per step, lane t the bytes
+// t + 256 k; a byte owns its pair to the right (the same channel of the next pixel) and its pair below.  Integer
+// adds per lane, per wave, per workgroup, then one 64-bit vector atomic per workgroup and word.
+constexpr int kBlockingThreads = 256;
+constexpr int kBlockingLaneBytes = 8;
+constexpr int kBlockingBytes = kBlockingThreads * kBlockingLaneBytes;   // kernels.BLOCKING_BLOCK
+constexpr int kBlockingMaxBlocks = 1024;                                // kernels.BLOCKING_MAX_BLOCKS: stride beyond
+
+template <typename Src>
+__global__ __launch_bounds__(kBlockingThreads) void u8_blocking_kernel(const uint8_t* __restrict__ p, Src src, int C,
+                                                                       unsigned long long* out) {
+  const SsimImage im = src.image(blockIdx.y);
+  const uint32_t rowlen = (uint32_t)im.W * (uint32_t)C;           // H W C < 2^31: a byte's index fits 32 bits
+  const int64_t n = (int64_t)im.H * rowlen;
+  unsigned long long v[4] = {0, 0, 0, 0};                         // S_b, N_b, S_n, N_n
+  for (int64_t base = (int64_t)blockIdx.x * kBlockingBytes; base < n; base += (int64_t)gridDim.x * kBlockingBytes) {
+#pragma unroll
+    for (int k = 0; k < kBlockingLaneBytes; ++k) {
+      const int64_t e = base + k * kBlockingThreads + threadIdx.x;
+      if (e < n) {
+        const uint32_t y = (uint32_t)e / rowlen, x = ((uint32_t)e - y * rowlen) / (uint32_t)C;
+        const int here = p[src.clamped(im.off + e)];
+        if (x + 1 < (uint32_t)im.W) {
+          const int d = here - (int)p[src.clamped(im.off + e + C)];
+          const bool edge = (x & 7) == 7;
+          v[0] += edge ? (unsigned long long)(d * d) : 0ull;
+          v[1] += edge ? 1 : 0;
+          v[2] += edge ? 0ull : (unsigned long long)(d * d);
+          v[3] += edge ? 0 : 1;
+        }
+        if (y + 1 < (uint32_t)im.H) {
+          const int d = here - (int)p[src.clamped(im.off + e + rowlen)];
+          const bool edge = (y & 7) == 7;
+          v[0] += edge ? (unsigned long long)(d * d) : 0ull;
+          v[1] += edge ? 1 : 0;
+          v[2] += edge ? 0ull : (unsigned long long)(d * d);
+          v[3] += edge ? 0 : 1;
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1) v[j] += __shfl_down(v[j], off, kWave);
+  __shared__ unsigned long long part[4][kBlockingThreads / kWave];
+  if ((threadIdx.x & (kWave - 1)) == 0) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) part[j][threadIdx.x / kWave] = v[j];
+  }
+  __syncthreads();      // every lane arrives: nothing above returns
+  if (threadIdx.x < 4) {
+    unsigned long long s = 0;
+#pragma unroll
+    for (int w = 0; w < kBlockingThreads / kWave; ++w) s += part[threadIdx.x][w];
+    if (s) atomicAdd(out + 4 * (int64_t)blockIdx.y + threadIdx.x, s);
+  }
+}
+
 }  // namespace
 }  // namespace grr
 
@@ -469,6 +535,46 @@ grr_status grr_u8_luma_ssim_images(const uint8_t* a, const uint8_t* b, int64_t a
   luma_ssim_launch(dim3((uint32_t)tiles, (uint32_t)n_img), s, a, b, SsimArena{img_table, arena_elems, max_h, max_w},
                    reinterpret_cast<unsigned long long*>(out));
   return launch_status("grr_u8_luma_ssim_images");
+}
+
+grr_status grr_u8_blocking(const uint8_t* est, int H, int W, int C, uint64_t* out, void* stream) {
+  clear_error();
+  GRR_REQUIRE(est && out && H > 0 && W > 0 && C > 0 && (uintptr_t)out % 8 == 0, GRR_ERR_INVALID_ARG,
+              "grr_u8_blocking: bad args");
+  GRR_REQUIRE(grr_image_io_supported(C, H, W), GRR_ERR_UNSUPPORTED,
+              "grr_u8_blocking: needs C <= 4 and H W C < 2^31 (got %d x %d x %d)", H, W, C);
+  hipStream_t s = (hipStream_t)stream;
+  GRR_REQUIRE(hipMemsetAsync(out, 0, 4 * sizeof(uint64_t), s) == hipSuccess, GRR_ERR_HIP,
+              "grr_u8_blocking: zeroing the sums failed");
+  const int64_t n = (int64_t)H * W * C;
+  const int blocks = (int)std::min<int64_t>((n + kBlockingBytes - 1) / kBlockingBytes, kBlockingMaxBlocks);
+  hipLaunchKernelGGL((u8_blocking_kernel<SsimOne>), dim3(blocks), dim3(kBlockingThreads), 0, s, est, SsimOne{H, W}, C,
+                     reinterpret_cast<unsigned long long*>(out));
+  return launch_status("grr_u8_blocking");
+}
+
+grr_status grr_u8_blocking_images(const uint8_t* est, int64_t arena_elems, int C, const int64_t* img_table, int n_img,
+                                  int max_h, int max_w, uint64_t* out, void* stream) {
+  clear_error();
+  GRR_REQUIRE(est && img_table && out && arena_elems > 0 && C > 0 && n_img > 0 && max_h > 0 && max_w > 0 &&
+                  (uintptr_t)out % 8 == 0 && (uintptr_t)img_table % 8 == 0,
+              GRR_ERR_INVALID_ARG, "grr_u8_blocking_images: bad args");
+  GRR_REQUIRE(grr_image_arena_supported(C, n_img, arena_elems), GRR_ERR_UNSUPPORTED,
+              "grr_u8_blocking_images: needs C <= 4, n_img <= arena_elems < 2^62 (got C %d, %d images, %lld elements)", C,
+              n_img, (long long)arena_elems);
+  GRR_REQUIRE(n_img <= kSsimMaxImages, GRR_ERR_UNSUPPORTED,
+              "grr_u8_blocking_images: at most %d images per call, one grid row each (got %d)", kSsimMaxImages, n_img);
+  GRR_REQUIRE(grr_image_io_supported(C, max_h, max_w), GRR_ERR_UNSUPPORTED,
+              "grr_u8_blocking_images: max_h x max_w x C must be below 2^31 (got %d x %d x %d)", max_h, max_w, C);
+  hipStream_t s = (hipStream_t)stream;
+  GRR_REQUIRE(hipMemsetAsync(out, 0, 4 * sizeof(uint64_t) * n_img, s) == hipSuccess, GRR_ERR_HIP,
+              "grr_u8_blocking_images: zeroing the sums failed");
+  // workgroups per image from the mean image: one step each, at most 256
+  const int64_t bytes = arena_elems / n_img;
+  const int bx = (int)std::min<int64_t>(std::max<int64_t>((bytes + kBlockingBytes - 1) / kBlockingBytes, 1), 256);
+  hipLaunchKernelGGL((u8_blocking_kernel<SsimArena>), dim3(bx, n_img), dim3(kBlockingThreads), 0, s, est,
+                     SsimArena{img_table, arena_elems, max_h, max_w}, C, reinterpret_cast<unsigned long long*>(out));
+  return launch_status("grr_u8_blocking_images");
 }
 
 }  // extern "C"

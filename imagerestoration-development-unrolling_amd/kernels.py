@@ -12,6 +12,7 @@ from typing import List, Optional, Sequence, Tuple
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 from . import _native
@@ -2588,3 +2589,126 @@ def u8_bicubic_degrade_images(pack, s: int):
     out = u8_resize_images(low, s, True, [(h, w) for _, h, w in pack.host_table])
     same = out.host_table == tuple(tuple(int(v) for v in row) for row in pack.host_table)
     return type(out)(out.arena, pack.table, out.host_table, out.c, out.kinds) if same else out
+
+
+# ---------------------------------------------------------------------------
+# The JPEG round trip decode(encode(x)) of uint8 images in libjpeg's integer arithmetic (csrc/jpeg_ops.hip;
+# include/grr.h has the definition) and the blocking sums of PSNR-B (csrc/metric_ops.hip).  The quantisation tables
+# are made from the quality on the device: the library takes the quality itself.
+JPEG_TILE = 32                # a workgroup's rows and columns of the picture
+JPEG_QUALITIES = (1, 100)     # the smallest and the largest quality
+JPEG_SUBSAMPLINGS = (0, 2)    # 4:4:4 and 4:2:0, Pillow's numbering
+MAX_JPEG_IMAGES = 65535       # grr_u8_jpeg_images: one grid row per image
+BLOCKING_BLOCK = 2048         # the bytes a workgroup of the blocking kernel takes per step
+BLOCKING_MAX_BLOCKS = 1024    # workgroups of a single-image call: beyond them each strides over the image
+PSNRB_MIN_SIDE = 16           # PSNR-B is defined for pictures with both sides at least 16
+
+
+def jpeg_ok(c: int, h: int, w: int, sub: int = 0) -> bool:
+    """grr_u8_jpeg_supported in plain Python (tests/test_jpeg_abi.py checks the two agree): C of 1 or 3, a
+    subsampling of 0 or 2, sides >= 1, H W C < 2^31."""
+    return c in (1, 3) and sub in JPEG_SUBSAMPLINGS and h >= 1 and w >= 1 and h * w * c < (1 << 31)
+
+
+def _check_quality(name: str, q) -> int:
+    if isinstance(q, (bool, np.bool_)) or not isinstance(q, (int, np.integer)) \
+            or not JPEG_QUALITIES[0] <= q <= JPEG_QUALITIES[1]:
+        raise ValueError(f"{name}: the quality is an integer of {JPEG_QUALITIES[0]}..{JPEG_QUALITIES[1]}, got {q!r}")
+    return int(q)
+
+
+def _check_subsampling(name: str, sub) -> int:
+    if isinstance(sub, (bool, np.bool_)) or not isinstance(sub, (int, np.integer)) or sub not in JPEG_SUBSAMPLINGS:
+        raise ValueError(f"{name}: the subsampling is 0 (4:4:4) or 2 (4:2:0), got {sub!r}")
+    return int(sub)
+
+
+def u8_jpeg(img: Tensor, quality: int, subsampling: int = 0) -> Tensor:
+    """The JPEG round trip of an H x W x C uint8 device image, C of 1 or 3, at ``quality`` (1..100): what decoding
+    its baseline JPEG gives, byte for byte as libjpeg-turbo (Pillow) computes it, without a bitstream
+    (include/grr.h).  ``subsampling``: 0 for 4:4:4, 2 for 4:2:0 (Pillow's numbering; a gray image has no chroma
+    and ignores it).  One launch.  A non-contiguous image is copied first."""
+    name = "u8_jpeg"
+    quality, sub = _check_quality(name, quality), _check_subsampling(name, subsampling)
+    if isinstance(img, Tensor) and img.dtype != torch.uint8:
+        raise ValueError(f"{name}: the image must be uint8, got {img.dtype}")
+    if isinstance(img, Tensor) and img.dim() == 3 and img.shape[2] not in (1, 3):
+        raise ValueError(f"{name}: needs 1 or 3 channels (gray or R, G, B), got {tuple(img.shape)}")
+    h, w, c = _check_image(name, img)
+    img = img.contiguous()
+    out = torch.empty_like(img)
+    _launch("u8_jpeg", 2 * img.numel(), "grr_u8_jpeg", img.data_ptr(), h, w, c, out.data_ptr(), quality, sub,
+            _stream(img.device))
+    return out
+
+
+def u8_jpeg_images(pack, qualities, subsampling: int = 0):
+    """u8_jpeg of every image of a uint8 image pack into a new pack that shares its image table (so the two can
+    form a patch_pair_source), one launch per 65535 images.  ``qualities``: one integer for all images, a sequence
+    of one integer per image (checked here), or an int32 device tensor of one value per image (which the kernel
+    clamps into 1..100, as it does every device table)."""
+    from .restore import ImagePack
+    name = "u8_jpeg_images"
+    sub = _check_subsampling(name, subsampling)
+    n_img, c = _check_pack(name, pack, placed=False)
+    if pack.arena.dtype != torch.uint8:
+        raise ValueError(f"{name}: the arena must be uint8, got {pack.arena.dtype}")
+    shapes = [(int(h), int(w)) for _, h, w in pack.host_table]
+    for i, (h, w) in enumerate(shapes):
+        if not jpeg_ok(c, h, w, sub):
+            raise ValueError(f"{name}: image {i} needs 1 or 3 channels (gray or R, G, B), got {h} x {w} x {c}")
+    dev = pack.arena.device
+    if not isinstance(qualities, Tensor):       # the host list is checked before anything is asked of the device
+        if isinstance(qualities, (int, np.integer)) and not isinstance(qualities, (bool, np.bool_)):
+            qualities = [qualities] * n_img
+        if len(qualities) != n_img:
+            raise ValueError(f"{name}: {len(qualities)} qualities for {n_img} images")
+        qualities = [_check_quality(name, v) for v in qualities]
+    _check_placed(name, pack)
+    if isinstance(qualities, Tensor):
+        if qualities.dtype != torch.int32 or tuple(qualities.shape) != (n_img,) or qualities.device != dev \
+                or not qualities.is_contiguous():
+            raise ValueError(f"{name}: a quality tensor is int32 [{n_img}], contiguous and on the arena's device")
+        q = qualities
+    else:
+        q = torch.tensor(qualities, dtype=torch.int32).to(dev)
+    covered = sum(h * w * c for h, w in shapes) == pack.arena.numel()
+    arena = (torch.empty_like if covered else torch.zeros_like)(pack.arena)      # bytes between images stay 0
+    for at in range(0, n_img, MAX_JPEG_IMAGES):
+        n = min(MAX_JPEG_IMAGES, n_img - at)
+        part = shapes[at:at + n]
+        _launch("u8_jpeg_images", 2 * sum(h * w * c for h, w in part), "grr_u8_jpeg_images", pack.arena.data_ptr(),
+                pack.arena.numel(), c, pack.table.data_ptr() + at * 24, n, max(h for h, _ in part),
+                max(w for _, w in part), arena.data_ptr(), q.data_ptr() + at * 4, sub, _stream(dev))
+    return ImagePack(arena, pack.table, tuple(tuple(int(v) for v in row) for row in pack.host_table), c,
+                     tuple(getattr(pack, "kinds", ())))
+
+
+def u8_blocking(est: Tensor) -> Tuple[int, int, int, int]:
+    """(S_b, N_b, S_n, N_n) of an H x W x C uint8 device image (include/grr.h, PSNR-B): the sums of squared
+    differences and the counts of the adjacent same-channel pairs that straddle a multiple-of-8 line and of those
+    that do not, exact Python ints (synchronises)."""
+    name = "u8_blocking"
+    if isinstance(est, Tensor) and est.dtype != torch.uint8:
+        raise ValueError(f"{name}: the image must be uint8, got {est.dtype}")
+    h, w, c = _check_image(name, est)
+    est = est.contiguous()
+    out = torch.empty(4, dtype=torch.int64, device=est.device)
+    _launch("u8_blocking", est.numel(), "grr_u8_blocking", est.data_ptr(), h, w, c, out.data_ptr(), _stream(est.device))
+    return tuple(int(v) for v in out.tolist())
+
+
+def u8_blocking_images(pack) -> List[Tuple[int, int, int, int]]:
+    """[u8_blocking of image i of a uint8 pack for each i] in one launch (synchronises)."""
+    name = "u8_blocking_images"
+    n_img, c = _check_pack(name, pack)
+    if pack.arena.dtype != torch.uint8:
+        raise ValueError(f"{name}: the arena must be uint8, got {pack.arena.dtype}")
+    if n_img > MAX_SSIM_IMAGES:
+        raise ValueError(f"{name}: 1..{MAX_SSIM_IMAGES} images per call (got {n_img})")
+    a = pack.arena
+    out = torch.empty((n_img, 4), dtype=torch.int64, device=a.device)
+    _launch("u8_blocking_images", a.numel(), "grr_u8_blocking_images", a.data_ptr(), a.numel(), c,
+            pack.table.data_ptr(), n_img, max(int(h) for _, h, _ in pack.host_table),
+            max(int(w) for _, _, w in pack.host_table), out.data_ptr(), _stream(a.device))
+    return [tuple(int(v) for v in row) for row in out.tolist()]

@@ -53,10 +53,16 @@ integer scale on the device with the exact fixed-point bicubic of include/grr.h 
 ``evaluate_sr`` runs the protocol of the super-resolution tables on clean pictures: mod-crop, degrade, restore, shave,
 score.  The filter stays same-size-in, same-size-out: its input is the picture brought back to size by the bicubic.
 
+JPEG compression-artifact removal: ``jpeg_degrade_u8`` is the JPEG round trip at a quality of 1..100 on the device
+(``kernels.u8_jpeg``: libjpeg's integer arithmetic without a bitstream, Pillow's bytes), ``psnrb_u8`` the PSNR-B of a
+picture against its reference (the "psnrb" metric of evaluate_metrics and evaluate_pairs), and ``evaluate_car``
+degrades clean pictures, restores them and scores them.
+
 Single process: several ranks are ``tiling.tiled_forward``'s business.
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from functools import partial
 from typing import Callable, List, Sequence, Tuple
@@ -507,8 +513,45 @@ def ssim_y_u8(a, b) -> float:
     return _ssim(kernels.u8_luma_ssim(ta, tb), kernels.luma_ssim_count(ta.shape[0], ta.shape[1]))
 
 
+def _psnrb(sse: int, h: int, w: int, c: int, sums) -> float:
+    """PSNR-B from the exact integers: D_b = S_b / N_b and D_n = S_n / N_n are single true divisions of Python ints,
+    BEF = (3 / log2 min(H, W)) (D_b - D_n) where D_b > D_n, else 0; 10 log10(255^2 / (SSE / (H W C) + BEF)) in
+    float64, inf for a zero denominator."""
+    sb, nb, sn, nn = sums
+    db, dn = sb / nb, sn / nn
+    bef = 3.0 / math.log2(min(h, w)) * (db - dn) if db > dn else 0.0
+    den = sse / (h * w * c) + bef
+    return float("inf") if den == 0 else 10.0 * math.log10(255.0 ** 2 / den)
+
+
+def _check_psnrb_shape(who: str, what: str, shape) -> None:
+    shape = tuple(shape)
+    if len(shape) != 3 or min(shape[:2]) < kernels.PSNRB_MIN_SIDE:
+        raise ValueError(f"{who}: {what} is {shape}; PSNR-B needs an H x W x C image with both sides at least "
+                         f"{kernels.PSNRB_MIN_SIDE}")
+
+
+def psnrb_u8(est, ref) -> float:
+    """PSNR-B (Yim and Bovik) of the uint8 H x W x C picture ``est`` against ``ref`` of the same shape (numpy or
+    tensor, host or device), both sides at least 16: the PSNR with the blocking effect factor of ``est`` on the
+    8 x 8 grid from (0, 0) added to the mean squared error (include/grr.h has the definition; the pair counts are
+    the true numbers of pairs).  From exact integers -- kernels.u8_sse and kernels.u8_blocking -- so it does not
+    depend on any summation order; inf for equal pictures without blocking.  Not symmetric: the factor is ``est``'s."""
+    for t in (est, ref):
+        if not (isinstance(t, (np.ndarray, torch.Tensor)) and t.dtype in (np.uint8, torch.uint8)):
+            raise ValueError(f"psnrb_u8: expected uint8 images, got {getattr(t, 'dtype', type(t).__name__)}")
+    if tuple(est.shape) != tuple(ref.shape):
+        raise ValueError(f"psnrb_u8: shapes differ ({tuple(est.shape)} vs {tuple(ref.shape)})")
+    _check_psnrb_shape("psnrb_u8", "the picture", est.shape)
+    ta, tb = _u8_pair("psnrb_u8", est, ref)
+    h, w, c = ta.shape
+    return _psnrb(kernels.u8_sse(ta, tb), h, w, c, kernels.u8_blocking(ta))
+
+
 METRICS = ("psnr", "ssim", "psnr_y", "ssim_y")
-_SCORE = {"psnr": psnr_u8, "ssim": ssim_u8, "psnr_y": psnr_y_u8, "ssim_y": ssim_y_u8}      # per image, by name
+BLOCKING_METRICS = ("psnrb",)       # beside them: the metric of compression-artifact removal
+_SCORE = {"psnr": psnr_u8, "ssim": ssim_u8, "psnr_y": psnr_y_u8, "ssim_y": ssim_y_u8,      # per image, by name
+          "psnrb": psnrb_u8}
 
 
 def _check_metric_shape(who: str, what: str, shape, metrics) -> None:
@@ -520,14 +563,16 @@ def _check_metric_shape(who: str, what: str, shape, metrics) -> None:
                          f"least {kernels.SSIM_WINDOW}")
     if ("psnr_y" in metrics or "ssim_y" in metrics) and (len(shape) != 3 or shape[2] != 3):
         raise ValueError(f"{who}: {what} is {shape}; the Y-channel metrics need an H x W x 3 image (R, G, B)")
+    if "psnrb" in metrics:
+        _check_psnrb_shape(who, what, shape)
 
 
 def _evaluate_args(who: str, model: Callable, ensemble, metrics, tiling_args: dict):
     """(modes, metrics, device, tile, halo, micro_batch) of an evaluate call, checked; tiling_args is emptied."""
     modes = _ensemble_modes(who, ensemble)
     metrics = (metrics,) if isinstance(metrics, str) else tuple(metrics)
-    if not metrics or any(m not in METRICS for m in metrics) or len(set(metrics)) != len(metrics):
-        raise ValueError(f"{who}: metrics are distinct names of {METRICS}, got {metrics!r}")
+    if not metrics or any(m not in METRICS + BLOCKING_METRICS for m in metrics) or len(set(metrics)) != len(metrics):
+        raise ValueError(f"{who}: metrics are distinct names of {METRICS + BLOCKING_METRICS}, got {metrics!r}")
     device = tiling_args.pop("device", None) or _model_device(model)
     tile, halo = tiling_args.pop("tile", TILE), tiling_args.pop("halo", HALO)
     micro_batch = tiling_args.pop("micro_batch", MICRO_BATCH)
@@ -618,6 +663,11 @@ def _score_packs(who: str, restored: ImagePack, clean_u8: ImagePack, metrics) ->
     if "ssim_y" in metrics:
         qs = kernels.u8_luma_ssim_images(restored, clean_u8)
         values["ssim_y"] = [_ssim(q, kernels.luma_ssim_count(h, w)) for q, (_, h, w) in zip(qs, restored.host_table)]
+    if "psnrb" in metrics:
+        offsets = [off for off, _, _ in restored.host_table] + [restored.arena.numel()]
+        sses = kernels.u8_sse_segments(restored.arena, clean_u8.arena, offsets)
+        values["psnrb"] = [_psnrb(sse, h, w, restored.c, sums) for sse, sums, (_, h, w) in
+                           zip(sses, kernels.u8_blocking_images(restored), restored.host_table)]
     return values
 
 
@@ -707,6 +757,62 @@ def evaluate_sr(model: Callable, images, scale: int, shave: int = None, factor: 
             h, w = clean.shape[:2]
             restored = restored[shave:h - shave, shave:w - shave].contiguous()
             clean = clean[shave:h - shave, shave:w - shave].contiguous()
+        for m in metrics:
+            values[m].append(_SCORE[m](restored, clean))
+    return {m: (float(np.mean(values[m])), values[m]) for m in metrics}
+
+
+def jpeg_degrade_u8(a, quality: int, subsampling: int = 0):
+    """The JPEG round trip of the uint8 H x W x C picture ``a`` (numpy array or tensor, C of 1 or 3) at ``quality``
+    (1..100), on the GPU: what decoding its baseline JPEG gives, byte for byte as Pillow (libjpeg-turbo) computes
+    it, without a bitstream (kernels.u8_jpeg; include/grr.h has the definition).  ``subsampling``: 0 for 4:4:4, 2 for
+    4:2:0.  training.jpeg_degrade_u8 gives the same bytes on the CPU."""
+    quality = kernels._check_quality("jpeg_degrade_u8", quality)           # before any transfer
+    subsampling = kernels._check_subsampling("jpeg_degrade_u8", subsampling)
+    return _resized_u8("jpeg_degrade_u8", a, lambda t: kernels.u8_jpeg(t, quality, subsampling))
+
+
+def evaluate_car(model: Callable, images, quality: int, subsampling: int = 0, factor: int = 16, ensemble=1,
+                 metrics=("psnr", "ssim", "psnrb"), **tiling_args) -> dict:
+    """Score ``model`` on JPEG compression-artifact removal (the protocol of the LIVE1 / Classic5 / BSDS500 tables)
+    over clean uint8 H x W x C pictures (numpy arrays or tensors, host or device; C of 1 or 3).  Per picture: the
+    JPEG round trip at ``quality`` on the device (kernels.u8_jpeg), the degraded picture restored as
+    ``restore_image(..., quantise=True)`` does, and the result scored against the clean picture with the
+    exact-integer kernels.  Returns {metric: (mean, per-image values)} as evaluate_pairs does; it is
+    evaluate_pairs(model, degraded, clean) bit for bit.  tiling_args: tile, halo, micro_batch, device; ``ensemble`` as
+    in restore_image.
+
+    Everything is checked before any launch: the quality (1..100), the subsampling (0 or 2), uint8 pictures of 1 or
+    3 channels, and what the metrics need of a picture (SSIM: both sides at least 11; PSNR-B: at least 16; the
+    Y-channel metrics: 3 channels)."""
+    who = "evaluate_car"
+    modes, metrics, device, tile, halo, micro_batch = _evaluate_args(who, model, ensemble, metrics, tiling_args)
+    quality = kernels._check_quality(who, quality)
+    subsampling = kernels._check_subsampling(who, subsampling)
+    if len(images) < 1:
+        raise ValueError(f"{who}: no images")
+    cleans = []
+    for i in range(len(images)):
+        try:
+            t, _ = _checked_image(images[i])
+        except ValueError as e:
+            raise ValueError(f"{who}: image {i}: {e}") from None
+        if t.dtype != torch.uint8:
+            raise ValueError(f"{who}: image {i} is {t.dtype}; JPEG is defined on uint8 pictures")
+        if not kernels.jpeg_ok(t.shape[2], t.shape[0], t.shape[1], subsampling):
+            raise ValueError(f"{who}: image {i} is {tuple(t.shape)}; JPEG takes 1 or 3 channels (gray or R, G, B)")
+        _check_metric_shape(who, f"image {i}", t.shape, metrics)
+        plan(t.shape[0], t.shape[1], factor, tile, halo)                          # raises what the restoration would
+        cleans.append(t)
+    if device is None:
+        device = next((t.device for t in cleans if t.is_cuda), None)
+    values = {m: [] for m in metrics}
+    for t in cleans:
+        clean = _to_device(t, device)
+        restored = _restore_device(model, kernels.u8_jpeg(clean, quality, subsampling), None, factor, tile, halo,
+                                   micro_batch, True, modes)
+        if restored.shape != clean.shape:
+            raise ValueError(f"{who}: the model returns {restored.shape[2]} channel(s) for {clean.shape[2]}; no score")
         for m in metrics:
             values[m].append(_SCORE[m](restored, clean))
     return {m: (float(np.mean(values[m])), values[m]) for m in metrics}

@@ -35,6 +35,10 @@ and ``validate_pairs`` scores them with restore.evaluate_pairs.
 degraded by the exact bicubic down and up at an integer scale (``bicubic_degrade_u8`` on the host; on the device
 csrc/resize_ops.hip makes the degraded arena from the clean one), and ``validate_sr`` scores the protocol on a
 ``TestImagesCSV`` set with restore.evaluate_sr.
+``JpegArtifactRemoval`` is the same over clean files for JPEG compression-artifact removal: the input is the picture
+after the JPEG round trip at a quality of 1..100 (``jpeg_degrade_u8`` on the host, Pillow's bytes; on the device
+csrc/jpeg_ops.hip makes the degraded arena), and ``validate_car`` scores it on a ``TestImagesCSV`` set with a
+``jpeg_quality`` key through restore.evaluate_car.
 """
 from __future__ import annotations
 
@@ -421,28 +425,145 @@ def bicubic_degrade_u8(a: np.ndarray, s: int) -> np.ndarray:
     return _bicubic_resize_u8(_bicubic_resize_u8(a, s, None), s, a.shape[:2])
 
 
-class BicubicSuperResolution(ImageSuperResolution):
-    """Bicubic super-resolution pairs synthesised from clean files under ImageSuperResolution's csv, crop and patch
-    plan and draws: the input of a sample is the same patch of the whole picture degraded by ``scale`` (2..8) --
-    the exact antialiased bicubic down and the bicubic back up to the picture's size, bicubic_degrade_u8 -- and the
-    target the clean patch.  ``dist_mode``: "none" (default), or one of the parent's three additive modes, whose
-    noise is added on top of the degraded patch as in PairedImageRestoration.  ``__getitem__`` is the host path:
-    it degrades the decoded picture with numpy (the last CACHE pictures are kept), makes the parent's draws in the
-    parent's order and returns (input, target) float32 HWC, cut and turned alike.  A DevicePatchLoader decodes only
-    the clean files and makes the degraded arena on the GPU."""
+_JPEG_LUMA = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56,
+              14, 17, 22, 29, 51, 87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92,
+              49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99)
+_JPEG_CHROMA = (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99,
+                47, 66, 99, 99, 99, 99, 99, 99) + (99,) * 32
+
+
+def jpeg_quality_table(quality: int, chroma: bool = False) -> np.ndarray:
+    """The int64 8 x 8 quantisation table of ``quality`` (1..100) in natural order: libjpeg's scaling of the
+    Annex-K luminance (or chrominance) table, clamp((base scale + 50) / 100, 1, 255) with scale = 5000 / q below 50
+    and 200 - 2 q from 50 on.  100 gives all ones, 50 the base table."""
+    if isinstance(quality, (bool, np.bool_)) or not isinstance(quality, (int, np.integer)) or not 1 <= quality <= 100:
+        raise ValueError(f"jpeg_quality_table: the quality is an integer of 1..100, got {quality!r}")
+    q = int(quality)
+    scale = 5000 // q if q < 50 else 200 - 2 * q
+    base = np.array(_JPEG_CHROMA if chroma else _JPEG_LUMA, np.int64).reshape(8, 8)
+    return np.clip((base * scale + 50) // 100, 1, 255)
+
+
+def _jpeg_odd(a, b, c, d):
+    """The odd part jfdctint and jidctint share (include/grr.h, ODD)."""
+    z5 = 9633 * (a + b + c + d)
+    z1, z2, z3, z4 = -7373 * (a + d), -20995 * (b + c), z5 - 16069 * (a + c), z5 - 3196 * (b + d)
+    return 2446 * a + z1 + z3, 16819 * b + z2 + z4, 25172 * c + z2 + z3, 12299 * d + z1 + z4
+
+
+def _jpeg_pass(x: np.ndarray, axis: int, inverse: bool, shift: int, dc_shift: int) -> np.ndarray:
+    """One 1-D pass of the integer DCT along ``axis`` (of length 8) of an int64 array: the forward pass rounds
+    outputs 0 and 4 by ``dc_shift`` (negative: a left shift) and the others by ``shift``; the inverse rounds all by
+    ``shift``."""
+    d = np.moveaxis(x, axis, 0)
+    rnd = lambda v, n: (v + (1 << (n - 1))) >> n
+    out = np.empty_like(d)
+    if inverse:
+        z1 = 4433 * (d[2] + d[6])
+        t2, t3 = z1 - 15137 * d[6], z1 + 6270 * d[2]
+        t0, t1 = (d[0] + d[4]) << 13, (d[0] - d[4]) << 13
+        even = (t0 + t3, t1 + t2, t1 - t2, t0 - t3)
+        odd = _jpeg_odd(d[7], d[5], d[3], d[1])
+        for k in range(4):
+            out[k], out[7 - k] = rnd(even[k] + odd[3 - k], shift), rnd(even[k] - odd[3 - k], shift)
+    else:
+        t = [d[k] + d[7 - k] for k in range(4)] + [d[3 - k] - d[4 + k] for k in range(4)]     # t0..t3, t4..t7
+        t10, t13, t11, t12 = t[0] + t[3], t[0] - t[3], t[1] + t[2], t[1] - t[2]
+        for k, v in ((0, t10 + t11), (4, t10 - t11)):
+            out[k] = v << -dc_shift if dc_shift < 0 else rnd(v, dc_shift)
+        z1 = 4433 * (t12 + t13)
+        out[2], out[6] = rnd(z1 + 6270 * t13, shift), rnd(z1 - 15137 * t12, shift)
+        for k, v in zip((7, 5, 3, 1), _jpeg_odd(t[4], t[5], t[6], t[7])):
+            out[k] = rnd(v, shift)
+    return np.moveaxis(out, 0, axis)
+
+
+def _jpeg_plane(p: np.ndarray, table: np.ndarray) -> np.ndarray:
+    """An int64 [h, w] plane of samples 0..255 through the forward DCT, the quantiser and the inverse DCT."""
+    h, w = p.shape
+    p = np.pad(p, ((0, -h % 8), (0, -w % 8)), mode="edge") - 128
+    b = p.reshape(p.shape[0] // 8, 8, p.shape[1] // 8, 8)            # [block row, row, block column, column]
+    b = _jpeg_pass(_jpeg_pass(b, 3, False, 11, -2), 1, False, 15, 2)
+    tab = table[None, :, None, :]
+    b = np.sign(b) * ((np.abs(b) + 4 * tab) // (8 * tab)) * tab
+    b = _jpeg_pass(_jpeg_pass(b, 1, True, 11, 0), 3, True, 18, 0)
+    return np.clip(b + 128, 0, 255).reshape(p.shape)[:h, :w]
+
+
+def _jpeg_chroma_420(p: np.ndarray, table: np.ndarray) -> np.ndarray:
+    """A full-resolution int64 chroma plane down to 4:2:0, through the codec and back up to its size."""
+    h, w = p.shape
+    ch, cw = -(-h // 2), -(-w // 2)
+    q = np.pad(p, ((0, h % 2), (0, -w % 16)), mode="edge")
+    q = q.reshape(ch, 2, q.shape[1] // 2, 2).sum(axis=(1, 3))
+    q = (q + 1 + (np.arange(q.shape[1]) & 1)) >> 2
+    c = _jpeg_plane(q, table)[:, :cw]
+    if cw <= 2:                                                       # libjpeg's triangle filter is off
+        return c.repeat(2, axis=0).repeat(2, axis=1)[:h, :w]
+    above, below = np.concatenate([c[:1], c[:-1]]), np.concatenate([c[1:], c[-1:]])
+    s = np.stack([3 * c + above, 3 * c + below], axis=1).reshape(2 * ch, cw)      # even rows look up, odd down
+    left = np.concatenate([4 * s[:, :1], 3 * s[:, 1:] + s[:, :-1]], axis=1) + 8
+    right = np.concatenate([3 * s[:, :-1] + s[:, 1:], 4 * s[:, -1:]], axis=1) + 7
+    return (np.stack([left, right], axis=2).reshape(2 * ch, 2 * cw) >> 4)[:h, :w]
+
+
+def jpeg_degrade_u8(a: np.ndarray, quality: int, subsampling: int = 0) -> np.ndarray:
+    """The JPEG round trip of a uint8 H x W x C picture (C of 1 or 3) on the CPU: what decoding its baseline JPEG of
+    ``quality`` (1..100) gives, in libjpeg's integer arithmetic and without a bitstream (include/grr.h) -- the bytes
+    Pillow's ``save(format="JPEG", quality=q, subsampling=s)`` followed by ``open`` returns.  ``subsampling``: 0 for
+    4:4:4, 2 for 4:2:0; a gray picture ignores it.  The same integers as kernels.u8_jpeg, bit for bit: it serves
+    the host DataLoader path and users without a GPU."""
+    a = np.asarray(a)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] not in (1, 3) or 0 in a.shape:
+        raise ValueError(f"jpeg_degrade_u8: expected a uint8 H x W x 1 or H x W x 3 picture, got {a.dtype} {a.shape}")
+    if isinstance(subsampling, (bool, np.bool_)) or not isinstance(subsampling, (int, np.integer)) \
+            or subsampling not in (0, 2):
+        raise ValueError(f"jpeg_degrade_u8: the subsampling is 0 (4:4:4) or 2 (4:2:0), got {subsampling!r}")
+    try:
+        luma, chroma = jpeg_quality_table(quality), jpeg_quality_table(quality, True)
+    except ValueError:
+        raise ValueError(f"jpeg_degrade_u8: the quality is an integer of 1..100, got {quality!r}") from None
+    x = a.astype(np.int64)
+    if a.shape[2] == 1:
+        return _jpeg_plane(x[:, :, 0], luma).astype(np.uint8)[:, :, None]
+    F = lambda v: int(v * 65536 + 0.5)
+    r, g, b = x[:, :, 0], x[:, :, 1], x[:, :, 2]
+    y = (F(.299) * r + F(.587) * g + F(.114) * b + 32768) >> 16
+    cb = (-F(.16874) * r - F(.33126) * g + F(.5) * b + (128 << 16) + 32767) >> 16
+    cr = (F(.5) * r - F(.41869) * g - F(.08131) * b + (128 << 16) + 32767) >> 16
+    code = _jpeg_chroma_420 if subsampling == 2 else _jpeg_plane
+    y, cb, cr = _jpeg_plane(y, luma), code(cb, chroma) - 128, code(cr, chroma) - 128
+    out = np.stack([y + ((F(1.402) * cr + 32768) >> 16), y + ((-F(.34414) * cb - F(.71414) * cr + 32768) >> 16),
+                    y + ((F(1.772) * cb + 32768) >> 16)], axis=2)
+    return np.clip(out, 0, 255).astype(np.uint8)
+
+
+class _DegradedFromClean(ImageSuperResolution):
+    """Pairs synthesised from clean files under ImageSuperResolution's csv, crop and patch plan and draws: the input
+    of a sample is the same patch of the whole picture degraded (``degrade_host``), the target the clean patch.
+    ``dist_mode``: "none" (default), or one of the parent's three additive modes, whose noise is added on top of the
+    degraded patch as in PairedImageRestoration.  ``__getitem__`` is the host path: it degrades the decoded picture
+    with numpy (the last CACHE pictures are kept), makes the parent's draws in the parent's order and returns (input,
+    target) float32 HWC, cut and turned alike.  A DevicePatchLoader decodes only the clean files and makes the
+    degraded arena on the GPU: ``degrade_pack`` of the clean pack, under ``synthetic_key`` in a shared store."""
 
     DIST_MODES = ("none",) + ImageSuperResolution.DIST_MODES
     CACHE = 4
 
-    def __init__(self, csv_path, scale, dist_mode="none", lambda_noise=None, use_data_aug=False, patch_size=(64, 64),
-                 max_num_patchs=100000, root_folder="", logger=None, device=None, seed=2204, n_channels=3):
-        if isinstance(scale, bool) or not isinstance(scale, int) or not 2 <= scale <= 8:
-            raise ValueError(f"BicubicSuperResolution: scale is an integer of 2..8, got {scale!r}")
-        self.scale = scale
-        self._degraded = {}          # image index -> (clean, degraded), the last CACHE decoded
-        super().__init__(csv_path, dist_mode, lambda_noise, use_data_aug=use_data_aug, patch_size=patch_size,
-                         max_num_patchs=max_num_patchs, root_folder=root_folder, logger=logger, device=device,
-                         seed=seed, n_channels=n_channels)
+    def __init__(self, csv_path, dist_mode, lambda_noise, **kwargs):
+        self._degraded = {}          # image index -> (degraded, clean), the last CACHE decoded
+        super().__init__(csv_path, dist_mode, lambda_noise, **kwargs)
+
+    def degrade_host(self, img: int, clean: np.ndarray) -> np.ndarray:
+        raise NotImplementedError
+
+    def degrade_pack(self, pack, used: Sequence[int]):
+        """The degraded pack of the clean pack of the files ``used``, sharing its image table."""
+        raise NotImplementedError
+
+    def synthetic_key(self, used: Sequence[int]) -> tuple:
+        """What tells this degradation of the files ``used`` from any other."""
+        raise NotImplementedError
 
     def load_pair(self, img: int) -> Tuple[np.ndarray, np.ndarray]:
         """(degraded, clean) of file ``img`` as uint8 H x W x n_channels."""
@@ -450,7 +571,7 @@ class BicubicSuperResolution(ImageSuperResolution):
             while len(self._degraded) >= self.CACHE:
                 self._degraded.pop(next(iter(self._degraded)))
             clean = self.load_image(img)
-            self._degraded[img] = (bicubic_degrade_u8(clean, self.scale), clean)
+            self._degraded[img] = (self.degrade_host(img, clean), clean)
         return self._degraded[img]
 
     def __getitem__(self, idx):
@@ -464,6 +585,88 @@ class BicubicSuperResolution(ImageSuperResolution):
         if self.dist_mode != "none":
             inp = _noisy(inp, self.random_state, self.dist_mode, self.lambda_noise)
         return torch.from_numpy(inp), torch.from_numpy(tgt)
+
+
+class BicubicSuperResolution(_DegradedFromClean):
+    """Bicubic super-resolution pairs synthesised from clean files under ImageSuperResolution's csv, crop and patch
+    plan and draws: the input of a sample is the same patch of the whole picture degraded by ``scale`` (2..8) --
+    the exact antialiased bicubic down and the bicubic back up to the picture's size, bicubic_degrade_u8 -- and the
+    target the clean patch.  ``dist_mode``: "none" (default), or one of the parent's three additive modes, whose
+    noise is added on top of the degraded patch as in PairedImageRestoration.  ``__getitem__`` is the host path:
+    it degrades the decoded picture with numpy (the last CACHE pictures are kept), makes the parent's draws in the
+    parent's order and returns (input, target) float32 HWC, cut and turned alike.  A DevicePatchLoader decodes only
+    the clean files and makes the degraded arena on the GPU."""
+
+    def __init__(self, csv_path, scale, dist_mode="none", lambda_noise=None, use_data_aug=False, patch_size=(64, 64),
+                 max_num_patchs=100000, root_folder="", logger=None, device=None, seed=2204, n_channels=3):
+        if isinstance(scale, bool) or not isinstance(scale, int) or not 2 <= scale <= 8:
+            raise ValueError(f"BicubicSuperResolution: scale is an integer of 2..8, got {scale!r}")
+        self.scale = scale
+        super().__init__(csv_path, dist_mode, lambda_noise, use_data_aug=use_data_aug, patch_size=patch_size,
+                         max_num_patchs=max_num_patchs, root_folder=root_folder, logger=logger, device=device,
+                         seed=seed, n_channels=n_channels)
+
+    def degrade_host(self, img, clean):
+        return bicubic_degrade_u8(clean, self.scale)
+
+    def degrade_pack(self, pack, used):
+        from . import kernels
+        return kernels.u8_bicubic_degrade_images(pack, self.scale)
+
+    def synthetic_key(self, used):
+        return ("bicubic", self.scale)
+
+
+class JpegArtifactRemoval(_DegradedFromClean):
+    """JPEG compression-artifact-removal pairs synthesised from clean files under ImageSuperResolution's csv, crop
+    and patch plan and draws: the input of a sample is the same patch of the whole picture after the JPEG round trip
+    (jpeg_degrade_u8: decode(encode(picture)) in libjpeg's integer arithmetic), the target the clean patch.
+    ``quality``: an integer of 1..100 for every file, or ``[levels, probabilities]`` as ``lambda_noise`` of
+    vary_addictive_noise is; the quality of file i is then drawn once, in file order, from RandomState(seed), so it
+    is a function of (seed, file) alone and is fixed for the run -- it is not drawn again per epoch or per patch
+    (``qualities`` lists them).  ``subsampling``: 0 (4:4:4) or 2 (4:2:0); gray pictures ignore it.  ``dist_mode``
+    defaults to "none"; the additive modes add their noise on top of the degraded patch.  A DevicePatchLoader
+    decodes only the clean files and makes the degraded arena on the GPU (kernels.u8_jpeg_images)."""
+
+    def __init__(self, csv_path, quality, subsampling=0, dist_mode="none", lambda_noise=None, use_data_aug=False,
+                 patch_size=(64, 64), max_num_patchs=100000, root_folder="", logger=None, device=None, seed=2204,
+                 n_channels=3):
+        who = "JpegArtifactRemoval"
+        ok = lambda q: isinstance(q, (int, np.integer)) and not isinstance(q, (bool, np.bool_)) and 1 <= q <= 100
+        if isinstance(quality, (list, tuple)):
+            if len(quality) != 2 or len(quality[0]) < 1 or len(quality[0]) != len(quality[1]) \
+                    or not all(ok(q) for q in quality[0]):
+                raise ValueError(f"{who}: quality is an integer of 1..100 or [levels, probabilities] with as many "
+                                 f"probabilities as levels of 1..100, got {quality!r}")
+        elif not ok(quality):
+            raise ValueError(f"{who}: quality is an integer of 1..100 or [levels, probabilities], got {quality!r}")
+        if isinstance(subsampling, bool) or subsampling not in (0, 2):
+            raise ValueError(f"{who}: subsampling is 0 (4:4:4) or 2 (4:2:0), got {subsampling!r}")
+        if n_channels not in (1, 3):
+            raise ValueError(f"{who}: JPEG is defined for 1 or 3 channels, got n_channels {n_channels}")
+        self.quality, self.subsampling = quality, int(subsampling)
+        super().__init__(csv_path, dist_mode, lambda_noise, use_data_aug=use_data_aug, patch_size=patch_size,
+                         max_num_patchs=max_num_patchs, root_folder=root_folder, logger=logger, device=device,
+                         seed=seed, n_channels=n_channels)
+
+    def create_all_images(self):
+        super().create_all_images()
+        n = len(self.paths)
+        if isinstance(self.quality, (list, tuple)):
+            drawn = np.random.RandomState(self.seed).choice(self.quality[0], p=self.quality[1], size=n)
+            self.qualities = [int(q) for q in drawn]
+        else:
+            self.qualities = [int(self.quality)] * n
+
+    def degrade_host(self, img, clean):
+        return jpeg_degrade_u8(clean, self.qualities[img], self.subsampling)
+
+    def degrade_pack(self, pack, used):
+        from . import kernels
+        return kernels.u8_jpeg_images(pack, [self.qualities[i] for i in used], self.subsampling)
+
+    def synthetic_key(self, used):
+        return ("jpeg", tuple(self.qualities[i] for i in used), self.subsampling)
 
 
 class DevicePatchLoader:
@@ -490,7 +693,10 @@ class DevicePatchLoader:
 
     A BicubicSuperResolution dataset yields (input, target) by the paired path as well, but only its clean files are
     decoded: the degraded arena is made from the clean one on the device (kernels.u8_bicubic_degrade_images, once, in
-    ``prepare``) and shares its image table.  The host never holds a degraded picture."""
+    ``prepare``) and shares its image table.  The host never holds a degraded picture.  A JpegArtifactRemoval dataset
+    goes the same way with kernels.u8_jpeg_images at each file's quality: the switch is the datasets' common base
+    class, whose ``degrade_pack`` makes the arena and whose ``synthetic_key`` tells one degradation from another in a
+    shared store."""
     channels_first = True
     CHUNK_BYTES = 256 << 20      # decoded pictures staged on the host per transfer
 
@@ -505,7 +711,7 @@ class DevicePatchLoader:
         self.dataset, self.sampler, self.batch_size, self.drop_last = dataset, sampler, int(batch_size), bool(drop_last)
         self.device = device
         self.shared = shared
-        self.synthetic = isinstance(dataset, BicubicSuperResolution)     # the input arena is made on the device
+        self.synthetic = isinstance(dataset, _DegradedFromClean)         # the input arena is made on the device
         self.paired = self.synthetic or isinstance(dataset, PairedImageRestoration)
         self.source = None           # kernels.PatchSource (PatchPairSource if paired): the arena(s), checked once
         self._draws = (None, None, None)
@@ -562,14 +768,14 @@ class DevicePatchLoader:
             self._slot = slot
             key = (tuple(ds.paths[i] for i in used), ds.n_channels, str(dev))
             if self.synthetic:
-                key += ("bicubic", ds.scale)
+                key += ds.synthetic_key(used)
             elif self.paired:    # both arenas under one key: a curriculum decodes each file once
                 key += (tuple(ds.target_paths[i] for i in used),)
             store = self.shared if self.shared is not None else {}
             if key not in store:
                 packs = self._pack(used, dev)
                 if self.synthetic:
-                    packs = (kernels.u8_bicubic_degrade_images(packs[0], ds.scale), packs[0])
+                    packs = (ds.degrade_pack(packs[0], used), packs[0])
                 store[key] = kernels.patch_pair_source(*packs) if self.paired else kernels.patch_source(*packs)
             self.source = store[key]
         return (self.source.input, self.source.target) if self.paired else self.source.pack
@@ -623,7 +829,7 @@ class DevicePatchLoader:
 
 
 DATASETS = {c.__name__: c for c in (AddictiveGaussianNoiseImagePair, SyntheticNoisyPatches, ImageSuperResolution,
-                                    PairedImageRestoration, BicubicSuperResolution)}
+                                    PairedImageRestoration, BicubicSuperResolution, JpegArtifactRemoval)}
 
 
 # ---------------------------------------------------------------------------
@@ -816,18 +1022,62 @@ def validate_sr(model: nn.Module, images, scale: int, shave: Optional[int] = Non
     return float(acc[0] / acc[1])
 
 
+VAL_CAR_METRICS = ("psnr", "psnr_y", "psnrb")
+
+
+def validate_car(model: nn.Module, images, jpeg_quality: int, subsampling: int = 0, factor: int = 16, device=None,
+                 metric: str = "psnr", **tiling_args) -> float:
+    """Mean score of ``model`` on JPEG compression-artifact removal over clean test pictures (``images[i]``: uint8
+    H x W x C, or float32 in [0, 1] on the uint8 grid as TestImagesCSV yields them): restore.evaluate_car on this
+    rank's share -- the JPEG round trip at ``jpeg_quality`` on the device, restore, score against the clean picture.
+    ``metric``: "psnr" (default), "psnr_y" or "psnrb" (PSNR-B).  Nothing is drawn.  tiling_args: tile, halo,
+    micro_batch, ensemble.
+
+    Several ranks: sharded and all-reduced as validate_pairs does."""
+    from . import restore
+    if metric not in VAL_CAR_METRICS:
+        raise ValueError(f"validate_car: metric is one of {VAL_CAR_METRICS}, got {metric!r}")
+    rank, world = sharding.world()
+    if device is None:
+        device = next(model.parameters()).device
+    s, e = sharding.shard_range(len(images), rank, world)
+    mine = []
+    for i in range(s, e):
+        a = np.asarray(images[i])
+        a = a[:, :, None] if a.ndim == 2 else a
+        mine.append(a if a.dtype == np.uint8 else np.rint(a.astype(np.float64) * 255.0).astype(np.uint8))
+    scores = restore.evaluate_car(model, mine, jpeg_quality, subsampling=subsampling, factor=factor, device=device,
+                                  metrics=(metric,), **tiling_args)[metric][1] if mine else []
+    acc = torch.tensor([float(np.sum(scores)), float(len(scores))], dtype=torch.float64)
+    if world > 1:
+        if torch.distributed.get_backend() == "nccl":
+            acc = acc.to(device)
+        torch.distributed.all_reduce(acc)
+    return float(acc[0] / acc[1])
+
+
 def create_val_dataset(conf: dict):
     """``datasets.val`` of the YAML ({type, dataset_args, sigma, factor}), or None.  A paired set (TestPairsCSV)
     takes {type, dataset_args, factor, tile, halo, micro_batch, metric}: validate_pairs' arguments, no sigma; without
     ``metric`` validate_pairs' default, the RGB PSNR, is scored.  TestImagesCSV with a ``scale`` key is the bicubic
     super-resolution protocol: {type, dataset_args, scale, shave, factor, tile, halo, micro_batch, metric},
-    validate_sr's arguments, no sigma."""
+    validate_sr's arguments, no sigma.  TestImagesCSV with a ``jpeg_quality`` key is JPEG artifact removal:
+    {type, dataset_args, jpeg_quality, subsampling, factor, tile, halo, micro_batch, metric}, validate_car's
+    arguments, no sigma."""
     vconf = conf.get("datasets", {}).get("val")
     if not vconf:
         return None, {}
     cls = VAL_DATASETS.get(vconf["type"])
     if cls is None:
         raise ValueError(f"Validation dataset {vconf['type']} is not found.")
+    if cls is TestImagesCSV and vconf.get("jpeg_quality") is not None:
+        args = {k: int(vconf[k]) for k in ("tile", "halo", "micro_batch", "subsampling") if vconf.get(k) is not None}
+        if vconf.get("metric") is not None:
+            if vconf["metric"] not in VAL_CAR_METRICS:
+                raise ValueError(f"datasets.val.metric is one of {VAL_CAR_METRICS}, got {vconf['metric']!r}")
+            args["metric"] = str(vconf["metric"])
+        return cls(**vconf.get("dataset_args", {})), dict(args, jpeg_quality=int(vconf["jpeg_quality"]),
+                                                           factor=int(vconf.get("factor", 16)))
     if cls is TestImagesCSV and vconf.get("scale") is not None:
         args = {k: int(vconf[k]) for k in ("tile", "halo", "micro_batch", "shave") if vconf.get(k) is not None}
         if vconf.get("metric") is not None:
@@ -914,9 +1164,10 @@ class TrainStage:
         self.sampler = ResumeableSampler(self.dataset, self.batch_size, rank, world)
         if ds_conf.get("device_resident"):
             # batches made on the device from a packed arena; dataloader_args' num_workers is ignored
-            if ds_conf["type"] not in ("ImageSuperResolution", "PairedImageRestoration", "BicubicSuperResolution"):
+            if not isinstance(self.dataset, ImageSuperResolution):
                 raise ValueError(f"training stage {index}: device_resident needs type ImageSuperResolution, "
-                                 f"PairedImageRestoration or BicubicSuperResolution, got {ds_conf['type']}")
+                                 "PairedImageRestoration, BicubicSuperResolution or JpegArtifactRemoval, got "
+                                 f"{ds_conf['type']}")
             self.loader = DevicePatchLoader(self.dataset, self.sampler, self.batch_size, self.drop_last,
                                             shared=shared)
         else:
@@ -1163,6 +1414,7 @@ def run(conf: dict, device=None, max_iters: Optional[int] = None) -> Trainer:
                     saved_at = trainer.i
                 if val_every and trainer.i % val_every == 0:
                     check = validate_pairs if isinstance(val_set, TestPairsCSV) else \
+                        validate_car if "jpeg_quality" in val_args else \
                         validate_sr if "scale" in val_args else validate
                     psnr = check(trainer.model, val_set, device=device, **val_args)
                     trainer.val_history.append((trainer.i, psnr))

@@ -970,6 +970,92 @@ grr_status grr_u8_resize_images(const uint8_t* src_arena, int64_t src_elems, con
                                 int max_ho, int max_wo, int s, int up, int n_phase, const int32_t* first,
                                 const int32_t* count, const int32_t* taps, void* stream);
 
+/* ---- the JPEG round trip of uint8 pictures (csrc/jpeg_ops.hip): decode(encode(x)) of a baseline JPEG at quality
+ * q, the degradation of compression-artifact removal, made on the device without a bitstream.  Huffman coding is
+ * lossless, so the round trip is: colour transform, optional chroma down-sampling, 8 x 8 forward DCT, quantise,
+ * dequantise, inverse DCT, up-sample, colour transform back; in libjpeg's default integer ("islow") arithmetic
+ * every step is fixed-point and the bytes are exact.  tests/test_jpeg_ref.py holds a restatement of what follows
+ * to Pillow (libjpeg-turbo) byte for byte.
+ *
+ * All arithmetic is integer; >> is an arithmetic shift; DESCALE(x, n) = (x + (1 << (n - 1))) >> n.
+ *
+ * Quality: an integer q of 1..100.  scale = 5000 / q (integer division) if q < 50, else 200 - 2 q; a table entry
+ *   is clamp((base scale + 50) / 100, 1, 255), base from the Annex-K luminance or chrominance table in natural
+ *   (not zig-zag) order.  Gray uses the luminance table.
+ * Modes: C = 1: one plane, luminance table (sub is checked and otherwise ignored).  C = 3, sub = 0: 4:4:4.
+ *   C = 3, sub = 2: 4:2:0 (Pillow's numbering).  Other channel counts and subsamplings are refused.
+ * Colour in (C = 3), F(x) = floor(x 65536 + 0.5):
+ *   Y  = ( F(.299) R + F(.587) G + F(.114) B + 32768) >> 16
+ *   Cb = (-F(.16874) R - F(.33126) G + F(.5) B + (128 << 16) + 32767) >> 16
+ *   Cr = ( F(.5) R - F(.41869) G - F(.08131) B + (128 << 16) + 32767) >> 16
+ * Chroma down (4:2:0): the full-resolution chroma plane is extended by replicating its last column out to a
+ *   multiple of 16 columns and its last row to an even row count; a sample is (a + b + c + d + bias) >> 2 over its
+ *   2 x 2 cell, bias 1 in even output columns and 2 in odd ones.  The plane has ceil(H / 2) rows and a multiple of 8
+ *   columns; its rows are then padded as any plane's are.  So the padding columns hold the mean of the last
+ *   full-resolution column, not the last chroma sample, and the padding rows hold the last chroma row.
+ * Plane codec: the plane is extended to multiples of 8 by replicating its last column and row; samples are taken
+ *   minus 128; blocks are 8 x 8 on the plane's own grid from (0, 0).
+ *   Forward DCT, rows then columns, is jfdctint's (CONST_BITS 13, PASS1_BITS 2), with the constants 2446, 3196,
+ *   4433, 6270, 7373, 9633, 12299, 15137, 16069, 16819, 20995, 25172 for 0.298631336, 0.390180644, 0.541196100,
+ *   0.765366865, 0.899976223, 1.175875602, 1.501321110, 1.847759065, 1.961570560, 2.053119869, 2.562915447,
+ *   3.072711026.  With t0..t3 = d0 + d7, d1 + d6, d2 + d5, d3 + d4, t7..t4 = d0 - d7, d1 - d6, d2 - d5, d3 - d4,
+ *   t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2: outputs 0 and 4 are (t10 +- t11) << 2 in the row
+ *   pass and DESCALE(t10 +- t11, 2) in the column pass; with z1 = (t12 + t13) 4433, outputs 2 and 6 are
+ *   DESCALE(z1 + 6270 t13, n) and DESCALE(z1 - 15137 t12, n), n = 11 in the row pass and 15 in the column pass.
+ *   The odd part, shared with the inverse: ODD(a, b, c, d): z1 = a + d, z2 = b + c, z3 = a + c, z4 = b + d,
+ *   z5 = 9633 (z3 + z4), z3 = z5 - 16069 z3, z4 = z5 - 3196 z4, z1 = -7373 z1, z2 = -20995 z2, giving
+ *   (2446 a + z1 + z3, 16819 b + z2 + z4, 25172 c + z2 + z3, 12299 d + z1 + z4).  Outputs 7, 5, 3, 1 are
+ *   DESCALE(., n) of ODD(t4, t5, t6, t7).
+ *   Quantise with v = 8 entry: k = sign(c) ((|c| + (v >> 1)) / v); dequantise: k entry.
+ *   Inverse DCT, columns then rows, is jidctint's: z1 = 4433 (c2 + c6), t2 = z1 - 15137 c6, t3 = z1 + 6270 c2,
+ *   t0 = (c0 + c4) << 13, t1 = (c0 - c4) << 13, t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2,
+ *   (o0, o1, o2, o3) = ODD(c7, c5, c3, c1); outputs 0..7 are DESCALE(t10 + o3, t11 + o2, t12 + o1, t13 + o0,
+ *   t13 - o0, t12 - o1, t11 - o2, t10 - o3; n), n = 11 in the column pass and 18 in the row pass.
+ *   Then + 128 and a plain clamp to 0..255, as libjpeg-turbo's SIMD path does; the C range table's wrap beyond
+ *   +-512 is not reproduced.
+ * Chroma up (4:2:0), from the decoded chroma cropped to ceil(H / 2) x ceil(W / 2):
+ *   chroma width <= 2: each sample is replicated 2 x 2 (libjpeg turns its triangle filter off there);
+ *   chroma width > 2: s = 3 near row + far row, the far row of an even output row the row above, of an odd one the
+ *   row below, the first and last rows standing in for the missing ones; left output = (3 s[x] + s[x - 1] + 8) >> 4,
+ *   right output = (3 s[x] + s[x + 1] + 7) >> 4, except the first column's left output (4 s[0] + 8) >> 4 and the
+ *   last column's right output (4 s[last] + 7) >> 4; crop to H x W.
+ * Colour out, cb and cr taken minus 128: R = clamp(Y + ((F(1.402) cr + 32768) >> 16)),
+ *   B = clamp(Y + ((F(1.772) cb + 32768) >> 16)), G = clamp(Y + ((-F(.34414) cb - F(.71414) cr + 32768) >> 16)).
+ *
+ * The quantisation tables are made from the quality on the device.  src, dst: HWC interleaved uint8 at any byte
+ * address, distinct buffers; element offsets are 64-bit.  Each output byte is written once; no atomics; one launch;
+ * the int intermediates live in LDS only. */
+
+/* 1 where grr_u8_jpeg takes the image: C of 1 or 3, sub of 0 or 2, H, W >= 1, H W C < 2^31. */
+int grr_u8_jpeg_supported(int C, int H, int W, int sub);
+/* One image.  GRR_ERR_INVALID_ARG for a quality outside 1..100, GRR_ERR_UNSUPPORTED where the query says 0. */
+grr_status grr_u8_jpeg(const uint8_t* src, int H, int W, int C, uint8_t* dst, int quality, int sub, void* stream);
+/* Every image of arena into the same place of dst_arena (both of elems elements), one launch: image i is row i of
+ * table (int64 [n_img, 3] on the device, 8-byte aligned, rows (element offset, H, W)) at quality qualities[i] (int32
+ * [n_img] on the device).  max_h, max_w bound every image's sides.  Device data is clamped -- offsets into the
+ * arena, sides into [1, max_h] x [1, max_w], qualities into 1..100, every element index read into [0, elems), a
+ * write at or past elems dropped -- so a bad table gives wrong pixels, never an access outside the two arenas; the
+ * caller checks its host copies.  n_img <= 65535 (one grid row per image), else GRR_ERR_UNSUPPORTED. */
+grr_status grr_u8_jpeg_images(const uint8_t* arena, int64_t elems, int C, const int64_t* table, int n_img, int max_h,
+                              int max_w, uint8_t* dst_arena, const int32_t* qualities, int sub, void* stream);
+
+/* ---- the blocking sums of PSNR-B (Yim and Bovik; csrc/metric_ops.hip).  Of a uint8 H x W x C picture est take
+ * all horizontally and vertically adjacent pairs within one channel.  A pair is a boundary pair if it straddles a
+ * multiple-of-8 line: x % 8 == 7 for (x, x + 1), likewise for rows.  S_b, N_b, S_n, N_n are the integer sums of
+ * squared differences and the pair counts of the boundary and the non-boundary set.  D_b = S_b / N_b,
+ * D_n = S_n / N_n, BEF = (3 / log2 min(H, W)) (D_b - D_n) if D_b > D_n, else 0, and
+ * PSNR-B = 10 log10(255^2 / (SSE / (H W C) + BEF)) against a reference ref (SSE: grr_u8_sse), infinite when the
+ * denominator is 0; it needs min(H, W) >= 16.  The counts are the true numbers of pairs; some public
+ * implementations use H (W / 8 - 1) for the horizontal boundary count, which equals it only for multiples of 8.
+ * The device returns the four integers (255^2 2 2^31 < 2^48: they fit); the caller forms the quotients in float64.
+ * out: uint64 [4] (S_b, N_b, S_n, N_n) on the device, 8-byte aligned; integer adds, so the result does not depend
+ * on the grid or the order the atomics land in. */
+grr_status grr_u8_blocking(const uint8_t* est, int H, int W, int C, uint64_t* out, void* stream);
+/* The same for every image of an arena in one launch: out is uint64 [n_img, 4]; the table is clamped as
+ * grr_u8_ssim_images clamps it.  max_h max_w C < 2^31; n_img <= 65535. */
+grr_status grr_u8_blocking_images(const uint8_t* est, int64_t arena_elems, int C, const int64_t* img_table, int n_img,
+                                  int max_h, int max_w, uint64_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,8 @@
 
     python restore.py -yaml_path CONF.yaml --ckpt CHECKPOINT.pt --input FILE_OR_DIR --output DIR \\
            [--sigma S --seed N [--ssim] [--y-channel] | --reference DIR [--ssim] [--y-channel]
-            | --scale S [--shave N] [--ssim] [--y-channel] | --upscale S]
+            | --scale S [--shave N] [--ssim] [--y-channel] | --upscale S
+            | --jpeg-quality Q [--jpeg-subsampling 444|420] [--psnrb] [--ssim] [--y-channel]]
            [--tile T --halo H --factor F] [--batch-images]
            [--self-ensemble | --ensemble-modes 0,1,4,5]
 
@@ -35,6 +36,13 @@ the cropped input after --shave N border pixels (default S) are cut from both; t
 cropped size.  --ssim and --y-channel apply as above (the tables print PSNR-Y / SSIM-Y).  With --upscale S the inputs
 are low-resolution files: each is brought to S times its size by the bicubic (``irdu_amd.bicubic_up_u8``), restored
 and written at that size; nothing is scored.  Both work with --batch-images and the ensemble options.
+With --jpeg-quality Q (1..100; not with the other scored modes) the inputs are clean files and JPEG compression-artifact
+removal runs on each: it goes through the JPEG round trip at quality Q on the GPU (``irdu_amd.jpeg_degrade_u8``: what
+decoding its JPEG gives, Pillow's bytes, no file is written), the degraded picture is restored and scored against the
+input.  --jpeg-subsampling 444 (default) or 420 chooses the chroma subsampling of RGB files.  With --psnrb (with
+--jpeg-quality or --reference; both sides at least 16 pixels) each line also carries PSNR-B, the PSNR with the
+blocking effect factor of the restored picture (``irdu_amd.psnrb_u8``), and its mean follows the others; it is always
+taken on all channels, also with --y-channel.
 """
 import argparse
 import os
@@ -102,6 +110,13 @@ def parse_args(argv=None):
                              "against the cropped input")
     scored.add_argument("--upscale", type=int, default=None, metavar="S",
                         help="inputs are low-resolution: bring each to S times its size with the bicubic, restore, write")
+    scored.add_argument("--jpeg-quality", type=int, default=None, metavar="Q",
+                        help="inputs are clean: JPEG round trip at quality Q (1..100) on the GPU, restore, report PSNR "
+                             "against the input")
+    ap.add_argument("--jpeg-subsampling", type=str, default=None, choices=("444", "420"),
+                    help="with --jpeg-quality: the chroma subsampling of RGB files (default 444)")
+    ap.add_argument("--psnrb", action="store_true",
+                    help="with --jpeg-quality or --reference: report PSNR-B beside the PSNR")
     ap.add_argument("--shave", type=int, default=None, metavar="N",
                     help="with --scale: border pixels cut from both pictures before scoring (default: S)")
     ap.add_argument("--seed", type=int, default=2204)
@@ -121,12 +136,20 @@ def parse_args(argv=None):
     group.add_argument("--ensemble-modes", type=str, default=None, metavar="M,M,...",
                        help="average over these modes of 0..7 only, ascending (e.g. 0,1,4,5)")
     args = ap.parse_args(argv)
-    args.scored = args.sigma is not None or args.reference is not None or args.scale is not None
+    args.scored = args.sigma is not None or args.reference is not None or args.scale is not None \
+        or args.jpeg_quality is not None
     if args.ssim and not args.scored:
-        ap.error("--ssim needs --sigma, --reference or --scale: there is nothing to compare a restored image with otherwise")
+        ap.error("--ssim needs --sigma, --reference, --scale or --jpeg-quality: there is nothing to compare a restored image with otherwise")
     if args.y_channel and not args.scored:
-        ap.error("--y-channel needs --sigma, --reference or --scale: there is nothing to compare a restored image with "
+        ap.error("--y-channel needs --sigma, --reference, --scale or --jpeg-quality: there is nothing to compare a restored image with "
                  "otherwise")
+    if args.jpeg_quality is not None and not 1 <= args.jpeg_quality <= 100:
+        ap.error(f"--jpeg-quality: the quality is an integer of 1..100, got {args.jpeg_quality}")
+    if args.jpeg_subsampling is not None and args.jpeg_quality is None:
+        ap.error("--jpeg-subsampling needs --jpeg-quality")
+    args.jpeg_subsampling = 2 if args.jpeg_subsampling == "420" else 0
+    if args.psnrb and args.jpeg_quality is None and args.reference is None:
+        ap.error("--psnrb needs --jpeg-quality or --reference")
     for flag, value in (("--scale", args.scale), ("--upscale", args.upscale)):
         if value is not None and not 2 <= value <= 8:
             ap.error(f"{flag}: the scale is an integer of 2..8, got {value}")
@@ -189,7 +212,7 @@ def main(argv=None) -> None:
     halo = restore.HALO if args.halo is None else args.halo
     os.makedirs(args.output, exist_ok=True)
     rs = np.random.RandomState(seed=args.seed)
-    psnrs, ssims = [], []
+    psnrs, ssims, psnrbs = [], [], []
     psnr_of, ssim_of, tag = ((irdu_amd.psnr_y_u8, irdu_amd.ssim_y_u8, "-Y") if args.y_channel else
                              (irdu_amd.psnr_u8, irdu_amd.ssim_u8, ""))
 
@@ -215,6 +238,11 @@ def main(argv=None) -> None:
     def input_of(img):
         if args.sigma is not None:
             return noisy_of(img)
+        if args.jpeg_quality is not None:
+            try:
+                return irdu_amd.jpeg_degrade_u8(img, args.jpeg_quality, args.jpeg_subsampling)
+            except ValueError as e:
+                raise SystemExit(f"--jpeg-quality: {e}")
         return img if args.scale is None else irdu_amd.bicubic_degrade_u8(img, args.scale)
 
     def noisy_of(img):
@@ -241,6 +269,8 @@ def main(argv=None) -> None:
             except ValueError as e:
                 raise SystemExit(f"{path}: {e}")
             against = (f"bicubic x{args.scale} shave {args.shave}" if args.scale is not None else
+                       f"jpeg q{args.jpeg_quality} {'4:2:0' if args.jpeg_subsampling else '4:4:4'}"
+                       if args.jpeg_quality is not None else
                        f"sigma {args.sigma:g}" if args.reference is None else f"reference {refs[path]}")
             line = f"{path} -> {out_path}  {against}  PSNR{tag} {psnrs[-1]:.4f} dB"
             if args.ssim:
@@ -249,6 +279,12 @@ def main(argv=None) -> None:
                 except ValueError as e:
                     raise SystemExit(f"{path}: {e}")
                 line += f"  SSIM{tag} {ssims[-1]:.4f}"
+            if args.psnrb:
+                try:
+                    psnrbs.append(irdu_amd.psnrb_u8(scored, truth))
+                except ValueError as e:
+                    raise SystemExit(f"{path}: {e}")
+                line += f"  PSNR-B {psnrbs[-1]:.4f} dB"
             print(line)
         Image.fromarray(out[:, :, 0] if out.shape[2] == 1 else out).save(out_path)
 
@@ -271,6 +307,8 @@ def main(argv=None) -> None:
         print(f"mean PSNR{tag} over {len(psnrs)} image(s): {float(np.mean(psnrs)):.4f} dB")
     if ssims:
         print(f"mean SSIM{tag} over {len(ssims)} image(s): {float(np.mean(ssims)):.4f}")
+    if psnrbs:
+        print(f"mean PSNR-B over {len(psnrbs)} image(s): {float(np.mean(psnrbs)):.4f} dB")
 
 
 if __name__ == "__main__":
