@@ -38,7 +38,15 @@ byte out once) and the kernel / copy time ratio at equal bytes, then one ("bench
 kernels.u8_blocking against kernels.u8_sse on one 2048 x 2048 x 3 picture, host clock around calls that end in the
 sums' device-to-host copy.
 
-    python bench_data.py [--paired | --pair-kernel | --bicubic S | --jpeg Q] [--steps 60] [--warmup 10] [--images 12] [--side 1200] [--workers 4] [--files 8600]
+With --demosaic PATTERN only the synthesis of a demosaicking training set's filled mosaics is timed, on the same
+pictures and by the same method: "device" is grr_u8_demosaic_images on the clean arena (the one launch that
+kernels.u8_demosaic_images issues) for each fill (zero, bilinear, malvar), device events around each of 20 calls after a warm-up, and for malvar once more on the
+pictures with their last column cut off, whose odd width puts three rows in four on the byte-store path; "host" is
+one serial pass of training.demosaic_degrade_u8 (numpy) over every picture; grr_stream_copy is timed in the same
+process.  One JSON line ("bench": "demosaic") with, per case, the times, the algorithmic GB/s (3 bytes read and 3
+written per pixel) and that rate as a share of the copy's.
+
+    python bench_data.py [--paired | --pair-kernel | --bicubic S | --jpeg Q | --demosaic PATTERN] [--steps 60] [--warmup 10] [--images 12] [--side 1200] [--workers 4] [--files 8600]
 """
 from __future__ import annotations
 
@@ -290,6 +298,50 @@ def jpeg(quality: int, images: int, side: int, rounds: int = 20) -> None:
     print(json.dumps(out), flush=True)
 
 
+def demosaic(pattern: str, images: int, side: int, rounds: int = 20) -> None:
+    import irdu_amd
+    irdu_amd.load_native()
+    from irdu_amd import _native, kernels, restore, training
+    dev = torch.device("cuda:0")
+    pics = synthetic_pictures(images, side)
+    stream = torch.cuda.current_stream().cuda_stream
+    line = {"bench": "demosaic", "pattern": pattern, "images": images, "rounds": rounds,
+            "tile": list(kernels.DEMOSAIC_TILE)}
+    cases = [(fill, fill, pics) for fill in kernels.DEMOSAIC_FILLS]
+    cases.append(("malvar_odd_width", "malvar", [np.ascontiguousarray(p[:, :-1]) for p in pics]))
+    for name, fill, chosen in cases:
+        pack = restore.pack_images(chosen, dev)
+        n = pack.arena.numel()
+        patterns = torch.full((len(pack),), kernels._check_pattern("bench", pattern), dtype=torch.int32, device=dev)
+        # the library call itself on a preallocated arena, as the copy below is timed: the wrapper's host checks of a
+        # 96-image table would otherwise sit between the two events of a kernel this short
+        out = torch.empty_like(pack.arena)
+        max_h, max_w = max(h for _, h, _ in pack.host_table), max(w for _, _, w in pack.host_table)
+        code = kernels._check_fill("bench", fill)
+        assert torch.equal(kernels.u8_demosaic_images(pack, patterns, fill).arena,
+                           kernels.u8_demosaic_images(pack, pattern, fill).arena)
+        ms = device_ms(lambda: _native.call("grr_u8_demosaic_images", pack.arena.data_ptr(), n, pack.table.data_ptr(),
+                                            len(pack), max_h, max_w, out.data_ptr(), patterns.data_ptr(), code, stream),
+                       rounds)
+        assert torch.equal(out, kernels.u8_demosaic_images(pack, patterns, fill).arena)
+        # the float4 copy of the same bytes, in the same process
+        a = torch.empty(n // 4, dtype=torch.float32, device=dev)
+        b = torch.empty_like(a)
+        copy = device_ms(lambda: _native.call("grr_stream_copy", b.data_ptr(), a.data_ptr(), n // 4, stream), rounds)
+        t0 = time.perf_counter()
+        for pic in chosen:
+            training.demosaic_degrade_u8(pic, pattern, fill)
+        host_s = time.perf_counter() - t0
+        med, copy_med = float(np.median(ms)), float(np.median(copy))
+        gbps, copy_gbps = 2 * n / med / 1e6, 8 * (n // 4) / copy_med / 1e6
+        line[name] = {"arena_mb": round(n / 2 ** 20, 1), "device_ms": spread(ms), "device_gbps": round(gbps, 1),
+                      "stream_copy_ms": spread(copy), "stream_copy_gbps": round(copy_gbps, 1),
+                      "share_of_copy_rate": round(gbps / copy_gbps, 3), "host_numpy_s": round(host_s, 3),
+                      "host_over_device": round(host_s * 1e3 / med, 1)}
+        del pack, a, b, out
+    print(json.dumps(line), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     # the DataLoader's workers hold up to 2 batches each in flight when the clock starts: enough timed batches
@@ -313,9 +365,14 @@ def main():
     ap.add_argument("--jpeg", type=int, default=None, metavar="Q",
                     help="only time the synthesis of the JPEG-degraded pictures at quality Q: the device kernel (gray, "
                          "4:4:4, 4:2:0) against Pillow's encode and decode on the host, then the blocking kernel")
+    ap.add_argument("--demosaic", type=str, default=None, metavar="PATTERN", choices=("rggb", "grbg", "gbrg", "bggr"),
+                    help="only time the synthesis of the filled Bayer mosaics with this pattern: the device kernel (each "
+                         "fill) against numpy on the host")
     args = ap.parse_args()
     if args.pair_kernel:
         return pair_kernel()
+    if args.demosaic is not None:
+        return demosaic(args.demosaic, args.images, args.side)
     if args.jpeg is not None:
         return jpeg(args.jpeg, args.images, args.side)
     if args.bicubic is not None:

@@ -50,5 +50,7 @@ from .training import BicubicSuperResolution  # noqa: F401  (bicubic super-resol
 from .restore import bicubic_degrade_u8, bicubic_down_u8, bicubic_up_u8, evaluate_sr  # noqa: F401
 from .training import JpegArtifactRemoval  # noqa: F401  (JPEG artifact-removal pairs made from clean files)
 from .restore import evaluate_car, jpeg_degrade_u8, psnrb_u8  # noqa: F401
+from .training import BayerDemosaicking  # noqa: F401  (demosaicking pairs made from clean files)
+from .restore import demosaic_u8, evaluate_demosaic  # noqa: F401
 
 __version__ = "0.1.0"

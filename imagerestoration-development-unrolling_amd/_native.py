@@ -201,6 +201,10 @@ SIGNATURES = {
     "grr_u8_jpeg_images": [P, L, I, P, I, I, I, P, P, I, P],
     "grr_u8_blocking": [P, I, I, I, P, P],
     "grr_u8_blocking_images": [P, L, I, P, I, I, I, P, P],
+    # Bayer mosaicking and the initial fill of demosaicking (demosaic_ops.hip)
+    "grr_u8_demosaic_supported": [I, I, I],
+    "grr_u8_demosaic": [P, I, I, I, P, I, I, P],
+    "grr_u8_demosaic_images": [P, L, P, I, I, I, P, P, I, P],
 }
 _RESTYPES = {"grr_version": c_int, "grr_last_error": ctypes.c_char_p, "grr_lnb_workspace_bytes": c_int64,
              "grr_conv1x1_workspace_bytes": c_int64, "grr_wgrad_workspace_bytes": c_int64,

@@ -2712,3 +2712,101 @@ def u8_blocking_images(pack) -> List[Tuple[int, int, int, int]]:
             pack.table.data_ptr(), n_img, max(int(h) for _, h, _ in pack.host_table),
             max(int(w) for _, _, w in pack.host_table), out.data_ptr(), _stream(a.device))
     return [tuple(int(v) for v in row) for row in out.tolist()]
+
+
+# ---------------------------------------------------------------------------
+# Bayer mosaicking and the initial fill of demosaicking (csrc/demosaic_ops.hip; include/grr.h has the definition):
+# an RGB picture sampled through a colour filter array, its missing channels filled by a fixed integer filter.
+DEMOSAIC_TILE = (16, 64)      # a workgroup's rows and columns of the picture
+DEMOSAIC_PATTERNS = ("rggb", "grbg", "gbrg", "bggr")      # the top-left 2 x 2 cell in reading order; the index is the code
+DEMOSAIC_FILLS = ("zero", "bilinear", "malvar")           # the index is the code
+MAX_DEMOSAIC_IMAGES = 65535   # grr_u8_demosaic_images: one grid row per image
+
+
+def demosaic_ok(src_c: int, h: int, w: int) -> bool:
+    """grr_u8_demosaic_supported in plain Python (tests/test_demosaic_abi.py checks the two agree): a source of 1 or
+    3 channels, sides >= 1, 3 H W < 2^31."""
+    return src_c in (1, 3) and h >= 1 and w >= 1 and 3 * h * w < (1 << 31)
+
+
+def _check_code(name: str, what: str, names, v) -> int:
+    if isinstance(v, str) and v in names:
+        return names.index(v)
+    if isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) and 0 <= v < len(names):
+        return int(v)
+    raise ValueError(f"{name}: the {what} is one of {names} or its code 0..{len(names) - 1}, got {v!r}")
+
+
+def _check_pattern(name: str, pattern) -> int:
+    """The code of a Bayer pattern given by name or code; ValueError otherwise."""
+    return _check_code(name, "pattern", DEMOSAIC_PATTERNS, pattern)
+
+
+def _check_fill(name: str, fill) -> int:
+    """The code of a fill given by name or code; ValueError otherwise."""
+    return _check_code(name, "fill", DEMOSAIC_FILLS, fill)
+
+
+def u8_demosaic(img: Tensor, pattern, fill="malvar") -> Tensor:
+    """The Bayer mosaic of a uint8 device image with its missing channels filled, H x W x 3 (include/grr.h).
+    ``img``: H x W x 3 (R, G, B: the mosaic keeps the site's channel of each pixel), or H x W x 1 or H x W (already
+    the mosaic plane).  ``pattern``: "rggb", "grbg", "gbrg", "bggr" or the code 0..3; ``fill``: "zero", "bilinear",
+    "malvar" (Malvar-He-Cutler, the default) or the code 0..2.  One launch.  A non-contiguous image is copied first."""
+    name = "u8_demosaic"
+    pattern, fill = _check_pattern(name, pattern), _check_fill(name, fill)
+    if isinstance(img, Tensor) and img.dtype != torch.uint8:
+        raise ValueError(f"{name}: the image must be uint8, got {img.dtype}")
+    if isinstance(img, Tensor) and img.dim() == 2:
+        img = img[:, :, None]
+    if isinstance(img, Tensor) and img.dim() == 3 and img.shape[2] not in (1, 3):
+        raise ValueError(f"{name}: needs 1 channel (the mosaic) or 3 (R, G, B), got {tuple(img.shape)}")
+    h, w, c = _check_image(name, img)
+    if not demosaic_ok(c, h, w):
+        raise ValueError(f"{name}: needs 3 H W < 2^31, got {tuple(img.shape)}")
+    img = img.contiguous()
+    out = torch.empty((h, w, 3), dtype=torch.uint8, device=img.device)
+    _launch("u8_demosaic", img.numel() + out.numel(), "grr_u8_demosaic", img.data_ptr(), h, w, c, out.data_ptr(),
+            pattern, fill, _stream(img.device))
+    return out
+
+
+def u8_demosaic_images(pack, patterns, fill="malvar"):
+    """u8_demosaic of every image of a uint8 RGB image pack into a new pack that shares its image table (so the two
+    can form a patch_pair_source), one launch per 65535 images.  ``patterns``: one name or code for all images, a
+    sequence of one per image (checked here), or an int32 device tensor of one code per image (which the kernel
+    clamps into 0..3, as it does every device table)."""
+    from .restore import ImagePack
+    name = "u8_demosaic_images"
+    fill = _check_fill(name, fill)
+    n_img, c = _check_pack(name, pack, placed=False)
+    if pack.arena.dtype != torch.uint8:
+        raise ValueError(f"{name}: the arena must be uint8, got {pack.arena.dtype}")
+    if c != 3:
+        raise ValueError(f"{name}: the arena form takes R, G, B pictures, got {c} channel(s)")
+    shapes = [(int(h), int(w)) for _, h, w in pack.host_table]
+    dev = pack.arena.device
+    if not isinstance(patterns, Tensor):        # the host list is checked before anything is asked of the device
+        if isinstance(patterns, (str, int, np.integer)):
+            patterns = [patterns] * n_img
+        if len(patterns) != n_img:
+            raise ValueError(f"{name}: {len(patterns)} patterns for {n_img} images")
+        patterns = [_check_pattern(name, v) for v in patterns]
+    _check_placed(name, pack)
+    if isinstance(patterns, Tensor):
+        if patterns.dtype != torch.int32 or tuple(patterns.shape) != (n_img,) or patterns.device != dev \
+                or not patterns.is_contiguous():
+            raise ValueError(f"{name}: a pattern tensor is int32 [{n_img}], contiguous and on the arena's device")
+        p = patterns
+    else:
+        p = torch.tensor(patterns, dtype=torch.int32).to(dev)
+    covered = sum(h * w * 3 for h, w in shapes) == pack.arena.numel()
+    arena = (torch.empty_like if covered else torch.zeros_like)(pack.arena)      # bytes between images stay 0
+    for at in range(0, n_img, MAX_DEMOSAIC_IMAGES):
+        n = min(MAX_DEMOSAIC_IMAGES, n_img - at)
+        part = shapes[at:at + n]
+        _launch("u8_demosaic_images", 2 * sum(h * w * 3 for h, w in part), "grr_u8_demosaic_images",
+                pack.arena.data_ptr(), pack.arena.numel(), pack.table.data_ptr() + at * 24, n,
+                max(h for h, _ in part), max(w for _, w in part), arena.data_ptr(), p.data_ptr() + at * 4, fill,
+                _stream(dev))
+    return ImagePack(arena, pack.table, tuple(tuple(int(v) for v in row) for row in pack.host_table), 3,
+                     tuple(getattr(pack, "kinds", ())))

@@ -58,6 +58,10 @@ JPEG compression-artifact removal: ``jpeg_degrade_u8`` is the JPEG round trip at
 picture against its reference (the "psnrb" metric of evaluate_metrics and evaluate_pairs), and ``evaluate_car``
 degrades clean pictures, restores them and scores them.
 
+Demosaicking: ``demosaic_u8`` is the Bayer mosaic of a picture (or a raw 1-channel mosaic) with its missing channels
+filled by the zero, bilinear or Malvar-He-Cutler filter in exact integers (``kernels.u8_demosaic``), and
+``evaluate_demosaic`` mosaics clean pictures, restores the filled ones and scores them (CPSNR, SSIM).
+
 Single process: several ranks are ``tiling.tiled_forward``'s business.
 """
 from __future__ import annotations
@@ -813,6 +817,76 @@ def evaluate_car(model: Callable, images, quality: int, subsampling: int = 0, fa
                                    micro_batch, True, modes)
         if restored.shape != clean.shape:
             raise ValueError(f"{who}: the model returns {restored.shape[2]} channel(s) for {clean.shape[2]}; no score")
+        for m in metrics:
+            values[m].append(_SCORE[m](restored, clean))
+    return {m: (float(np.mean(values[m])), values[m]) for m in metrics}
+
+
+def demosaic_u8(a, pattern, fill="malvar"):
+    """The Bayer mosaic of the uint8 picture ``a`` with its missing channels filled, H x W x 3, on the GPU
+    (kernels.u8_demosaic; include/grr.h has the definition).  ``a``: a numpy array or a tensor, host or device, of
+    H x W x 3 (R, G, B; the mosaic keeps the site's channel of each pixel) or H x W x 1 or H x W (a raw mosaic plane);
+    the result is of the same kind.  ``pattern``: "rggb", "grbg", "gbrg" or "bggr" (or the code 0..3); ``fill``:
+    "zero", "bilinear" or "malvar" (or 0..2).  training.demosaic_degrade_u8 gives the same bytes on the CPU."""
+    pattern = kernels._check_pattern("demosaic_u8", pattern)               # before any transfer
+    fill = kernels._check_fill("demosaic_u8", fill)
+    if isinstance(a, (np.ndarray, torch.Tensor)) and a.ndim == 2:
+        a = a[:, :, None]
+    if isinstance(a, (np.ndarray, torch.Tensor)) and a.ndim == 3 and a.shape[2] not in (1, 3):
+        raise ValueError(f"demosaic_u8: needs 1 channel (the mosaic) or 3 (R, G, B), got {tuple(a.shape)}")
+    return _resized_u8("demosaic_u8", a, lambda t: kernels.u8_demosaic(t, pattern, fill))
+
+
+def evaluate_demosaic(model: Callable, images, pattern="rggb", fill="malvar", shave: int = 0, factor: int = 16,
+                      ensemble=1, metrics=("psnr", "ssim"), **tiling_args) -> dict:
+    """Score ``model`` on Bayer demosaicking (the protocol of the Kodak / McMaster tables) over clean uint8
+    H x W x 3 pictures (numpy arrays or tensors, host or device).  Per picture: mosaic and fill on the device
+    (kernels.u8_demosaic), the filled picture restored as ``restore_image(..., quantise=True)`` does, ``shave``
+    pixels cut from each side of the restored and the clean picture, and the two scored with the exact-integer
+    kernels.  "psnr" is taken over the three channels together: the CPSNR of the demosaicking tables.  Returns
+    {metric: (mean, per-image values)} as evaluate_pairs does; with ``shave=0`` it is
+    evaluate_pairs(model, filled, clean) bit for bit.  tiling_args: tile, halo, micro_batch, device; ``ensemble`` as
+    in restore_image.
+
+    Everything is checked before any launch: the pattern, the fill, the shave, uint8 pictures of 3 channels, a
+    picture smaller than the shave leaves, and what the metrics need of the shaved picture (SSIM: both sides at
+    least 11; PSNR-B: at least 16)."""
+    who = "evaluate_demosaic"
+    modes, metrics, device, tile, halo, micro_batch = _evaluate_args(who, model, ensemble, metrics, tiling_args)
+    pattern, fill = kernels._check_pattern(who, pattern), kernels._check_fill(who, fill)
+    if isinstance(shave, bool) or not isinstance(shave, int) or shave < 0:
+        raise ValueError(f"{who}: shave is a non-negative integer, got {shave!r}")
+    if len(images) < 1:
+        raise ValueError(f"{who}: no images")
+    cleans = []
+    for i in range(len(images)):
+        try:
+            t, _ = _checked_image(images[i])
+        except ValueError as e:
+            raise ValueError(f"{who}: image {i}: {e}") from None
+        if t.dtype != torch.uint8:
+            raise ValueError(f"{who}: image {i} is {t.dtype}; the mosaic is defined on uint8 pictures")
+        h, w = t.shape[:2]
+        if t.shape[2] != 3 or not kernels.demosaic_ok(3, h, w):
+            raise ValueError(f"{who}: image {i} is {tuple(t.shape)}; the protocol takes clean R, G, B pictures")
+        if min(h, w) <= 2 * shave:
+            raise ValueError(f"{who}: image {i} is {tuple(t.shape)}: nothing is left after a shave of {shave}")
+        _check_metric_shape(who, f"image {i} after the shave", (h - 2 * shave, w - 2 * shave, 3), metrics)
+        plan(h, w, factor, tile, halo)                                            # raises what the restoration would
+        cleans.append(t)
+    if device is None:
+        device = next((t.device for t in cleans if t.is_cuda), None)
+    values = {m: [] for m in metrics}
+    for t in cleans:
+        clean = _to_device(t, device)
+        restored = _restore_device(model, kernels.u8_demosaic(clean, pattern, fill), None, factor, tile, halo,
+                                   micro_batch, True, modes)
+        if restored.shape != clean.shape:
+            raise ValueError(f"{who}: the model returns {restored.shape[2]} channel(s) for 3; no score")
+        if shave:       # an ATen slice and copy, as in evaluate_sr
+            h, w = clean.shape[:2]
+            restored = restored[shave:h - shave, shave:w - shave].contiguous()
+            clean = clean[shave:h - shave, shave:w - shave].contiguous()
         for m in metrics:
             values[m].append(_SCORE[m](restored, clean))
     return {m: (float(np.mean(values[m])), values[m]) for m in metrics}

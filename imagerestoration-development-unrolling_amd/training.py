@@ -39,6 +39,10 @@ csrc/resize_ops.hip makes the degraded arena from the clean one), and ``validate
 after the JPEG round trip at a quality of 1..100 (``jpeg_degrade_u8`` on the host, Pillow's bytes; on the device
 csrc/jpeg_ops.hip makes the degraded arena), and ``validate_car`` scores it on a ``TestImagesCSV`` set with a
 ``jpeg_quality`` key through restore.evaluate_car.
+``BayerDemosaicking`` is the third of the kind, for demosaicking: the input is the picture sampled through a Bayer
+colour filter array with its missing channels filled by a fixed integer filter (``demosaic_degrade_u8`` on the host;
+on the device csrc/demosaic_ops.hip makes the filled arena), and ``validate_demosaic`` scores it on a
+``TestImagesCSV`` set with a ``bayer`` key through restore.evaluate_demosaic.
 """
 from __future__ import annotations
 
@@ -669,6 +673,125 @@ class JpegArtifactRemoval(_DegradedFromClean):
         return ("jpeg", tuple(self.qualities[i] for i in used), self.subsampling)
 
 
+BAYER_PATTERNS = ("rggb", "grbg", "gbrg", "bggr")      # kernels.DEMOSAIC_PATTERNS: the index is the code
+BAYER_FILLS = ("zero", "bilinear", "malvar")           # kernels.DEMOSAIC_FILLS
+
+
+def _bayer_code(who: str, what: str, names, v) -> int:
+    if isinstance(v, str) and v in names:
+        return names.index(v)
+    if isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) and 0 <= v < len(names):
+        return int(v)
+    raise ValueError(f"{who}: the {what} is one of {names} or its code 0..{len(names) - 1}, got {v!r}")
+
+
+def _mirror(n: int) -> np.ndarray:
+    """The indices -2 .. n + 1 of a side n reflected about its edge samples, which are not repeated."""
+    i = np.arange(-2, n + 2)
+    if n == 1:
+        return np.zeros_like(i)
+    t = i % (2 * (n - 1))
+    return np.where(t < n, t, 2 * (n - 1) - t)
+
+
+def demosaic_degrade_u8(a: np.ndarray, pattern, fill="malvar") -> np.ndarray:
+    """The Bayer mosaic of a uint8 picture with its missing channels filled, H x W x 3, on the CPU (include/grr.h
+    has the definition).  ``a``: H x W x 3 (R, G, B) or the mosaic plane itself as H x W x 1 or H x W.  ``pattern``:
+    "rggb", "grbg", "gbrg", "bggr" or the code 0..3; ``fill``: "zero", "bilinear", "malvar" or 0..2.  The same
+    integers as kernels.u8_demosaic, bit for bit: it serves the host DataLoader path and users without a GPU."""
+    who = "demosaic_degrade_u8"
+    a = np.asarray(a)
+    a = a[:, :, None] if a.ndim == 2 else a
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] not in (1, 3) or 0 in a.shape:
+        raise ValueError(f"{who}: expected a uint8 H x W x 3, H x W x 1 or H x W picture, got {a.dtype} {a.shape}")
+    code, fill = _bayer_code(who, "pattern", BAYER_PATTERNS, pattern), _bayer_code(who, "fill", BAYER_FILLS, fill)
+    h, w = a.shape[:2]
+    ry, rx = code >> 1, code & 1
+    red, blue = (slice(ry, None, 2), slice(rx, None, 2)), (slice(1 - ry, None, 2), slice(1 - rx, None, 2))
+    m = a[:, :, a.shape[2] // 2].astype(np.int32)                      # G everywhere, or the plane itself
+    if a.shape[2] == 3:
+        m[red], m[blue] = a[:, :, 0][red], a[:, :, 2][blue]
+    p = m[_mirror(h)][:, _mirror(w)]                                    # the plane with its reflected 2-sample frame
+    at = lambda dy, dx: p[2 + dy:2 + dy + h, 2 + dx:2 + dx + w]
+    ctr = at(0, 0)
+    if fill == 0:
+        green = other = inrow = incol = np.zeros_like(ctr)
+    else:
+        h1, v1 = at(0, -1) + at(0, 1), at(-1, 0) + at(1, 0)
+        diag = at(-1, -1) + at(-1, 1) + at(1, -1) + at(1, 1)
+        if fill == 1:
+            green, other, inrow, incol = 4 * (h1 + v1), 4 * diag, 8 * h1, 8 * v1
+        else:
+            h2, v2 = at(0, -2) + at(0, 2), at(-2, 0) + at(2, 0)
+            green = 8 * ctr + 4 * (h1 + v1) - 2 * (h2 + v2)
+            other = 12 * ctr + 4 * diag - 3 * (h2 + v2)
+            inrow = 10 * ctr + 8 * h1 - 2 * diag - 2 * h2 + v2
+            incol = 10 * ctr + 8 * v1 - 2 * diag - 2 * v2 + h2
+    s = np.empty((h, w, 3), np.int32)                                   # sixteenths
+    s[:, :, 1] = green
+    s[:, :, 0], s[:, :, 2] = other, other
+    for rows, cols, of_row, of_col in ((red[0], blue[1], 0, 2), (blue[0], red[1], 2, 0)):      # the two kinds of G site
+        s[rows, cols, of_row], s[rows, cols, of_col] = inrow[rows, cols], incol[rows, cols]
+        s[rows, cols, 1] = 16 * ctr[rows, cols]
+    s[red + (0,)], s[blue + (2,)] = 16 * ctr[red], 16 * ctr[blue]
+    return np.clip((s + 8) >> 4, 0, 255).astype(np.uint8)
+
+
+class BayerDemosaicking(_DegradedFromClean):
+    """Demosaicking pairs synthesised from clean RGB files under ImageSuperResolution's csv, crop and patch plan and
+    draws: the input of a sample is the same patch of the whole picture sampled through a Bayer colour filter array
+    and filled (demosaic_degrade_u8), the target the clean patch.  ``pattern``: "rggb", "grbg", "gbrg" or "bggr" for
+    every file, or ``[names, probabilities]``; the pattern of file i is then drawn once, in file order, from
+    RandomState(seed), so it is a function of (seed, file) alone and is fixed for the run (``patterns`` lists the
+    names drawn).  ``fill``: "zero", "bilinear" or "malvar".  It needs ``n_channels == 3``.  A DevicePatchLoader
+    decodes only the clean files and makes the filled arena on the GPU (kernels.u8_demosaic_images).
+
+    Two properties to know.  Patches are cut from the filled whole picture at any origin, odd ones included, and the
+    8 augmentation modes turn them, so the model sees every phase of the colour filter array under one pattern.  An
+    additive ``dist_mode`` (default "none") adds its noise on top of the filled patch, as the sibling datasets do:
+    noise on the mosaic before the fill (joint denoising and demosaicking) is not modelled."""
+
+    def __init__(self, csv_path, pattern="rggb", fill="malvar", dist_mode="none", lambda_noise=None,
+                 use_data_aug=False, patch_size=(64, 64), max_num_patchs=100000, root_folder="", logger=None,
+                 device=None, seed=2204, n_channels=3):
+        who = "BayerDemosaicking"
+        ok = lambda p: isinstance(p, str) and p in BAYER_PATTERNS
+        if isinstance(pattern, (list, tuple)):
+            if len(pattern) != 2 or isinstance(pattern[0], str) or len(pattern[0]) < 1 \
+                    or len(pattern[0]) != len(pattern[1]) or not all(ok(p) for p in pattern[0]):
+                raise ValueError(f"{who}: pattern is one of {BAYER_PATTERNS} or [names, probabilities] with as many "
+                                 f"probabilities as names, got {pattern!r}")
+        elif not ok(pattern):
+            raise ValueError(f"{who}: pattern is one of {BAYER_PATTERNS} or [names, probabilities], got {pattern!r}")
+        if not (isinstance(fill, str) and fill in BAYER_FILLS):
+            raise ValueError(f"{who}: fill is one of {BAYER_FILLS}, got {fill!r}")
+        if n_channels != 3:
+            raise ValueError(f"{who}: a Bayer mosaic is made from R, G, B pictures, got n_channels {n_channels}")
+        self.pattern, self.fill = pattern, fill
+        super().__init__(csv_path, dist_mode, lambda_noise, use_data_aug=use_data_aug, patch_size=patch_size,
+                         max_num_patchs=max_num_patchs, root_folder=root_folder, logger=logger, device=device,
+                         seed=seed, n_channels=n_channels)
+
+    def create_all_images(self):
+        super().create_all_images()
+        n = len(self.paths)
+        if isinstance(self.pattern, (list, tuple)):
+            drawn = np.random.RandomState(self.seed).choice(len(self.pattern[0]), p=self.pattern[1], size=n)
+            self.patterns = [str(self.pattern[0][int(k)]) for k in drawn]
+        else:
+            self.patterns = [self.pattern] * n
+
+    def degrade_host(self, img, clean):
+        return demosaic_degrade_u8(clean, self.patterns[img], self.fill)
+
+    def degrade_pack(self, pack, used):
+        from . import kernels
+        return kernels.u8_demosaic_images(pack, [self.patterns[i] for i in used], self.fill)
+
+    def synthetic_key(self, used):
+        return ("bayer", tuple(self.patterns[i] for i in used), self.fill)
+
+
 class DevicePatchLoader:
     """Batches of an ImageSuperResolution dataset made on the device: yields (noisy, clean) float32
     [B, C, h, w], planar (``channels_first``), in place of a DataLoader.  On first use (or in ``prepare``) every file
@@ -696,7 +819,8 @@ class DevicePatchLoader:
     ``prepare``) and shares its image table.  The host never holds a degraded picture.  A JpegArtifactRemoval dataset
     goes the same way with kernels.u8_jpeg_images at each file's quality: the switch is the datasets' common base
     class, whose ``degrade_pack`` makes the arena and whose ``synthetic_key`` tells one degradation from another in a
-    shared store."""
+    shared store.  A BayerDemosaicking dataset is a third of the kind (kernels.u8_demosaic_images, each file's
+    pattern)."""
     channels_first = True
     CHUNK_BYTES = 256 << 20      # decoded pictures staged on the host per transfer
 
@@ -829,7 +953,8 @@ class DevicePatchLoader:
 
 
 DATASETS = {c.__name__: c for c in (AddictiveGaussianNoiseImagePair, SyntheticNoisyPatches, ImageSuperResolution,
-                                    PairedImageRestoration, BicubicSuperResolution, JpegArtifactRemoval)}
+                                    PairedImageRestoration, BicubicSuperResolution, JpegArtifactRemoval,
+                                    BayerDemosaicking)}
 
 
 # ---------------------------------------------------------------------------
@@ -1056,6 +1181,39 @@ def validate_car(model: nn.Module, images, jpeg_quality: int, subsampling: int =
     return float(acc[0] / acc[1])
 
 
+VAL_DEMOSAIC_METRICS = ("psnr", "psnr_y", "ssim")
+
+
+def validate_demosaic(model: nn.Module, images, bayer="rggb", fill="malvar", shave: int = 0, factor: int = 16,
+                      device=None, metric: str = "psnr", **tiling_args) -> float:
+    """Mean score of ``model`` on Bayer demosaicking over clean RGB test pictures (``images[i]``: uint8 H x W x 3, or
+    float32 in [0, 1] on the uint8 grid as TestImagesCSV yields them): restore.evaluate_demosaic on this rank's
+    share -- mosaic with the pattern ``bayer`` and ``fill`` on the device, restore, cut ``shave`` pixels from each
+    side, score against the clean picture.  ``metric``: "psnr" (default: over the three channels, the CPSNR),
+    "psnr_y" or "ssim".  Nothing is drawn.  tiling_args: tile, halo, micro_batch, ensemble.
+
+    Several ranks: sharded and all-reduced as validate_pairs does."""
+    from . import restore
+    if metric not in VAL_DEMOSAIC_METRICS:
+        raise ValueError(f"validate_demosaic: metric is one of {VAL_DEMOSAIC_METRICS}, got {metric!r}")
+    rank, world = sharding.world()
+    if device is None:
+        device = next(model.parameters()).device
+    s, e = sharding.shard_range(len(images), rank, world)
+    mine = []
+    for i in range(s, e):
+        a = np.asarray(images[i])
+        mine.append(a if a.dtype == np.uint8 else np.rint(a.astype(np.float64) * 255.0).astype(np.uint8))
+    scores = restore.evaluate_demosaic(model, mine, bayer, fill=fill, shave=shave, factor=factor, device=device,
+                                       metrics=(metric,), **tiling_args)[metric][1] if mine else []
+    acc = torch.tensor([float(np.sum(scores)), float(len(scores))], dtype=torch.float64)
+    if world > 1:
+        if torch.distributed.get_backend() == "nccl":
+            acc = acc.to(device)
+        torch.distributed.all_reduce(acc)
+    return float(acc[0] / acc[1])
+
+
 def create_val_dataset(conf: dict):
     """``datasets.val`` of the YAML ({type, dataset_args, sigma, factor}), or None.  A paired set (TestPairsCSV)
     takes {type, dataset_args, factor, tile, halo, micro_batch, metric}: validate_pairs' arguments, no sigma; without
@@ -1063,7 +1221,9 @@ def create_val_dataset(conf: dict):
     super-resolution protocol: {type, dataset_args, scale, shave, factor, tile, halo, micro_batch, metric},
     validate_sr's arguments, no sigma.  TestImagesCSV with a ``jpeg_quality`` key is JPEG artifact removal:
     {type, dataset_args, jpeg_quality, subsampling, factor, tile, halo, micro_batch, metric}, validate_car's
-    arguments, no sigma."""
+    arguments, no sigma.  TestImagesCSV with a ``bayer`` key (a pattern name) is demosaicking:
+    {type, dataset_args, bayer, fill, shave, factor, tile, halo, micro_batch, metric}, validate_demosaic's arguments,
+    no sigma."""
     vconf = conf.get("datasets", {}).get("val")
     if not vconf:
         return None, {}
@@ -1077,6 +1237,20 @@ def create_val_dataset(conf: dict):
                 raise ValueError(f"datasets.val.metric is one of {VAL_CAR_METRICS}, got {vconf['metric']!r}")
             args["metric"] = str(vconf["metric"])
         return cls(**vconf.get("dataset_args", {})), dict(args, jpeg_quality=int(vconf["jpeg_quality"]),
+                                                           factor=int(vconf.get("factor", 16)))
+    if cls is TestImagesCSV and vconf.get("bayer") is not None:
+        if vconf["bayer"] not in BAYER_PATTERNS:
+            raise ValueError(f"datasets.val.bayer is one of {BAYER_PATTERNS}, got {vconf['bayer']!r}")
+        if vconf.get("fill") is not None and vconf["fill"] not in BAYER_FILLS:
+            raise ValueError(f"datasets.val.fill is one of {BAYER_FILLS}, got {vconf['fill']!r}")
+        args = {k: int(vconf[k]) for k in ("tile", "halo", "micro_batch", "shave") if vconf.get(k) is not None}
+        if vconf.get("fill") is not None:
+            args["fill"] = str(vconf["fill"])
+        if vconf.get("metric") is not None:
+            if vconf["metric"] not in VAL_DEMOSAIC_METRICS:
+                raise ValueError(f"datasets.val.metric is one of {VAL_DEMOSAIC_METRICS}, got {vconf['metric']!r}")
+            args["metric"] = str(vconf["metric"])
+        return cls(**vconf.get("dataset_args", {})), dict(args, bayer=str(vconf["bayer"]),
                                                            factor=int(vconf.get("factor", 16)))
     if cls is TestImagesCSV and vconf.get("scale") is not None:
         args = {k: int(vconf[k]) for k in ("tile", "halo", "micro_batch", "shave") if vconf.get(k) is not None}
@@ -1166,7 +1340,7 @@ class TrainStage:
             # batches made on the device from a packed arena; dataloader_args' num_workers is ignored
             if not isinstance(self.dataset, ImageSuperResolution):
                 raise ValueError(f"training stage {index}: device_resident needs type ImageSuperResolution, "
-                                 "PairedImageRestoration, BicubicSuperResolution or JpegArtifactRemoval, got "
+                                 "PairedImageRestoration, BicubicSuperResolution, JpegArtifactRemoval or BayerDemosaicking, got "
                                  f"{ds_conf['type']}")
             self.loader = DevicePatchLoader(self.dataset, self.sampler, self.batch_size, self.drop_last,
                                             shared=shared)
@@ -1415,6 +1589,7 @@ def run(conf: dict, device=None, max_iters: Optional[int] = None) -> Trainer:
                 if val_every and trainer.i % val_every == 0:
                     check = validate_pairs if isinstance(val_set, TestPairsCSV) else \
                         validate_car if "jpeg_quality" in val_args else \
+                        validate_demosaic if "bayer" in val_args else \
                         validate_sr if "scale" in val_args else validate
                     psnr = check(trainer.model, val_set, device=device, **val_args)
                     trainer.val_history.append((trainer.i, psnr))

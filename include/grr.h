@@ -1056,6 +1056,51 @@ grr_status grr_u8_blocking(const uint8_t* est, int H, int W, int C, uint64_t* ou
 grr_status grr_u8_blocking_images(const uint8_t* est, int64_t arena_elems, int C, const int64_t* img_table, int n_img,
                                   int max_h, int max_w, uint64_t* out, void* stream);
 
+/* ---- Bayer mosaicking and the initial fill of demosaicking (csrc/demosaic_ops.hip): an RGB picture is sampled
+ * through a Bayer colour filter array and the two missing channels of every pixel are filled by a fixed linear
+ * filter, the input a demosaicking model restores.  No floating point appears in the definition.
+ *
+ * Pattern: the colours of the top-left 2 x 2 cell in reading order, rggb = 0, grbg = 1, gbrg = 2, bggr = 3.  The R
+ *   site has (row parity, column parity) = (0,0), (0,1), (1,0), (1,1) for the four codes, i.e. (code >> 1, code & 1);
+ *   the B site has both parities opposite; every other site is G.  Channel order of a picture is R, G, B.
+ * Mosaic: the plane of an H x W x 3 picture a is m[y,x] = a[y,x,site(y,x)], one byte per pixel.  A 1-channel source
+ *   is already m.
+ * Border: a neighbour outside the plane is read by reflection about the edge sample, without repeating it: for a
+ *   side n >= 2 index i maps to t = i mod 2(n - 1) (non-negative), then t < n ? t : 2(n - 1) - t; for n = 1 every
+ *   index maps to 0.  For n >= 2 this keeps the parity of an index, so a reflected neighbour has the colour the
+ *   formula expects -- which sym of grr_patch_batch, repeating the edge sample, would not.  For n = 1 parity is not
+ *   kept; the value read is still defined.
+ * Fill: every output byte is clamp((s + 8) >> 4, 0, 255), s an int32 sum in sixteenths, >> arithmetic.  The site's own
+ *   channel is s = 16 m[y,x] in every mode: a measured sample passes through.  With ctr = m[y,x], cross = the sum of
+ *   the 4 neighbours at distance 1 along the axes, far = of the 4 at distance 2 along the axes, diag = of the 4
+ *   diagonal neighbours, h1, h2 = of the 2 horizontal neighbours at distance 1 and at distance 2, v1, v2 the same
+ *   vertically:
+ *   zero (0):     every missing channel is 0 (the masked picture).
+ *   bilinear (1): G at an R or B site 4 cross; R or B at a G site 8 h1 when that colour lies in this row, else
+ *                 8 v1; R at a B site and B at an R site 4 diag.
+ *   malvar (2):   the Malvar-He-Cutler gradient-corrected filters.  G at an R or B site 8 ctr + 4 cross - 2 far;
+ *                 R or B at a G site, that colour in this row: 10 ctr + 8 h1 - 2 diag - 2 h2 + v2; in this column:
+ *                 10 ctr + 8 v1 - 2 diag - 2 v2 + h2; R at a B site and B at an R site 12 ctr + 4 diag - 3 far.
+ *   Every coefficient set sums to 16, so a gray constant maps to itself; |s| <= 2 * 20 * 255.
+ *
+ * src: HWC uint8 of src_c channels, dst: H x W x 3, both at any byte address, distinct buffers; element offsets are
+ * 64-bit.  Each output byte is written once; no atomics; one launch; the mosaic plane lives in LDS only. */
+
+/* 1 where grr_u8_demosaic takes the image: src_c of 1 or 3, H, W >= 1, 3 H W < 2^31. */
+int grr_u8_demosaic_supported(int src_c, int H, int W);
+/* One image.  GRR_ERR_INVALID_ARG for a pattern outside 0..3 or a fill outside 0..2, before any launch;
+ * GRR_ERR_UNSUPPORTED where the query says 0. */
+grr_status grr_u8_demosaic(const uint8_t* src, int H, int W, int src_c, uint8_t* dst, int pattern, int fill,
+                           void* stream);
+/* Every image of an RGB arena into the same place of dst_arena (both of elems elements), one launch: image i is row
+ * i of table (int64 [n_img, 3] on the device, 8-byte aligned, rows (element offset, H, W)) with pattern patterns[i]
+ * (int32 [n_img] on the device).  max_h, max_w bound every image's sides.  Device data is clamped -- offsets into the
+ * arena, sides into [1, max_h] x [1, max_w], patterns into 0..3, every element index read into [0, elems), a write
+ * at or past elems dropped -- so a bad table gives wrong pixels, never an access outside the two arenas; the caller
+ * checks its host copies.  n_img <= 65535 (one grid row per image), else GRR_ERR_UNSUPPORTED. */
+grr_status grr_u8_demosaic_images(const uint8_t* arena, int64_t elems, const int64_t* table, int n_img, int max_h,
+                                  int max_w, uint8_t* dst_arena, const int32_t* patterns, int fill, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,9 @@
     python restore.py -yaml_path CONF.yaml --ckpt CHECKPOINT.pt --input FILE_OR_DIR --output DIR \\
            [--sigma S --seed N [--ssim] [--y-channel] | --reference DIR [--ssim] [--y-channel]
             | --scale S [--shave N] [--ssim] [--y-channel] | --upscale S
-            | --jpeg-quality Q [--jpeg-subsampling 444|420] [--psnrb] [--ssim] [--y-channel]]
+            | --jpeg-quality Q [--jpeg-subsampling 444|420] [--psnrb] [--ssim] [--y-channel]
+            | --bayer PATTERN [--demosaic-fill FILL] [--shave N] [--ssim] [--y-channel]
+            | --raw PATTERN [--demosaic-fill FILL]]
            [--tile T --halo H --factor F] [--batch-images]
            [--self-ensemble | --ensemble-modes 0,1,4,5]
 
@@ -43,6 +45,13 @@ input.  --jpeg-subsampling 444 (default) or 420 chooses the chroma subsampling o
 --jpeg-quality or --reference; both sides at least 16 pixels) each line also carries PSNR-B, the PSNR with the
 blocking effect factor of the restored picture (``irdu_amd.psnrb_u8``), and its mean follows the others; it is always
 taken on all channels, also with --y-channel.
+With --bayer PATTERN (rggb, grbg, gbrg or bggr; not with the other scored modes) the inputs are clean RGB files and the
+demosaicking protocol runs on each: it is sampled through the Bayer colour filter array and its missing channels are
+filled on the GPU (``irdu_amd.demosaic_u8``; --demosaic-fill zero, bilinear or malvar, the default), the filled picture
+is restored and scored against the input after --shave N border pixels (default 0) are cut from both.  The PSNR over
+the three channels is the CPSNR of the demosaicking tables; --ssim and --y-channel apply as above.  With --raw PATTERN
+the inputs are 1-channel mosaic files as a sensor gives them: each is filled to RGB the same way, restored and written
+as RGB; nothing is scored.  Both need a 3-channel model and work with --batch-images and the ensemble options.
 """
 import argparse
 import os
@@ -50,6 +59,8 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+PATTERNS = ("rggb", "grbg", "gbrg", "bggr")     # irdu_amd.kernels.DEMOSAIC_PATTERNS
+FILLS = ("zero", "bilinear", "malvar")          # irdu_amd.kernels.DEMOSAIC_FILLS
 EXTENSIONS = (".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff", ".ppm", ".pgm", ".webp")
 
 
@@ -113,12 +124,20 @@ def parse_args(argv=None):
     scored.add_argument("--jpeg-quality", type=int, default=None, metavar="Q",
                         help="inputs are clean: JPEG round trip at quality Q (1..100) on the GPU, restore, report PSNR "
                              "against the input")
+    scored.add_argument("--bayer", type=str, default=None, metavar="PATTERN", choices=PATTERNS,
+                        help="inputs are clean RGB: Bayer mosaic with this pattern (rggb, grbg, gbrg, bggr) and fill on the "
+                             "GPU, restore, report PSNR (CPSNR) against the input")
+    scored.add_argument("--raw", type=str, default=None, metavar="PATTERN", choices=PATTERNS,
+                        help="inputs are 1-channel Bayer mosaics with this pattern: fill to RGB, restore, write")
+    ap.add_argument("--demosaic-fill", type=str, default=None, choices=FILLS,
+                    help="with --bayer or --raw: how the missing channels are filled before the model (default malvar)")
     ap.add_argument("--jpeg-subsampling", type=str, default=None, choices=("444", "420"),
                     help="with --jpeg-quality: the chroma subsampling of RGB files (default 444)")
     ap.add_argument("--psnrb", action="store_true",
                     help="with --jpeg-quality or --reference: report PSNR-B beside the PSNR")
     ap.add_argument("--shave", type=int, default=None, metavar="N",
-                    help="with --scale: border pixels cut from both pictures before scoring (default: S)")
+                    help="with --scale or --bayer: border pixels cut from both pictures before scoring (default: S with "
+                         "--scale, 0 with --bayer)")
     ap.add_argument("--seed", type=int, default=2204)
     ap.add_argument("--ssim", action="store_true",
                     help="with --sigma, --reference or --scale: report the SSIM beside the PSNR")
@@ -137,11 +156,11 @@ def parse_args(argv=None):
                        help="average over these modes of 0..7 only, ascending (e.g. 0,1,4,5)")
     args = ap.parse_args(argv)
     args.scored = args.sigma is not None or args.reference is not None or args.scale is not None \
-        or args.jpeg_quality is not None
+        or args.jpeg_quality is not None or args.bayer is not None
     if args.ssim and not args.scored:
-        ap.error("--ssim needs --sigma, --reference, --scale or --jpeg-quality: there is nothing to compare a restored image with otherwise")
+        ap.error("--ssim needs --sigma, --reference, --scale, --jpeg-quality or --bayer: there is nothing to compare a restored image with otherwise")
     if args.y_channel and not args.scored:
-        ap.error("--y-channel needs --sigma, --reference, --scale or --jpeg-quality: there is nothing to compare a restored image with "
+        ap.error("--y-channel needs --sigma, --reference, --scale, --jpeg-quality or --bayer: there is nothing to compare a restored image with "
                  "otherwise")
     if args.jpeg_quality is not None and not 1 <= args.jpeg_quality <= 100:
         ap.error(f"--jpeg-quality: the quality is an integer of 1..100, got {args.jpeg_quality}")
@@ -153,10 +172,15 @@ def parse_args(argv=None):
     for flag, value in (("--scale", args.scale), ("--upscale", args.upscale)):
         if value is not None and not 2 <= value <= 8:
             ap.error(f"{flag}: the scale is an integer of 2..8, got {value}")
-    if args.shave is not None and (args.scale is None or args.shave < 0):
-        ap.error("--shave is a non-negative number of pixels and needs --scale")
+    if args.demosaic_fill is not None and args.bayer is None and args.raw is None:
+        ap.error("--demosaic-fill needs --bayer or --raw")
+    args.demosaic_fill = args.demosaic_fill or "malvar"
+    if args.shave is not None and ((args.scale is None and args.bayer is None) or args.shave < 0):
+        ap.error("--shave is a non-negative number of pixels and needs --scale or --bayer")
     if args.scale is not None and args.shave is None:
         args.shave = args.scale
+    if args.bayer is not None and args.shave is None:
+        args.shave = 0
     args.ensemble = 8 if args.self_ensemble else 1
     if args.ensemble_modes is not None:
         try:
@@ -198,6 +222,19 @@ def main(argv=None) -> None:
                 if len(im.getbands()) != 3:
                     raise SystemExit(f"--y-channel: {path} has {len(im.getbands())} channel(s) ({im.mode}); the Y "
                                      "channel is defined for 3-channel (RGB) images")
+    if args.bayer is not None or args.raw is not None:      # before anything runs
+        flag, bands = ("--bayer", 3) if args.bayer is not None else ("--raw", 1)
+        model_args = conf.get("model", {}).get("args", {})
+        for key in ("n_channels_in", "n_channels_out"):
+            if model_args.get(key) is not None and int(model_args[key]) != 3:
+                raise SystemExit(f"{flag}: the model of {args.yaml_path} has {key} {model_args[key]}; a demosaicked "
+                                 "picture has 3 channels (R, G, B)")
+        for path in files:
+            with Image.open(path) as im:
+                if len(im.getbands()) != bands:
+                    raise SystemExit(f"{flag}: {path} has {len(im.getbands())} channel(s) ({im.mode}); " +
+                                     ("the protocol takes clean 3-channel (RGB) images" if bands == 3 else
+                                      "a raw mosaic is a 1-channel image"))
     if not torch.cuda.is_available():
         raise SystemExit("restore.py needs a GPU: the HIP engine has no CPU path")
     irdu_amd.load_native()
@@ -233,6 +270,10 @@ def main(argv=None) -> None:
             img = np.ascontiguousarray(img[:h, :w])
         elif args.upscale is not None:
             img = irdu_amd.bicubic_up_u8(img, args.upscale)
+        elif args.raw is not None:
+            img = irdu_amd.demosaic_u8(img, args.raw, args.demosaic_fill)
+        elif args.bayer is not None and min(img.shape[:2]) <= 2 * args.shave:
+            raise SystemExit(f"{path}: nothing is left of {img.shape[0]}x{img.shape[1]} after a shave of {args.shave}")
         return img
 
     def input_of(img):
@@ -243,6 +284,8 @@ def main(argv=None) -> None:
                 return irdu_amd.jpeg_degrade_u8(img, args.jpeg_quality, args.jpeg_subsampling)
             except ValueError as e:
                 raise SystemExit(f"--jpeg-quality: {e}")
+        if args.bayer is not None:
+            return irdu_amd.demosaic_u8(img, args.bayer, args.demosaic_fill)
         return img if args.scale is None else irdu_amd.bicubic_degrade_u8(img, args.scale)
 
     def noisy_of(img):
@@ -261,7 +304,7 @@ def main(argv=None) -> None:
             if truth.shape != out.shape:
                 raise SystemExit(f"--reference: {refs[path]} decodes to {truth.shape}, the restored {path} is {out.shape}")
             scored = out
-            if args.scale is not None and args.shave:
+            if args.shave:
                 n = args.shave
                 scored, truth = np.ascontiguousarray(out[n:-n, n:-n]), np.ascontiguousarray(truth[n:-n, n:-n])
             try:
@@ -271,6 +314,7 @@ def main(argv=None) -> None:
             against = (f"bicubic x{args.scale} shave {args.shave}" if args.scale is not None else
                        f"jpeg q{args.jpeg_quality} {'4:2:0' if args.jpeg_subsampling else '4:4:4'}"
                        if args.jpeg_quality is not None else
+                       f"bayer {args.bayer} {args.demosaic_fill} shave {args.shave}" if args.bayer is not None else
                        f"sigma {args.sigma:g}" if args.reference is None else f"reference {refs[path]}")
             line = f"{path} -> {out_path}  {against}  PSNR{tag} {psnrs[-1]:.4f} dB"
             if args.ssim:
