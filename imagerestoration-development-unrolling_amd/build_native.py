@@ -23,9 +23,13 @@ SOURCES = ["graph_ops.hip", "feature_ops.hip", "lnb_ops.hip", "graph_bwd.hip", "
 # every header of csrc/ (a new one can never go stale unnoticed) and the public ABI
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(ROOT, "include", "grr.h")]
 ARCH = "gfx950"
-# lnb_ops, graph_ops: no SLP packing of independent f32 FMAs into v_pk_fma_f32 (the packing
-# needs register-pair moves that cost more than it saves, MI355X_MICROARCH.md; graph_step2_kernel:
-# 1149 -> 1055 VALU instructions per iteration)
+# lnb_ops: no SLP packing of independent f32 ops into v_pk_*_f32 -- a packed f32 op issued on a SIMD that also
+# runs MFMAs costs more than the two scalar ops it replaces (MI355X_MICROARCH.md, "price of one filler beside
+# MFMAs"; the fused LNB's gate measured 10 % of the kernel).
+# graph_ops (no MFMA): the packing needs register-pair moves that cost more than it saves
+# (graph_step2_kernel: 1149 -> 1055 VALU instructions per iteration).
+# feature_edge.hip stays on plain -O3: without SLP feat_edge_kernel loses its 314 v_pk_mul_f32 and its 9
+# spilled VGPRs, and measured slower (1.85-1.87 -> 1.88-1.98 ms per step)
 EXTRA_FLAGS = {"lnb_ops.hip": ["-fno-slp-vectorize"], "graph_ops.hip": ["-fno-slp-vectorize"]}
 
 

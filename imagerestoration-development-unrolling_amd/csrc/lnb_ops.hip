@@ -739,6 +739,22 @@ __global__ void lnb_rep_pack_kernel(const float* __restrict__ w1, const float* _
   }
 }
 
+// the chunk loop's accumulator rescales per component: v_mul_f32, not v_pk_mul_f32 on a SIMD whose other waves
+// issue MFMAs (the same product per component, the same bits).  Both rescales sit in rarely taken branches,
+// yet the kernel measured 1.43 -> 1.37 ms per step at 64 x 256^2 and went from 123 to 108 VGPRs (DESIGN.md
+// §4.pk).  GRR_REP_PK=1: the packed form (A/B builds)
+#ifndef GRR_REP_PK
+#define GRR_REP_PK 0
+#endif
+__device__ __forceinline__ void rep_scale16(f32x16& a, float f) {
+#if GRR_REP_PK
+  a *= f;
+#else
+#pragma unroll
+  for (int u = 0; u < 16; ++u) a[u] *= f;
+#endif
+}
+
 template <int MT, int CS>
 // four waves per SIMD (two workgroups per CU): <= 128 VGPRs; the four-tile instance (C > 96) three
 __global__ __launch_bounds__(64 * LR_NW, MT <= 3 ? 4 : 3) void lnb_rep_kernel(LnbRepArgs a) {
@@ -852,7 +868,7 @@ __global__ __launch_bounds__(64 * LR_NW, MT <= 3 ? 4 : 3) void lnb_rep_kernel(Ln
 
   // gate of the chunk whose GEMM1 accumulator is acc (ring slot of chunk c), then its GEMM2
   auto gate_gemm2 = [&](int c, f32x16 acc) {
-    if (wave_corr) acc *= corr;
+    if (wave_corr) rep_scale16(acc, corr);
     // gate sigmoid(m) m v (REF:947) on the accumulator: registers 2q, 2q + 1 = mask, value of chunk pair
     // 4 (q >> 1) + (q & 1) + 2 kh; the row constants undo the scales and carry the exp2 fold
     const float* cslot = smem + (c % LR_NSLOT) * SLOTF;
@@ -877,7 +893,7 @@ __global__ __launch_bounds__(64 * LR_NW, MT <= 3 ? 4 : 3) void lnb_rep_kernel(Ln
     if (__builtin_amdgcn_readfirstlane((int)__any(eg != E && E != 1000)) != 0) {
       const float f = E != 1000 ? ldexpf(1.0f, eg - E) : 1.0f;
 #pragma unroll
-      for (int t = 0; t < MT; ++t) acc2[t] *= f;
+      for (int t = 0; t < MT; ++t) rep_scale16(acc2[t], f);
     }
     E = eg;
     const int Eu = E == 1000 ? 0 : E;
@@ -1051,6 +1067,30 @@ __global__ void lnb_fused_pack_kernel(const float* __restrict__ w1, const float*
 }
 
 typedef __attribute__((address_space(4))) const float* const_f32_t;
+
+// The consumer gate's f32x4 multiply / fma per component: four v_mul_f32 / v_fmac_f32 in place of two
+// v_pk_mul_f32 / v_pk_fma_f32.  A packed f32 op issued beside the producer wave's MFMAs on the same SIMD costs
+// more than the two scalar ops it replaces (MI355X_MICROARCH.md, "price of one filler beside MFMAs"): the
+// kernel measured 10.88 -> 9.79 ms per step at 64 x 256^2.  Each component sees the same
+// IEEE operations in the same order: bitwise the packed result.  GRR_FUSED_PK=1: the packed forms (A/B builds)
+#ifndef GRR_FUSED_PK
+#define GRR_FUSED_PK 0
+#endif
+__device__ __forceinline__ f32x4 mul4s(const f32x4& a, const f32x4& b) {
+#if GRR_FUSED_PK
+  return a * b;
+#else
+  return f32x4{a[0] * b[0], a[1] * b[1], a[2] * b[2], a[3] * b[3]};
+#endif
+}
+__device__ __forceinline__ f32x4 fma4s(const f32x4& a, const f32x4& b, const f32x4& c) {
+#if GRR_FUSED_PK
+  return __builtin_elementwise_fma(a, b, c);
+#else
+  return f32x4{__builtin_fmaf(a[0], b[0], c[0]), __builtin_fmaf(a[1], b[1], c[1]), __builtin_fmaf(a[2], b[2], c[2]),
+               __builtin_fmaf(a[3], b[3], c[3])};
+#endif
+}
 // consumer mapping: lane per (column, pair half), two rows per lane, taps from the LDS ring (a lane per
 // pixel with scalar taps and B operands by v_permlane32_swap measured slower)
 
@@ -1339,7 +1379,8 @@ __global__ __launch_bounds__(512, 1) void lnb_fused16_kernel(LnbFusedArgs a) {
       float g[2][8];
       // the gate, a pair duo at a time (taps and window of both output rows as 16-byte reads): the window is
       // halo rows 2 cw .. 2 cw + 3, columns col .. col + 2; the two planes' depthwise sums of both pairs run
-      // as packed FMA chains (v_pk_fma_f32: the same fp32 fma per component)
+      // as four scalar fma chains per f32x4 (mul4s / fma4s: the same fp32 fma per component as the packed
+      // form, without its price beside the producer's MFMAs)
       // duo dd = pairs 8 kh + 2 dd, + 1
       const float* hwin4 = smem + (st & 1) * LF_HBUF + 4 * kh * 2 * LF_PP + 4 * (2 * cw * LF_HWD + col);
       const float* tapd = slot + (2 * KS + 2 * MT) * 256 + 4 * kh * LF_DSTR;
@@ -1376,12 +1417,12 @@ __global__ __launch_bounds__(512, 1) void lnb_fused16_kernel(LnbFusedArgs a) {
         ld_taps(dd, 1);
         ld_row(dd, 2);
         __builtin_amdgcn_sched_barrier(0);
-        mv0 = tc[dd][0] * wc[dd][0];
-        mv1 = tc[dd][0] * wc[dd][3];
+        mv0 = mul4s(tc[dd][0], wc[dd][0]);
+        mv1 = mul4s(tc[dd][0], wc[dd][3]);
 #pragma unroll
         for (int x = 1; x < 3; ++x) {
-          mv0 = __builtin_elementwise_fma(tc[dd][x], wc[dd][x], mv0);
-          mv1 = __builtin_elementwise_fma(tc[dd][x], wc[dd][3 + x], mv1);
+          mv0 = fma4s(tc[dd][x], wc[dd][x], mv0);
+          mv1 = fma4s(tc[dd][x], wc[dd][3 + x], mv1);
         }
         __builtin_amdgcn_sched_barrier(0);
         ld_taps(dd, 2);
@@ -1389,8 +1430,8 @@ __global__ __launch_bounds__(512, 1) void lnb_fused16_kernel(LnbFusedArgs a) {
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int x = 0; x < 3; ++x) {
-          mv0 = __builtin_elementwise_fma(tc[dd][3 + x], wc[dd][3 + x], mv0);
-          mv1 = __builtin_elementwise_fma(tc[dd][3 + x], wc[dd][6 + x], mv1);
+          mv0 = fma4s(tc[dd][3 + x], wc[dd][3 + x], mv0);
+          mv1 = fma4s(tc[dd][3 + x], wc[dd][6 + x], mv1);
         }
         __builtin_amdgcn_sched_barrier(0);
         if (dd < 3) {
@@ -1401,8 +1442,8 @@ __global__ __launch_bounds__(512, 1) void lnb_fused16_kernel(LnbFusedArgs a) {
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int x = 0; x < 3; ++x) {
-          mv0 = __builtin_elementwise_fma(tc[dd][6 + x], wc[dd][6 + x], mv0);
-          mv1 = __builtin_elementwise_fma(tc[dd][6 + x], wc[dd][9 + x], mv1);
+          mv0 = fma4s(tc[dd][6 + x], wc[dd][6 + x], mv0);
+          mv1 = fma4s(tc[dd][6 + x], wc[dd][9 + x], mv1);
         }
         gate2(mv0, 0, dd);
         gate2(mv1, 1, dd);
