@@ -69,7 +69,7 @@ from __future__ import annotations
 import math
 from dataclasses import dataclass
 from functools import partial
-from typing import Callable, List, Sequence, Tuple
+from typing import Callable, List, NamedTuple, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -585,6 +585,11 @@ def _evaluate_args(who: str, model: Callable, ensemble, metrics, tiling_args: di
     return modes, metrics, device, tile, halo, micro_batch
 
 
+def _means(values: dict, metrics) -> dict:
+    """{metric: (mean, per-image values)}: what every evaluate function returns."""
+    return {m: (float(np.mean(values[m])), values[m]) for m in metrics}
+
+
 def _evaluate(who: str, model: Callable, images, sigma: float, factor: int, seed: int, across_images: bool, ensemble,
               metrics, tiling_args: dict) -> dict:
     """The one body of evaluate and evaluate_metrics: {metric: (mean, per-image values)} for the metrics asked
@@ -606,7 +611,7 @@ def _evaluate(who: str, model: Callable, images, sigma: float, factor: int, seed
             clean_u8 = torch.from_numpy(_clean_u8(clean)).to(restored.device)
             for m in metrics:
                 values[m].append(_SCORE[m](restored, clean_u8))
-    return {m: (float(np.mean(values[m])), values[m]) for m in metrics}
+    return _means(values, metrics)
 
 
 def evaluate(model: Callable, images, sigma: float = 25.0, factor: int = 16, seed: int = 2204,
@@ -675,6 +680,110 @@ def _score_packs(who: str, restored: ImagePack, clean_u8: ImagePack, metrics) ->
     return values
 
 
+class _Protocol(NamedTuple):
+    """A degrade-from-clean evaluation protocol: take a clean uint8 picture, crop it, degrade it on the device, restore,
+    shave, score.  The record holds what evaluate_sr, evaluate_car and evaluate_demosaic differ in (_sr_protocol,
+    _car_protocol and _demosaic_protocol build it, parameters checked); _evaluate_degraded is the one loop they share,
+    and the restore.py command takes its crop, degradation, shave and label from the same record."""
+    who: str                # the caller its refusals name
+    label: str              # the protocol and its parameters in a few words: the command's "against" text
+    defined_on: str         # "image i is float32; {defined_on} uint8 pictures"
+    admit: Callable         # admit(i, t) raises the protocol's refusal of a uint8 H x W x C picture it does not take
+    crop: Callable          # crop(h, w) -> the (h, w) kept from the top left
+    shave: int              # border pixels cut from the restored and the clean picture before scoring
+    left_after: str         # "image i is (shape): nothing is left {left_after}"
+    scored: str             # what the metrics' refusals call the scored picture i, "image {i}" formatted
+    degrade: Callable       # the cropped clean picture on the device -> the model's input, there too
+
+    def shaved(self, a):
+        """``a`` (H x W x C, array or tensor) without the shave's border: a view."""
+        n = self.shave
+        return a[n:a.shape[0] - n, n:a.shape[1] - n] if n else a
+
+
+def _check_shave(who: str, shave) -> int:
+    if isinstance(shave, bool) or not isinstance(shave, int) or shave < 0:
+        raise ValueError(f"{who}: shave is a non-negative integer, got {shave!r}")
+    return shave
+
+
+def _sr_protocol(who: str, scale, shave) -> _Protocol:
+    """Bicubic super-resolution: mod-crop to multiples of ``scale``, the bicubic down and back up, a shave of
+    ``shave`` (default ``scale``)."""
+    scale = kernels._check_scale(who, scale)
+    shave = _check_shave(who, scale if shave is None else shave)
+    return _Protocol(who, label=f"bicubic x{scale} shave {shave}", defined_on="the protocol is defined on",
+                     admit=lambda i, t: None, crop=lambda h, w: (h // scale * scale, w // scale * scale), shave=shave,
+                     left_after=f"after the crop to multiples of {scale} and a shave of {shave}",
+                     scored="image {i} after the shave", degrade=lambda clean: kernels.u8_bicubic_degrade(clean, scale))
+
+
+def _car_protocol(who: str, quality, subsampling) -> _Protocol:
+    """JPEG compression-artifact removal: the whole picture through the JPEG round trip, no shave."""
+    quality = kernels._check_quality(who, quality)
+    subsampling = kernels._check_subsampling(who, subsampling)
+
+    def admit(i, t):
+        if not kernels.jpeg_ok(t.shape[2], t.shape[0], t.shape[1], subsampling):
+            raise ValueError(f"{who}: image {i} is {tuple(t.shape)}; JPEG takes 1 or 3 channels (gray or R, G, B)")
+
+    return _Protocol(who, label=f"jpeg q{quality} {'4:2:0' if subsampling else '4:4:4'}", defined_on="JPEG is defined on",
+                     admit=admit, crop=lambda h, w: (h, w), shave=0, left_after="", scored="image {i}",
+                     degrade=lambda clean: kernels.u8_jpeg(clean, quality, subsampling))
+
+
+def _demosaic_protocol(who: str, pattern, fill, shave) -> _Protocol:
+    """Bayer demosaicking: the whole R, G, B picture mosaicked and filled, a shave of ``shave``."""
+    pattern, fill = kernels._check_pattern(who, pattern), kernels._check_fill(who, fill)
+    shave = _check_shave(who, shave)
+
+    def admit(i, t):
+        if t.shape[2] != 3 or not kernels.demosaic_ok(3, t.shape[0], t.shape[1]):
+            raise ValueError(f"{who}: image {i} is {tuple(t.shape)}; the protocol takes clean R, G, B pictures")
+
+    return _Protocol(who, label=f"bayer {kernels.DEMOSAIC_PATTERNS[pattern]} {kernels.DEMOSAIC_FILLS[fill]} shave {shave}",
+                     defined_on="the mosaic is defined on", admit=admit, crop=lambda h, w: (h, w), shave=shave,
+                     left_after=f"after a shave of {shave}", scored="image {i} after the shave",
+                     degrade=lambda clean: kernels.u8_demosaic(clean, pattern, fill))
+
+
+def _evaluate_degraded(p: _Protocol, model: Callable, images, factor: int, modes, metrics, device, tile, halo,
+                       micro_batch) -> dict:
+    """The one body of evaluate_sr, evaluate_car and evaluate_demosaic, after _evaluate_args and the protocol's own
+    checks: every picture is checked before any launch; then per picture degrade, restore, shave, score."""
+    who = p.who
+    if len(images) < 1:
+        raise ValueError(f"{who}: no images")
+    cleans = []
+    for i in range(len(images)):
+        try:
+            t, _ = _checked_image(images[i])
+        except ValueError as e:
+            raise ValueError(f"{who}: image {i}: {e}") from None
+        if t.dtype != torch.uint8:
+            raise ValueError(f"{who}: image {i} is {t.dtype}; {p.defined_on} uint8 pictures")
+        p.admit(i, t)
+        h, w = p.crop(t.shape[0], t.shape[1])
+        if min(h, w) <= 2 * p.shave:        # with no shave: a side the crop leaves nothing of
+            raise ValueError(f"{who}: image {i} is {tuple(t.shape)}: nothing is left {p.left_after}")
+        _check_metric_shape(who, p.scored.format(i=i), (h - 2 * p.shave, w - 2 * p.shave, t.shape[2]), metrics)
+        plan(h, w, factor, tile, halo)                          # raises what the restoration would
+        cleans.append(t[:h, :w])
+    if device is None:
+        device = next((t.device for t in cleans if t.is_cuda), None)
+    values = {m: [] for m in metrics}
+    for t in cleans:
+        clean = _to_device(t, device)
+        restored = _restore_device(model, p.degrade(clean), None, factor, tile, halo, micro_batch, True, modes)
+        if restored.shape != clean.shape:
+            raise ValueError(f"{who}: the model returns {restored.shape[2]} channel(s) for {clean.shape[2]}; no score")
+        # the shave is an ATen slice and copy: a few hundred kilobytes per picture, not a hot path
+        restored, clean = p.shaved(restored).contiguous(), p.shaved(clean).contiguous()
+        for m in metrics:
+            values[m].append(_SCORE[m](restored, clean))
+    return _means(values, metrics)
+
+
 def _resized_u8(who: str, a, resize):
     """``resize`` (device uint8 H x W x C -> device uint8) of a uint8 picture, numpy array or tensor, host or device;
     the result is of the input's kind and, for a tensor, on its device."""
@@ -725,45 +834,9 @@ def evaluate_sr(model: Callable, images, scale: int, shave: int = None, factor: 
     Everything is checked before any launch: the scale (2..8), the shave, uint8 pictures, a picture smaller than
     ``scale`` or than the shave leaves, and what the metrics need of the shaved picture (SSIM: both sides at least
     11; the Y-channel metrics: 3 channels)."""
-    who = "evaluate_sr"
-    modes, metrics, device, tile, halo, micro_batch = _evaluate_args(who, model, ensemble, metrics, tiling_args)
-    scale = kernels._check_scale(who, scale)
-    shave = scale if shave is None else shave
-    if isinstance(shave, bool) or not isinstance(shave, int) or shave < 0:
-        raise ValueError(f"{who}: shave is a non-negative integer, got {shave!r}")
-    if len(images) < 1:
-        raise ValueError(f"{who}: no images")
-    cleans = []
-    for i in range(len(images)):
-        try:
-            t, _ = _checked_image(images[i])
-        except ValueError as e:
-            raise ValueError(f"{who}: image {i}: {e}") from None
-        if t.dtype != torch.uint8:
-            raise ValueError(f"{who}: image {i} is {t.dtype}; the protocol is defined on uint8 pictures")
-        h, w = t.shape[0] // scale * scale, t.shape[1] // scale * scale
-        if min(h, w) < 1 or min(h, w) <= 2 * shave:
-            raise ValueError(f"{who}: image {i} is {tuple(t.shape)}: nothing is left after the crop to multiples of "
-                             f"{scale} and a shave of {shave}")
-        _check_metric_shape(who, f"image {i} after the shave", (h - 2 * shave, w - 2 * shave, t.shape[2]), metrics)
-        plan(h, w, factor, tile, halo)                          # raises what the restoration would
-        cleans.append(t[:h, :w])
-    if device is None:
-        device = next((t.device for t in cleans if t.is_cuda), None)
-    values = {m: [] for m in metrics}
-    for i, t in enumerate(cleans):
-        clean = _to_device(t, device)
-        restored = _restore_device(model, kernels.u8_bicubic_degrade(clean, scale), None, factor, tile, halo,
-                                   micro_batch, True, modes)
-        if restored.shape != clean.shape:
-            raise ValueError(f"{who}: the model returns {restored.shape[2]} channel(s) for {clean.shape[2]}; no score")
-        if shave:       # an ATen slice and copy: a few hundred kilobytes per picture, not a hot path
-            h, w = clean.shape[:2]
-            restored = restored[shave:h - shave, shave:w - shave].contiguous()
-            clean = clean[shave:h - shave, shave:w - shave].contiguous()
-        for m in metrics:
-            values[m].append(_SCORE[m](restored, clean))
-    return {m: (float(np.mean(values[m])), values[m]) for m in metrics}
+    modes, metrics, device, tile, halo, micro_batch = _evaluate_args("evaluate_sr", model, ensemble, metrics, tiling_args)
+    return _evaluate_degraded(_sr_protocol("evaluate_sr", scale, shave), model, images, factor, modes, metrics, device,
+                              tile, halo, micro_batch)
 
 
 def jpeg_degrade_u8(a, quality: int, subsampling: int = 0):
@@ -789,37 +862,9 @@ def evaluate_car(model: Callable, images, quality: int, subsampling: int = 0, fa
     Everything is checked before any launch: the quality (1..100), the subsampling (0 or 2), uint8 pictures of 1 or
     3 channels, and what the metrics need of a picture (SSIM: both sides at least 11; PSNR-B: at least 16; the
     Y-channel metrics: 3 channels)."""
-    who = "evaluate_car"
-    modes, metrics, device, tile, halo, micro_batch = _evaluate_args(who, model, ensemble, metrics, tiling_args)
-    quality = kernels._check_quality(who, quality)
-    subsampling = kernels._check_subsampling(who, subsampling)
-    if len(images) < 1:
-        raise ValueError(f"{who}: no images")
-    cleans = []
-    for i in range(len(images)):
-        try:
-            t, _ = _checked_image(images[i])
-        except ValueError as e:
-            raise ValueError(f"{who}: image {i}: {e}") from None
-        if t.dtype != torch.uint8:
-            raise ValueError(f"{who}: image {i} is {t.dtype}; JPEG is defined on uint8 pictures")
-        if not kernels.jpeg_ok(t.shape[2], t.shape[0], t.shape[1], subsampling):
-            raise ValueError(f"{who}: image {i} is {tuple(t.shape)}; JPEG takes 1 or 3 channels (gray or R, G, B)")
-        _check_metric_shape(who, f"image {i}", t.shape, metrics)
-        plan(t.shape[0], t.shape[1], factor, tile, halo)                          # raises what the restoration would
-        cleans.append(t)
-    if device is None:
-        device = next((t.device for t in cleans if t.is_cuda), None)
-    values = {m: [] for m in metrics}
-    for t in cleans:
-        clean = _to_device(t, device)
-        restored = _restore_device(model, kernels.u8_jpeg(clean, quality, subsampling), None, factor, tile, halo,
-                                   micro_batch, True, modes)
-        if restored.shape != clean.shape:
-            raise ValueError(f"{who}: the model returns {restored.shape[2]} channel(s) for {clean.shape[2]}; no score")
-        for m in metrics:
-            values[m].append(_SCORE[m](restored, clean))
-    return {m: (float(np.mean(values[m])), values[m]) for m in metrics}
+    modes, metrics, device, tile, halo, micro_batch = _evaluate_args("evaluate_car", model, ensemble, metrics, tiling_args)
+    return _evaluate_degraded(_car_protocol("evaluate_car", quality, subsampling), model, images, factor, modes, metrics,
+                              device, tile, halo, micro_batch)
 
 
 def demosaic_u8(a, pattern, fill="malvar"):
@@ -851,45 +896,10 @@ def evaluate_demosaic(model: Callable, images, pattern="rggb", fill="malvar", sh
     Everything is checked before any launch: the pattern, the fill, the shave, uint8 pictures of 3 channels, a
     picture smaller than the shave leaves, and what the metrics need of the shaved picture (SSIM: both sides at
     least 11; PSNR-B: at least 16)."""
-    who = "evaluate_demosaic"
-    modes, metrics, device, tile, halo, micro_batch = _evaluate_args(who, model, ensemble, metrics, tiling_args)
-    pattern, fill = kernels._check_pattern(who, pattern), kernels._check_fill(who, fill)
-    if isinstance(shave, bool) or not isinstance(shave, int) or shave < 0:
-        raise ValueError(f"{who}: shave is a non-negative integer, got {shave!r}")
-    if len(images) < 1:
-        raise ValueError(f"{who}: no images")
-    cleans = []
-    for i in range(len(images)):
-        try:
-            t, _ = _checked_image(images[i])
-        except ValueError as e:
-            raise ValueError(f"{who}: image {i}: {e}") from None
-        if t.dtype != torch.uint8:
-            raise ValueError(f"{who}: image {i} is {t.dtype}; the mosaic is defined on uint8 pictures")
-        h, w = t.shape[:2]
-        if t.shape[2] != 3 or not kernels.demosaic_ok(3, h, w):
-            raise ValueError(f"{who}: image {i} is {tuple(t.shape)}; the protocol takes clean R, G, B pictures")
-        if min(h, w) <= 2 * shave:
-            raise ValueError(f"{who}: image {i} is {tuple(t.shape)}: nothing is left after a shave of {shave}")
-        _check_metric_shape(who, f"image {i} after the shave", (h - 2 * shave, w - 2 * shave, 3), metrics)
-        plan(h, w, factor, tile, halo)                                            # raises what the restoration would
-        cleans.append(t)
-    if device is None:
-        device = next((t.device for t in cleans if t.is_cuda), None)
-    values = {m: [] for m in metrics}
-    for t in cleans:
-        clean = _to_device(t, device)
-        restored = _restore_device(model, kernels.u8_demosaic(clean, pattern, fill), None, factor, tile, halo,
-                                   micro_batch, True, modes)
-        if restored.shape != clean.shape:
-            raise ValueError(f"{who}: the model returns {restored.shape[2]} channel(s) for 3; no score")
-        if shave:       # an ATen slice and copy, as in evaluate_sr
-            h, w = clean.shape[:2]
-            restored = restored[shave:h - shave, shave:w - shave].contiguous()
-            clean = clean[shave:h - shave, shave:w - shave].contiguous()
-        for m in metrics:
-            values[m].append(_SCORE[m](restored, clean))
-    return {m: (float(np.mean(values[m])), values[m]) for m in metrics}
+    modes, metrics, device, tile, halo, micro_batch = _evaluate_args("evaluate_demosaic", model, ensemble, metrics,
+                                                                     tiling_args)
+    return _evaluate_degraded(_demosaic_protocol("evaluate_demosaic", pattern, fill, shave), model, images, factor, modes,
+                              metrics, device, tile, halo, micro_batch)
 
 
 def evaluate_pairs(model: Callable, inputs, targets, factor: int = 16, across_images: bool = False, ensemble=1,
@@ -941,4 +951,4 @@ def evaluate_pairs(model: Callable, inputs, targets, factor: int = 16, across_im
             target = target.to(restored.device)
             for m in metrics:
                 values[m].append(_SCORE[m](restored, target))
-    return {m: (float(np.mean(values[m])), values[m]) for m in metrics}
+    return _means(values, metrics)

@@ -52,7 +52,7 @@ import logging
 import math
 import os
 import random
-from typing import Dict, Iterator, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, Iterator, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -1073,14 +1073,45 @@ def validate(model: nn.Module, images, sigma: float = 25.0, factor: int = 16, se
         img_true_255 = np.rint(img_true.astype(np.float64) * 255.0).astype(np.float32)   # the uint8 image (:253)
         mse = np.square(img_true_255 - restored).mean()                                  # float32, as :273
         psnrs.append(float(20 * np.log10(np.float32(255.0) / np.sqrt(mse))))
-    acc = torch.tensor([float(np.sum(psnrs)), float(len(psnrs))], dtype=torch.float64)
+    if was_training:
+        model.train()
+    return _mean_over_ranks(psnrs, world, device)
+
+
+def _mean_over_ranks(values, world: int, device) -> float:
+    """The mean of per-image values over all ranks: this rank's float64 [sum, count], moved to ``device`` under NCCL,
+    all-reduced; the one tail of validate and of every validate_* below."""
+    acc = torch.tensor([float(np.sum(values)), float(len(values))], dtype=torch.float64)
     if world > 1:
         if torch.distributed.get_backend() == "nccl":
             acc = acc.to(device)
         torch.distributed.all_reduce(acc)
-    if was_training:
-        model.train()
     return float(acc[0] / acc[1])
+
+
+def _clean_share_u8(images, rank: int, world: int) -> list:
+    """This rank's share (sharding.shard_range) of a clean test set as uint8 H x W x C arrays: a 2-D picture gets its
+    channel axis, a float one in [0, 1] on the uint8 grid (as TestImagesCSV yields them) becomes rint(x 255)."""
+    s, e = sharding.shard_range(len(images), rank, world)
+    mine = []
+    for i in range(s, e):
+        a = np.asarray(images[i])
+        a = a[:, :, None] if a.ndim == 2 else a
+        mine.append(a if a.dtype == np.uint8 else np.rint(a.astype(np.float64) * 255.0).astype(np.uint8))
+    return mine
+
+
+def _validate_degraded(name: str, val_metrics, evaluate: Callable, model, images, device, metric: str, **args) -> float:
+    """The one body of validate_sr, validate_car and validate_demosaic: the metric checked first, this rank's share
+    of the pictures through ``evaluate`` (a restore.evaluate_* with its protocol's ``args``), the mean over ranks."""
+    if metric not in val_metrics:
+        raise ValueError(f"{name}: metric is one of {val_metrics}, got {metric!r}")
+    rank, world = sharding.world()
+    if device is None:
+        device = next(model.parameters()).device
+    mine = _clean_share_u8(images, rank, world)
+    scores = evaluate(model, mine, device=device, metrics=(metric,), **args)[metric][1] if mine else []
+    return _mean_over_ranks(scores, world, device)
 
 
 VAL_PAIR_METRICS = ("psnr", "psnr_y")
@@ -1105,12 +1136,7 @@ def validate_pairs(model: nn.Module, pairs, factor: int = 16, device=None, metri
     mine = [pairs[i] for i in range(s, e)]
     psnrs = restore.evaluate_pairs(model, [p[0] for p in mine], [p[1] for p in mine], factor=factor, device=device,
                                    metrics=(metric,), **tiling_args)[metric][1] if mine else []
-    acc = torch.tensor([float(np.sum(psnrs)), float(len(psnrs))], dtype=torch.float64)
-    if world > 1:
-        if torch.distributed.get_backend() == "nccl":
-            acc = acc.to(device)
-        torch.distributed.all_reduce(acc)
-    return float(acc[0] / acc[1])
+    return _mean_over_ranks(psnrs, world, device)
 
 
 VAL_SR_METRICS = ("psnr", "psnr_y")
@@ -1126,25 +1152,8 @@ def validate_sr(model: nn.Module, images, scale: int, shave: Optional[int] = Non
 
     Several ranks: sharded and all-reduced as validate_pairs does."""
     from . import restore
-    if metric not in VAL_SR_METRICS:
-        raise ValueError(f"validate_sr: metric is one of {VAL_SR_METRICS}, got {metric!r}")
-    rank, world = sharding.world()
-    if device is None:
-        device = next(model.parameters()).device
-    s, e = sharding.shard_range(len(images), rank, world)
-    mine = []
-    for i in range(s, e):
-        a = np.asarray(images[i])
-        a = a[:, :, None] if a.ndim == 2 else a
-        mine.append(a if a.dtype == np.uint8 else np.rint(a.astype(np.float64) * 255.0).astype(np.uint8))
-    psnrs = restore.evaluate_sr(model, mine, scale, shave=shave, factor=factor, device=device, metrics=(metric,),
-                                **tiling_args)[metric][1] if mine else []
-    acc = torch.tensor([float(np.sum(psnrs)), float(len(psnrs))], dtype=torch.float64)
-    if world > 1:
-        if torch.distributed.get_backend() == "nccl":
-            acc = acc.to(device)
-        torch.distributed.all_reduce(acc)
-    return float(acc[0] / acc[1])
+    return _validate_degraded("validate_sr", VAL_SR_METRICS, restore.evaluate_sr, model, images, device, metric,
+                              scale=scale, shave=shave, factor=factor, **tiling_args)
 
 
 VAL_CAR_METRICS = ("psnr", "psnr_y", "psnrb")
@@ -1160,25 +1169,8 @@ def validate_car(model: nn.Module, images, jpeg_quality: int, subsampling: int =
 
     Several ranks: sharded and all-reduced as validate_pairs does."""
     from . import restore
-    if metric not in VAL_CAR_METRICS:
-        raise ValueError(f"validate_car: metric is one of {VAL_CAR_METRICS}, got {metric!r}")
-    rank, world = sharding.world()
-    if device is None:
-        device = next(model.parameters()).device
-    s, e = sharding.shard_range(len(images), rank, world)
-    mine = []
-    for i in range(s, e):
-        a = np.asarray(images[i])
-        a = a[:, :, None] if a.ndim == 2 else a
-        mine.append(a if a.dtype == np.uint8 else np.rint(a.astype(np.float64) * 255.0).astype(np.uint8))
-    scores = restore.evaluate_car(model, mine, jpeg_quality, subsampling=subsampling, factor=factor, device=device,
-                                  metrics=(metric,), **tiling_args)[metric][1] if mine else []
-    acc = torch.tensor([float(np.sum(scores)), float(len(scores))], dtype=torch.float64)
-    if world > 1:
-        if torch.distributed.get_backend() == "nccl":
-            acc = acc.to(device)
-        torch.distributed.all_reduce(acc)
-    return float(acc[0] / acc[1])
+    return _validate_degraded("validate_car", VAL_CAR_METRICS, restore.evaluate_car, model, images, device, metric,
+                              quality=jpeg_quality, subsampling=subsampling, factor=factor, **tiling_args)
 
 
 VAL_DEMOSAIC_METRICS = ("psnr", "psnr_y", "ssim")
@@ -1194,24 +1186,38 @@ def validate_demosaic(model: nn.Module, images, bayer="rggb", fill="malvar", sha
 
     Several ranks: sharded and all-reduced as validate_pairs does."""
     from . import restore
-    if metric not in VAL_DEMOSAIC_METRICS:
-        raise ValueError(f"validate_demosaic: metric is one of {VAL_DEMOSAIC_METRICS}, got {metric!r}")
-    rank, world = sharding.world()
-    if device is None:
-        device = next(model.parameters()).device
-    s, e = sharding.shard_range(len(images), rank, world)
-    mine = []
-    for i in range(s, e):
-        a = np.asarray(images[i])
-        mine.append(a if a.dtype == np.uint8 else np.rint(a.astype(np.float64) * 255.0).astype(np.uint8))
-    scores = restore.evaluate_demosaic(model, mine, bayer, fill=fill, shave=shave, factor=factor, device=device,
-                                       metrics=(metric,), **tiling_args)[metric][1] if mine else []
-    acc = torch.tensor([float(np.sum(scores)), float(len(scores))], dtype=torch.float64)
-    if world > 1:
-        if torch.distributed.get_backend() == "nccl":
-            acc = acc.to(device)
-        torch.distributed.all_reduce(acc)
-    return float(acc[0] / acc[1])
+    return _validate_degraded("validate_demosaic", VAL_DEMOSAIC_METRICS, restore.evaluate_demosaic, model, images, device,
+                              metric, pattern=bayer, fill=fill, shave=shave, factor=factor, **tiling_args)
+
+
+class _ValProtocol(NamedTuple):
+    """A row of _VAL_PROTOCOLS: how a ``datasets.val`` section selects a validator, and which of its keys the
+    validator gets (beside factor, tile, halo, micro_batch and metric, which every row has)."""
+    key: Optional[str]              # the YAML key that selects the row on a set of ``dataset``; None: the set alone does
+    dataset: type
+    convert: Optional[Callable]     # the selecting key's value as the validator takes it
+    int_keys: Tuple[str, ...]       # the row's own optional integer keys
+    choices: dict                   # its string keys, the selecting one included, with their allowed values
+    metrics: Tuple[str, ...]
+    validator: Callable
+
+
+_VAL_PROTOCOLS = (      # in order of precedence; a section that selects no row is the noise protocol, validate's
+    _ValProtocol("jpeg_quality", TestImagesCSV, int, ("subsampling",), {}, VAL_CAR_METRICS, validate_car),
+    _ValProtocol("bayer", TestImagesCSV, str, ("shave",), {"bayer": BAYER_PATTERNS, "fill": BAYER_FILLS},
+                 VAL_DEMOSAIC_METRICS, validate_demosaic),
+    _ValProtocol("scale", TestImagesCSV, int, ("shave",), {}, VAL_SR_METRICS, validate_sr),
+    _ValProtocol(None, TestPairsCSV, None, (), {}, VAL_PAIR_METRICS, validate_pairs),
+)
+
+
+def val_check(val_set, val_args: dict) -> Callable:
+    """The validator of what create_val_dataset returned: ``val_check(val_set, val_args)(model, val_set, device=device,
+    **val_args)`` is the validation run() makes."""
+    for p in _VAL_PROTOCOLS:
+        if (p.key in val_args) if p.key else isinstance(val_set, p.dataset):
+            return p.validator
+    return validate
 
 
 def create_val_dataset(conf: dict):
@@ -1230,43 +1236,22 @@ def create_val_dataset(conf: dict):
     cls = VAL_DATASETS.get(vconf["type"])
     if cls is None:
         raise ValueError(f"Validation dataset {vconf['type']} is not found.")
-    if cls is TestImagesCSV and vconf.get("jpeg_quality") is not None:
-        args = {k: int(vconf[k]) for k in ("tile", "halo", "micro_batch", "subsampling") if vconf.get(k) is not None}
+    for p in _VAL_PROTOCOLS:
+        if cls is not p.dataset or (p.key is not None and vconf.get(p.key) is None):
+            continue
+        for k, allowed in p.choices.items():
+            if vconf.get(k) is not None and vconf[k] not in allowed:
+                raise ValueError(f"datasets.val.{k} is one of {allowed}, got {vconf[k]!r}")
+        args = {k: int(vconf[k]) for k in ("tile", "halo", "micro_batch") + p.int_keys if vconf.get(k) is not None}
+        args.update({k: str(vconf[k]) for k in p.choices if k != p.key and vconf.get(k) is not None})
         if vconf.get("metric") is not None:
-            if vconf["metric"] not in VAL_CAR_METRICS:
-                raise ValueError(f"datasets.val.metric is one of {VAL_CAR_METRICS}, got {vconf['metric']!r}")
+            if vconf["metric"] not in p.metrics:
+                raise ValueError(f"datasets.val.metric is one of {p.metrics}, got {vconf['metric']!r}")
             args["metric"] = str(vconf["metric"])
-        return cls(**vconf.get("dataset_args", {})), dict(args, jpeg_quality=int(vconf["jpeg_quality"]),
-                                                           factor=int(vconf.get("factor", 16)))
-    if cls is TestImagesCSV and vconf.get("bayer") is not None:
-        if vconf["bayer"] not in BAYER_PATTERNS:
-            raise ValueError(f"datasets.val.bayer is one of {BAYER_PATTERNS}, got {vconf['bayer']!r}")
-        if vconf.get("fill") is not None and vconf["fill"] not in BAYER_FILLS:
-            raise ValueError(f"datasets.val.fill is one of {BAYER_FILLS}, got {vconf['fill']!r}")
-        args = {k: int(vconf[k]) for k in ("tile", "halo", "micro_batch", "shave") if vconf.get(k) is not None}
-        if vconf.get("fill") is not None:
-            args["fill"] = str(vconf["fill"])
-        if vconf.get("metric") is not None:
-            if vconf["metric"] not in VAL_DEMOSAIC_METRICS:
-                raise ValueError(f"datasets.val.metric is one of {VAL_DEMOSAIC_METRICS}, got {vconf['metric']!r}")
-            args["metric"] = str(vconf["metric"])
-        return cls(**vconf.get("dataset_args", {})), dict(args, bayer=str(vconf["bayer"]),
-                                                           factor=int(vconf.get("factor", 16)))
-    if cls is TestImagesCSV and vconf.get("scale") is not None:
-        args = {k: int(vconf[k]) for k in ("tile", "halo", "micro_batch", "shave") if vconf.get(k) is not None}
-        if vconf.get("metric") is not None:
-            if vconf["metric"] not in VAL_SR_METRICS:
-                raise ValueError(f"datasets.val.metric is one of {VAL_SR_METRICS}, got {vconf['metric']!r}")
-            args["metric"] = str(vconf["metric"])
-        return cls(**vconf.get("dataset_args", {})), dict(args, scale=int(vconf["scale"]),
-                                                           factor=int(vconf.get("factor", 16)))
-    if cls is TestPairsCSV:
-        args = {k: int(vconf[k]) for k in ("tile", "halo", "micro_batch") if vconf.get(k) is not None}
-        if vconf.get("metric") is not None:
-            if vconf["metric"] not in VAL_PAIR_METRICS:
-                raise ValueError(f"datasets.val.metric is one of {VAL_PAIR_METRICS}, got {vconf['metric']!r}")
-            args["metric"] = str(vconf["metric"])
-        return cls(**vconf.get("dataset_args", {})), dict(args, factor=int(vconf.get("factor", 16)))
+        dataset = cls(**vconf.get("dataset_args", {}))
+        if p.key is not None:
+            args[p.key] = p.convert(vconf[p.key])
+        return dataset, dict(args, factor=int(vconf.get("factor", 16)))
     return cls(**vconf.get("dataset_args", {})), {"sigma": float(vconf.get("sigma", 25.0)),
                                                    "factor": int(vconf.get("factor", 16))}
 
@@ -1587,11 +1572,7 @@ def run(conf: dict, device=None, max_iters: Optional[int] = None) -> Trainer:
                     save()
                     saved_at = trainer.i
                 if val_every and trainer.i % val_every == 0:
-                    check = validate_pairs if isinstance(val_set, TestPairsCSV) else \
-                        validate_car if "jpeg_quality" in val_args else \
-                        validate_demosaic if "bayer" in val_args else \
-                        validate_sr if "scale" in val_args else validate
-                    psnr = check(trainer.model, val_set, device=device, **val_args)
+                    psnr = val_check(val_set, val_args)(trainer.model, val_set, device=device, **val_args)
                     trainer.val_history.append((trainer.i, psnr))
                     if rank == 0:
                         LOG.info("FINISH VAL EPOCH %d - iter=%d - psnr_testing=%.4f", epoch, trainer.i, psnr)

@@ -140,10 +140,10 @@ def parse_args(argv=None):
                          "--scale, 0 with --bayer)")
     ap.add_argument("--seed", type=int, default=2204)
     ap.add_argument("--ssim", action="store_true",
-                    help="with --sigma, --reference or --scale: report the SSIM beside the PSNR")
+                    help="with --sigma, --reference, --scale, --jpeg-quality or --bayer: report the SSIM beside the PSNR")
     ap.add_argument("--y-channel", action="store_true",
-                    help="with --sigma, --reference or --scale: score on the Y channel of YCbCr (BT.601 luma of RGB images): "
-                         "PSNR-Y, and with --ssim SSIM-Y, in place of the RGB values")
+                    help="with --sigma, --reference, --scale, --jpeg-quality or --bayer: score on the Y channel of YCbCr "
+                         "(BT.601 luma of RGB images): PSNR-Y, and with --ssim SSIM-Y, in place of the RGB values")
     ap.add_argument("--tile", type=int, default=None)
     ap.add_argument("--halo", type=int, default=None)
     ap.add_argument("--factor", type=int, default=16)
@@ -211,30 +211,33 @@ def main(argv=None) -> None:
         check_references(files, found)
         refs = dict(zip(files, found))
     conf = training.parse_options(args.yaml_path)
-    if args.y_channel:      # before anything runs
+
+    def need_three_channels(flag, model_needs, bands, files_need):
+        """Before anything runs: SystemExit for a model of the YAML that is not 3-channel, or a file without ``bands``."""
         model_args = conf.get("model", {}).get("args", {})
         for key in ("n_channels_in", "n_channels_out"):
             if model_args.get(key) is not None and int(model_args[key]) != 3:
-                raise SystemExit(f"--y-channel: the model of {args.yaml_path} has {key} {model_args[key]}; the Y channel "
-                                 "is defined for 3-channel (RGB) models")
-        for path in files:
-            with Image.open(path) as im:
-                if len(im.getbands()) != 3:
-                    raise SystemExit(f"--y-channel: {path} has {len(im.getbands())} channel(s) ({im.mode}); the Y "
-                                     "channel is defined for 3-channel (RGB) images")
-    if args.bayer is not None or args.raw is not None:      # before anything runs
-        flag, bands = ("--bayer", 3) if args.bayer is not None else ("--raw", 1)
-        model_args = conf.get("model", {}).get("args", {})
-        for key in ("n_channels_in", "n_channels_out"):
-            if model_args.get(key) is not None and int(model_args[key]) != 3:
-                raise SystemExit(f"{flag}: the model of {args.yaml_path} has {key} {model_args[key]}; a demosaicked "
-                                 "picture has 3 channels (R, G, B)")
+                raise SystemExit(f"{flag}: the model of {args.yaml_path} has {key} {model_args[key]}; {model_needs}")
         for path in files:
             with Image.open(path) as im:
                 if len(im.getbands()) != bands:
-                    raise SystemExit(f"{flag}: {path} has {len(im.getbands())} channel(s) ({im.mode}); " +
-                                     ("the protocol takes clean 3-channel (RGB) images" if bands == 3 else
-                                      "a raw mosaic is a 1-channel image"))
+                    raise SystemExit(f"{flag}: {path} has {len(im.getbands())} channel(s) ({im.mode}); {files_need}")
+
+    if args.y_channel:
+        need_three_channels("--y-channel", "the Y channel is defined for 3-channel (RGB) models", 3,
+                            "the Y channel is defined for 3-channel (RGB) images")
+    if args.bayer is not None:
+        need_three_channels("--bayer", "a demosaicked picture has 3 channels (R, G, B)", 3,
+                            "the protocol takes clean 3-channel (RGB) images")
+    if args.raw is not None:
+        need_three_channels("--raw", "a demosaicked picture has 3 channels (R, G, B)", 1, "a raw mosaic is a 1-channel image")
+    # the degrade-from-clean protocol asked for, if any: read, input_of and finish take its crop, degradation, shave
+    # and label from the record (parse_args has checked the values)
+    protocol = (restore._sr_protocol("--scale", args.scale, args.shave) if args.scale is not None else
+                restore._car_protocol("--jpeg-quality", args.jpeg_quality, args.jpeg_subsampling)
+                if args.jpeg_quality is not None else
+                restore._demosaic_protocol("--bayer", args.bayer, args.demosaic_fill, args.shave)
+                if args.bayer is not None else None)
     if not torch.cuda.is_available():
         raise SystemExit("restore.py needs a GPU: the HIP engine has no CPU path")
     irdu_amd.load_native()
@@ -262,31 +265,26 @@ def main(argv=None) -> None:
     def read(path):
         """The picture the model's input is made of and, when scoring without a reference, compared with."""
         img = decode(path)
-        if args.scale is not None:          # the protocol's mod-crop
-            h, w = img.shape[0] // args.scale * args.scale, img.shape[1] // args.scale * args.scale
-            if min(h, w) <= 2 * args.shave:
-                raise SystemExit(f"{path}: nothing is left of {img.shape[0]}x{img.shape[1]} after the crop to multiples "
-                                 f"of {args.scale} and a shave of {args.shave}")
+        if protocol is not None:
+            h, w = protocol.crop(img.shape[0], img.shape[1])
+            if min(h, w) <= 2 * protocol.shave:
+                raise SystemExit(f"{path}: nothing is left of {img.shape[0]}x{img.shape[1]} {protocol.left_after}")
             img = np.ascontiguousarray(img[:h, :w])
         elif args.upscale is not None:
             img = irdu_amd.bicubic_up_u8(img, args.upscale)
         elif args.raw is not None:
             img = irdu_amd.demosaic_u8(img, args.raw, args.demosaic_fill)
-        elif args.bayer is not None and min(img.shape[:2]) <= 2 * args.shave:
-            raise SystemExit(f"{path}: nothing is left of {img.shape[0]}x{img.shape[1]} after a shave of {args.shave}")
         return img
 
     def input_of(img):
         if args.sigma is not None:
             return noisy_of(img)
-        if args.jpeg_quality is not None:
-            try:
-                return irdu_amd.jpeg_degrade_u8(img, args.jpeg_quality, args.jpeg_subsampling)
-            except ValueError as e:
-                raise SystemExit(f"--jpeg-quality: {e}")
-        if args.bayer is not None:
-            return irdu_amd.demosaic_u8(img, args.bayer, args.demosaic_fill)
-        return img if args.scale is None else irdu_amd.bicubic_degrade_u8(img, args.scale)
+        if protocol is None:
+            return img
+        try:
+            return restore._resized_u8(protocol.who, img, protocol.degrade)
+        except ValueError as e:
+            raise SystemExit(f"{protocol.who}: {e}")
 
     def noisy_of(img):
         noisy = img.astype(np.float32) / 255.0
@@ -304,17 +302,13 @@ def main(argv=None) -> None:
             if truth.shape != out.shape:
                 raise SystemExit(f"--reference: {refs[path]} decodes to {truth.shape}, the restored {path} is {out.shape}")
             scored = out
-            if args.shave:
-                n = args.shave
-                scored, truth = np.ascontiguousarray(out[n:-n, n:-n]), np.ascontiguousarray(truth[n:-n, n:-n])
+            if protocol is not None:
+                scored, truth = np.ascontiguousarray(protocol.shaved(out)), np.ascontiguousarray(protocol.shaved(truth))
             try:
                 psnrs.append(psnr_of(scored, truth))
             except ValueError as e:
                 raise SystemExit(f"{path}: {e}")
-            against = (f"bicubic x{args.scale} shave {args.shave}" if args.scale is not None else
-                       f"jpeg q{args.jpeg_quality} {'4:2:0' if args.jpeg_subsampling else '4:4:4'}"
-                       if args.jpeg_quality is not None else
-                       f"bayer {args.bayer} {args.demosaic_fill} shave {args.shave}" if args.bayer is not None else
+            against = (protocol.label if protocol is not None else
                        f"sigma {args.sigma:g}" if args.reference is None else f"reference {refs[path]}")
             line = f"{path} -> {out_path}  {against}  PSNR{tag} {psnrs[-1]:.4f} dB"
             if args.ssim:
