@@ -46,7 +46,17 @@ one serial pass of training.demosaic_degrade_u8 (numpy) over every picture; grr_
 process.  One JSON line ("bench": "demosaic") with, per case, the times, the algorithmic GB/s (3 bytes read and 3
 written per pixel) and that rate as a share of the copy's.
 
-    python bench_data.py [--paired | --pair-kernel | --bicubic S | --jpeg Q | --demosaic PATTERN] [--steps 60] [--warmup 10] [--images 12] [--side 1200] [--workers 4] [--files 8600]
+With --blur SPEC (gaussian:SIDE:SIGMA, box:SIDE, motion:LENGTH:ANGLE, file:PATH.npy, or random:SIDE for a random
+SIDE x SIDE table) only the synthesis of a deblurring training set's blurred pictures is timed, on the same pictures and
+by the same method: "device" is grr_u8_blur_images on the clean arena (the one launch kernels.u8_blur_images issues),
+device events around each of 20 calls after a warm-up; "host" is training.blur_degrade_u8 (numpy) over the first
+pictures of the set -- as many as keep it to a few hundred tap passes, one picture for a 25 x 25 kernel; the line says
+how many ("host_pictures") and scales their time to the arena by bytes; grr_stream_copy is timed in the same process.
+One JSON line ("bench": "blur") with the times, the algorithmic GB/s (a byte read and a byte written per element), that
+rate as a share of the copy's, and the multiply-adds per second (taps of the table, zeros included, per output byte)
+beside the v_dot4_u32_u8 issue ceiling derived from the clock and the SIMD width, not measured.
+
+    python bench_data.py [--paired | --pair-kernel | --bicubic S | --jpeg Q | --demosaic PATTERN | --blur SPEC] [--steps 60] [--warmup 10] [--images 12] [--side 1200] [--workers 4] [--files 8600]
 """
 from __future__ import annotations
 
@@ -342,6 +352,65 @@ def demosaic(pattern: str, images: int, side: int, rounds: int = 20) -> None:
     print(json.dumps(line), flush=True)
 
 
+def blur(spec: str, images: int, side: int, rounds: int = 20, boundary: str = "wrap") -> None:
+    import irdu_amd
+    irdu_amd.load_native()
+    from irdu_amd import _native, kernels, restore, training
+    dev = torch.device("cuda:0")
+    pics = synthetic_pictures(images, side)
+    stream = torch.cuda.current_stream().cuda_stream
+    if spec.startswith("random:"):
+        n = int(spec.split(":")[1])
+        kernel = training.BlurKernel(np.random.RandomState(5).rand(n, n), spec)
+    else:
+        kernel = training.parse_blur_spec(spec)
+    taps = kernel.kh * kernel.kw
+    pack = restore.pack_images(pics, dev)
+    n = pack.arena.numel()
+    # the library call itself on a preallocated arena and uploaded tables, as the copy below is timed
+    out = torch.empty_like(pack.arena)
+    slot = np.zeros((1, kernels.MAX_BLUR_SIDE, kernels.MAX_BLUR_SIDE), np.int32)
+    slot[0, :kernel.kh, :kernel.kw] = kernel.table
+    weights = torch.from_numpy(slot).to(dev)
+    sizes = torch.tensor([[kernel.kh, kernel.kw]], dtype=torch.int32, device=dev)
+    of = torch.zeros(len(pack), dtype=torch.int32, device=dev)
+    max_h, max_w = max(h for _, h, _ in pack.host_table), max(w for _, _, w in pack.host_table)
+    code = kernels._check_boundary("bench", boundary)
+    ms = device_ms(lambda: _native.call("grr_u8_blur_images", pack.arena.data_ptr(), n, pack.table.data_ptr(), len(pack),
+                                        max_h, max_w, 3, out.data_ptr(), weights.data_ptr(), sizes.data_ptr(), 1,
+                                        of.data_ptr(), code, stream), rounds)
+    assert torch.equal(out, kernels.u8_blur_images(pack, kernel, 0, boundary).arena)
+    # the float4 copy of the same bytes, in the same process
+    a = torch.empty(n // 4, dtype=torch.float32, device=dev)
+    b = torch.empty_like(a)
+    copy = device_ms(lambda: _native.call("grr_stream_copy", b.data_ptr(), a.data_ptr(), n // 4, stream), rounds)
+    host_pictures = max(1, min(images, 200 // taps))
+    t0 = time.perf_counter()
+    for i, pic in enumerate(pics[:host_pictures]):
+        got = training.blur_degrade_u8(pic, kernel, boundary)
+        if i == 0:
+            off, h, w = pack.host_table[0]
+            assert np.array_equal(got.ravel(), out[off:off + h * w * 3].cpu().numpy())      # the same bytes
+    host_s = time.perf_counter() - t0
+    host_arena_s = host_s * n / sum(p.size for p in pics[:host_pictures])
+    med, copy_med = float(np.median(ms)), float(np.median(copy))
+    gbps, copy_gbps = 2 * n / med / 1e6, 8 * (n // 4) / copy_med / 1e6
+    # v_dot4_u32_u8: 4 byte multiply-adds per lane, 32 lanes per SIMD and clock, 4 SIMDs on each of 256 CUs at 2.4 GHz;
+    # a tap takes two of them (low and high weight byte)
+    dot4_macs = 4 * 32 * 4 * 256 * 2.4e9
+    print(json.dumps({"bench": "blur", "spec": kernel.spec, "sides": [kernel.kh, kernel.kw], "boundary": boundary,
+                      "images": images, "rounds": rounds, "tile": list(kernels.BLUR_TILE),
+                      "arena_mb": round(n / 2 ** 20, 1), "device_ms": spread(ms), "device_gbps": round(gbps, 1),
+                      "stream_copy_ms": spread(copy), "stream_copy_gbps": round(copy_gbps, 1),
+                      "share_of_copy_rate": round(gbps / copy_gbps, 3), "time_over_copy": round(med / copy_med, 2),
+                      "host_pictures": host_pictures, "host_numpy_s": round(host_s, 3),
+                      "host_numpy_arena_s_scaled": round(host_arena_s, 2),
+                      "host_over_device": round(host_arena_s * 1e3 / med, 1),
+                      "tera_taps_per_s": round(n * taps / med / 1e9, 2),
+                      "derived_dot4_ceiling_tera_taps_per_s": round(dot4_macs / 2 / 1e12, 1),
+                      "share_of_derived_ceiling": round(n * taps / (med * 1e-3) / (dot4_macs / 2), 3)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     # the DataLoader's workers hold up to 2 batches each in flight when the clock starts: enough timed batches
@@ -368,7 +437,12 @@ def main():
     ap.add_argument("--demosaic", type=str, default=None, metavar="PATTERN", choices=("rggb", "grbg", "gbrg", "bggr"),
                     help="only time the synthesis of the filled Bayer mosaics with this pattern: the device kernel (each "
                          "fill) against numpy on the host")
+    ap.add_argument("--blur", type=str, default=None, metavar="SPEC",
+                    help="only time the synthesis of the blurred pictures with this kernel (a spec of "
+                         "training.parse_blur_spec, or random:SIDE): the device kernel against numpy on the host")
     args = ap.parse_args()
+    if args.blur is not None:
+        return blur(args.blur, args.images, args.side)
     if args.pair_kernel:
         return pair_kernel()
     if args.demosaic is not None:

@@ -205,6 +205,10 @@ SIGNATURES = {
     "grr_u8_demosaic_supported": [I, I, I],
     "grr_u8_demosaic": [P, I, I, I, P, I, I, P],
     "grr_u8_demosaic_images": [P, L, P, I, I, I, P, P, I, P],
+    # 2-D blur by an integer point-spread function (blur_ops.hip)
+    "grr_u8_blur_supported": [I, I, I],
+    "grr_u8_blur": [P, I, I, I, P, P, I, I, I, P],
+    "grr_u8_blur_images": [P, L, P, I, I, I, I, P, P, P, I, P, I, P],
 }
 _RESTYPES = {"grr_version": c_int, "grr_last_error": ctypes.c_char_p, "grr_lnb_workspace_bytes": c_int64,
              "grr_conv1x1_workspace_bytes": c_int64, "grr_wgrad_workspace_bytes": c_int64,

@@ -2810,3 +2810,122 @@ def u8_demosaic_images(pack, patterns, fill="malvar"):
                 _stream(dev))
     return ImagePack(arena, pack.table, tuple(tuple(int(v) for v in row) for row in pack.host_table), 3,
                      tuple(getattr(pack, "kinds", ())))
+
+
+# ---------------------------------------------------------------------------
+# 2-D blur by an integer point-spread function (csrc/blur_ops.hip; include/grr.h has the definition): the degradation
+# of deblurring.  A kernel is an int32 table of odd sides up to 31, non-negative, of sum 65536.
+BLUR_TILE = (16, 64)          # a workgroup's rows and columns of the picture
+BLUR_BOUNDARIES = ("wrap", "replicate", "reflect")        # the index is the code
+MAX_BLUR_SIDE = 31            # GRR_BLUR_MAX_SIDE
+BLUR_ONE = 65536              # GRR_BLUR_ONE
+MAX_BLUR_KERNELS = 16         # grr_u8_blur_images: kernels per call
+MAX_BLUR_IMAGES = 65535       # grr_u8_blur_images: one grid row per image
+
+
+def blur_ok(c: int, h: int, w: int) -> bool:
+    """grr_u8_blur_supported in plain Python (tests/test_blur_abi.py checks the two agree): 1..4 channels, sides
+    >= 1, C H W < 2^31."""
+    return 1 <= c <= 4 and h >= 1 and w >= 1 and c * h * w < (1 << 31)
+
+
+def _check_boundary(name: str, boundary) -> int:
+    """The code of a blur boundary given by name or code; ValueError otherwise."""
+    return _check_code(name, "boundary", BLUR_BOUNDARIES, boundary)
+
+
+def _check_blur_table(name: str, weights) -> np.ndarray:
+    """A blur kernel's weight table as a contiguous int32 [kh, kw] array, the definition's conditions checked on the
+    host: ``weights`` is that table (a 2-D integer array or host tensor) or a record with one as its ``table``
+    (training.BlurKernel).  ValueError otherwise."""
+    w = getattr(weights, "table", weights)
+    if isinstance(w, Tensor):
+        if w.is_cuda:
+            raise ValueError(f"{name}: a blur kernel is a host table; it is checked before it is sent to the device")
+        w = w.numpy()
+    w = np.asarray(w)
+    if w.ndim != 2 or w.dtype.kind not in "iu" or w.size == 0:
+        raise ValueError(f"{name}: a blur kernel is a 2-D integer table, got {w.dtype} {w.shape}")
+    if any(s % 2 == 0 or s > MAX_BLUR_SIDE for s in w.shape):
+        raise ValueError(f"{name}: a blur kernel's sides are odd and at most {MAX_BLUR_SIDE}, got {w.shape}")
+    w = w.astype(np.int64)
+    if w.min() < 0 or int(w.sum()) != BLUR_ONE:
+        raise ValueError(f"{name}: a blur kernel's weights are non-negative and sum to {BLUR_ONE} "
+                         f"(got a minimum of {int(w.min())} and a sum of {int(w.sum())})")
+    return np.ascontiguousarray(w, dtype=np.int32)
+
+
+def u8_blur(img: Tensor, weights, boundary="wrap") -> Tensor:
+    """The uint8 device image H x W x C (or H x W) convolved with a blur kernel in exact integers (include/grr.h).
+    ``weights``: the int32 table (a 2-D host array of odd sides up to 31, non-negative, of sum 65536) or a
+    training.BlurKernel; ``boundary``: "wrap" (circular), "replicate" or "reflect", or the code 0..2.  One launch.  A
+    non-contiguous image is copied first."""
+    name = "u8_blur"
+    table, boundary = _check_blur_table(name, weights), _check_boundary(name, boundary)
+    if isinstance(img, Tensor) and img.dtype != torch.uint8:
+        raise ValueError(f"{name}: the image must be uint8, got {img.dtype}")
+    flat = isinstance(img, Tensor) and img.dim() == 2
+    if flat:
+        img = img[:, :, None]
+    h, w, c = _check_image(name, img)
+    if not blur_ok(c, h, w):
+        raise ValueError(f"{name}: needs 1..4 channels and H W C < 2^31, got {tuple(img.shape)}")
+    img = img.contiguous()
+    out = torch.empty_like(img)
+    wd = torch.from_numpy(table).to(img.device)
+    _launch("u8_blur", img.numel() + out.numel(), "grr_u8_blur", img.data_ptr(), h, w, c, out.data_ptr(),
+            wd.data_ptr(), table.shape[0], table.shape[1], boundary, _stream(img.device))
+    return out[:, :, 0] if flat else out
+
+
+def u8_blur_images(pack, kernels, kernel_of, boundary="wrap"):
+    """u8_blur of every image of a uint8 image pack into a new pack that shares its image table (so the two can form
+    a patch_pair_source), one launch per 65535 images.  ``kernels``: one kernel or a sequence of at most 16 (tables or
+    training.BlurKernel records, checked here); ``kernel_of``: the index into ``kernels`` of every image, one int for
+    all, a sequence of one per image (checked here), or an int32 device tensor of one per image (which the kernel
+    clamps into range, as it does every device table)."""
+    from .restore import ImagePack
+    name = "u8_blur_images"
+    boundary = _check_boundary(name, boundary)
+    if hasattr(kernels, "table") or isinstance(kernels, (np.ndarray, Tensor)):
+        kernels = [kernels]
+    if not 1 <= len(kernels) <= MAX_BLUR_KERNELS:
+        raise ValueError(f"{name}: takes 1..{MAX_BLUR_KERNELS} kernels, got {len(kernels)}")
+    tables = [_check_blur_table(name, k) for k in kernels]
+    n_img, c = _check_pack(name, pack, placed=False)
+    if pack.arena.dtype != torch.uint8:
+        raise ValueError(f"{name}: the arena must be uint8, got {pack.arena.dtype}")
+    shapes = [(int(h), int(w)) for _, h, w in pack.host_table]
+    dev = pack.arena.device
+    if not isinstance(kernel_of, Tensor):       # the host list is checked before anything is asked of the device
+        if isinstance(kernel_of, (int, np.integer)):
+            kernel_of = [kernel_of] * n_img
+        if len(kernel_of) != n_img:
+            raise ValueError(f"{name}: {len(kernel_of)} kernel indices for {n_img} images")
+        for v in kernel_of:
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not 0 <= v < len(tables):
+                raise ValueError(f"{name}: a kernel index is an integer of 0..{len(tables) - 1}, got {v!r}")
+    _check_placed(name, pack)
+    if isinstance(kernel_of, Tensor):
+        if kernel_of.dtype != torch.int32 or tuple(kernel_of.shape) != (n_img,) or kernel_of.device != dev \
+                or not kernel_of.is_contiguous():
+            raise ValueError(f"{name}: a kernel-index tensor is int32 [{n_img}], contiguous and on the arena's device")
+        of = kernel_of
+    else:
+        of = torch.tensor([int(v) for v in kernel_of], dtype=torch.int32).to(dev)
+    slots = np.zeros((len(tables), MAX_BLUR_SIDE, MAX_BLUR_SIDE), np.int32)
+    for slot, t in zip(slots, tables):
+        slot[:t.shape[0], :t.shape[1]] = t
+    weights = torch.from_numpy(slots).to(dev)
+    sizes = torch.tensor([t.shape for t in tables], dtype=torch.int32).to(dev)
+    covered = sum(h * w * c for h, w in shapes) == pack.arena.numel()
+    arena = (torch.empty_like if covered else torch.zeros_like)(pack.arena)      # bytes between images stay 0
+    for at in range(0, n_img, MAX_BLUR_IMAGES):
+        n = min(MAX_BLUR_IMAGES, n_img - at)
+        part = shapes[at:at + n]
+        _launch("u8_blur_images", 2 * sum(h * w * c for h, w in part), "grr_u8_blur_images", pack.arena.data_ptr(),
+                pack.arena.numel(), pack.table.data_ptr() + at * 24, n, max(h for h, _ in part),
+                max(w for _, w in part), c, arena.data_ptr(), weights.data_ptr(), sizes.data_ptr(), len(tables),
+                of.data_ptr() + at * 4, boundary, _stream(dev))
+    return ImagePack(arena, pack.table, tuple(tuple(int(v) for v in row) for row in pack.host_table), c,
+                     tuple(getattr(pack, "kinds", ())))

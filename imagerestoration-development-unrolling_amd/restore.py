@@ -62,6 +62,10 @@ Demosaicking: ``demosaic_u8`` is the Bayer mosaic of a picture (or a raw 1-chann
 filled by the zero, bilinear or Malvar-He-Cutler filter in exact integers (``kernels.u8_demosaic``), and
 ``evaluate_demosaic`` mosaics clean pictures, restores the filled ones and scores them (CPSNR, SSIM).
 
+Deblurring: ``blur_u8`` is the convolution of a picture with an integer point-spread function under a wrap, replicate
+or reflect boundary in exact integers (``kernels.u8_blur``), and ``evaluate_deblur`` blurs clean pictures, adds noise
+where asked, restores and scores them.
+
 Single process: several ranks are ``tiling.tiled_forward``'s business.
 """
 from __future__ import annotations
@@ -682,8 +686,9 @@ def _score_packs(who: str, restored: ImagePack, clean_u8: ImagePack, metrics) ->
 
 class _Protocol(NamedTuple):
     """A degrade-from-clean evaluation protocol: take a clean uint8 picture, crop it, degrade it on the device, restore,
-    shave, score.  The record holds what evaluate_sr, evaluate_car and evaluate_demosaic differ in (_sr_protocol,
-    _car_protocol and _demosaic_protocol build it, parameters checked); _evaluate_degraded is the one loop they share,
+    shave, score.  The record holds what evaluate_sr, evaluate_car, evaluate_demosaic and evaluate_deblur differ in
+    (_sr_protocol, _car_protocol, _demosaic_protocol and _deblur_protocol build it, parameters checked);
+    _evaluate_degraded is the one loop they share,
     and the restore.py command takes its crop, degradation, shave and label from the same record."""
     who: str                # the caller its refusals name
     label: str              # the protocol and its parameters in a few words: the command's "against" text
@@ -900,6 +905,85 @@ def evaluate_demosaic(model: Callable, images, pattern="rggb", fill="malvar", sh
                                                                      tiling_args)
     return _evaluate_degraded(_demosaic_protocol("evaluate_demosaic", pattern, fill, shave), model, images, factor, modes,
                               metrics, device, tile, halo, micro_batch)
+
+
+def _blur_kernel(who: str, kernel):
+    """The training.BlurKernel of a spec; its refusal under the caller's name."""
+    from .training import parse_blur_spec
+    try:
+        return parse_blur_spec(kernel)
+    except ValueError as e:
+        raise ValueError(f"{who}: {e}") from None
+
+
+def blur_u8(a, kernel, boundary="wrap"):
+    """The uint8 picture ``a`` (H x W x C with C of 1..4, or H x W; a numpy array or a tensor, host or device)
+    convolved with a blur kernel on the GPU, in exact integers (kernels.u8_blur; include/grr.h has the definition);
+    the result is of the same kind.  ``kernel``: a spec as training.parse_blur_spec takes it ("gaussian:25:1.6",
+    "motion:15:30", "box:5", "file:psf.npy", a 2-D array or a BlurKernel); ``boundary``: "wrap", "replicate" or
+    "reflect" (or the code 0..2).  training.blur_degrade_u8 gives the same bytes on the CPU."""
+    kernel = _blur_kernel("blur_u8", kernel)                               # before any transfer
+    boundary = kernels._check_boundary("blur_u8", boundary)
+    flat = isinstance(a, (np.ndarray, torch.Tensor)) and a.ndim == 2
+    out = _resized_u8("blur_u8", a[:, :, None] if flat else a, lambda t: kernels.u8_blur(t, kernel, boundary))
+    return out[:, :, 0] if flat else out
+
+
+def _deblur_protocol(who: str, kernel, boundary, noise_sigma, seed, shave) -> _Protocol:
+    """Deblurring: the whole picture blurred by ``kernel`` under ``boundary``, a shave of ``shave``.  With a positive
+    ``noise_sigma`` the model's input is float32: the blurred picture / 255 plus N(0, noise_sigma / 255) noise drawn on
+    the host from one RandomState(seed) stream in picture order, cast to float32 and not quantised."""
+    kernel = _blur_kernel(who, kernel)
+    boundary = kernels._check_boundary(who, boundary)
+    if isinstance(noise_sigma, bool) or not isinstance(noise_sigma, (int, float, np.integer, np.floating)) \
+            or not (np.isfinite(noise_sigma) and noise_sigma >= 0):
+        raise ValueError(f"{who}: noise_sigma is a non-negative number, got {noise_sigma!r}")
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 2 ** 32:
+        raise ValueError(f"{who}: seed is an integer of 0..2^32 - 1, got {seed!r}")
+    shave = _check_shave(who, shave)
+    noise_sigma = float(noise_sigma)
+    rs = np.random.RandomState(seed=int(seed))
+
+    def admit(i, t):
+        if not kernels.blur_ok(t.shape[2], t.shape[0], t.shape[1]):
+            raise ValueError(f"{who}: image {i} is {tuple(t.shape)}; the blur takes 1..4 channels")
+
+    def degrade(clean):
+        blurred = kernels.u8_blur(clean, kernel, boundary)
+        if noise_sigma == 0:
+            return blurred
+        x = blurred.cpu().numpy().astype(np.float32) / np.float32(255.0)
+        x += rs.normal(0, noise_sigma / 255.0, x.shape).astype(np.float32)
+        return torch.from_numpy(x).to(clean.device)
+
+    label = f"blur {kernel.spec} {kernels.BLUR_BOUNDARIES[boundary]}" + \
+        (f" noise {noise_sigma:g}" if noise_sigma else "") + f" shave {shave}"
+    return _Protocol(who, label=label, defined_on="the blur is defined on", admit=admit, crop=lambda h, w: (h, w),
+                     shave=shave, left_after=f"after a shave of {shave}", scored="image {i} after the shave",
+                     degrade=degrade)
+
+
+def evaluate_deblur(model: Callable, images, kernel, boundary="wrap", noise_sigma: float = 0.0, seed: int = 2204,
+                    shave: int = 0, factor: int = 16, ensemble=1, metrics=("psnr", "ssim"), **tiling_args) -> dict:
+    """Score ``model`` on deblurring (the protocol of the Levin / IRCNN / DPIR tables) over clean uint8 H x W x C
+    pictures (numpy arrays or tensors, host or device).  Per picture: the blur by ``kernel`` (a spec as
+    training.parse_blur_spec takes it) under ``boundary`` on the device (kernels.u8_blur), the blurred picture restored
+    as ``restore_image(..., quantise=True)`` does, ``shave`` pixels cut from each side of the restored and the clean
+    picture, and the two scored with the exact-integer kernels.  Returns {metric: (mean, per-image values)} as
+    evaluate_pairs does.  tiling_args: tile, halo, micro_batch, device; ``ensemble`` as in restore_image.
+
+    With ``noise_sigma == 0`` the model's input is the blurred uint8 picture, and with ``shave=0`` the result is
+    evaluate_pairs(model, blurred, clean) bit for bit.  With ``noise_sigma > 0`` the input is float32: blurred / 255
+    plus RandomState(seed).normal(0, noise_sigma / 255, shape), drawn on the host in picture order, cast to float32
+    and not quantised -- the tables' protocol.
+
+    Everything is checked before any launch: the kernel spec first, then the boundary, the noise, the seed, the
+    shave, uint8 pictures of 1..4 channels, a picture smaller than the shave leaves, and what the metrics need of the
+    shaved picture (SSIM: both sides at least 11; PSNR-B: at least 16; the Y-channel metrics: 3 channels)."""
+    modes, metrics, device, tile, halo, micro_batch = _evaluate_args("evaluate_deblur", model, ensemble, metrics,
+                                                                     tiling_args)
+    return _evaluate_degraded(_deblur_protocol("evaluate_deblur", kernel, boundary, noise_sigma, seed, shave), model,
+                              images, factor, modes, metrics, device, tile, halo, micro_batch)
 
 
 def evaluate_pairs(model: Callable, inputs, targets, factor: int = 16, across_images: bool = False, ensemble=1,

@@ -43,6 +43,10 @@ csrc/jpeg_ops.hip makes the degraded arena), and ``validate_car`` scores it on a
 colour filter array with its missing channels filled by a fixed integer filter (``demosaic_degrade_u8`` on the host;
 on the device csrc/demosaic_ops.hip makes the filled arena), and ``validate_demosaic`` scores it on a
 ``TestImagesCSV`` set with a ``bayer`` key through restore.evaluate_demosaic.
+``GaussianMotionDeblurring`` is the fourth, for deblurring: the input is the picture convolved with an integer
+point-spread function -- Gaussian, box, motion or from a file (``parse_blur_spec``, ``blur_degrade_u8`` on the host; on
+the device csrc/blur_ops.hip makes the blurred arena) -- and ``validate_deblur`` scores it on a ``TestImagesCSV`` set
+with a ``blur`` key through restore.evaluate_deblur.
 """
 from __future__ import annotations
 
@@ -792,6 +796,258 @@ class BayerDemosaicking(_DegradedFromClean):
         return ("bayer", tuple(self.patterns[i] for i in used), self.fill)
 
 
+BLUR_BOUNDARIES = ("wrap", "replicate", "reflect")      # kernels.BLUR_BOUNDARIES: the index is the code
+MAX_BLUR_SIDE = 31            # GRR_BLUR_MAX_SIDE
+BLUR_ONE = 65536              # GRR_BLUR_ONE
+MAX_BLUR_KERNELS = 16         # kernels.MAX_BLUR_KERNELS: distinct kernels of one degraded arena
+
+
+def quantise_blur_kernel(k) -> np.ndarray:
+    """The int32 weight table of a non-negative real kernel ``k`` of positive sum (include/grr.h has the rule), in
+    float64: q = k / sum(k) * 65536 with sum(k) the correctly rounded sum (math.fsum, so it does not depend on an
+    order of summation), W = floor(q), and the 65536 - sum(W) units left go one each to the taps of largest
+    fractional part, ties to the lower flat index.  An integer table that already sums to 65536 passes through
+    unchanged."""
+    who = "quantise_blur_kernel"
+    k = np.asarray(k)
+    if k.ndim != 2 or k.size == 0 or k.dtype.kind not in "iuf":
+        raise ValueError(f"{who}: a blur kernel is a 2-D array of real numbers, got {k.dtype} {k.shape}")
+    if any(s % 2 == 0 or s > MAX_BLUR_SIDE for s in k.shape):
+        raise ValueError(f"{who}: a blur kernel's sides are odd and at most {MAX_BLUR_SIDE}, got {k.shape}")
+    if k.dtype.kind in "iu" and k.min() >= 0 and int(k.astype(np.int64).sum()) == BLUR_ONE:
+        return np.ascontiguousarray(k, dtype=np.int32)
+    k = k.astype(np.float64)
+    total = math.fsum(k.ravel().tolist())
+    if not np.all(np.isfinite(k)) or k.min() < 0 or not total > 0:
+        raise ValueError(f"{who}: a blur kernel is finite and non-negative with a positive sum")
+    q = k / total * float(BLUR_ONE)
+    w = np.floor(q)
+    left = BLUR_ONE - int(w.sum())
+    order = np.argsort(-(q - w).ravel(), kind="stable")      # largest fraction first, ties in flat order
+    w = w.astype(np.int64).ravel()
+    if not 0 <= left <= w.size:      # rounding of q cannot move the sum further than one unit per tap
+        raise ValueError(f"{who}: the kernel cannot be quantised ({left} units left for {w.size} taps)")
+    w[order[:left]] += 1
+    return np.ascontiguousarray(w.reshape(k.shape), dtype=np.int32)
+
+
+class BlurKernel:
+    """A blur kernel as the device takes it: ``table`` (int32 [kh, kw], read-only; odd sides up to 31, non-negative,
+    of sum 65536), ``kh``, ``kw`` and ``spec``, the string it was built from (for an array, its sides and a digest of
+    the table).  Immutable and hashable: equal kernels have equal tables."""
+    __slots__ = ("table", "kh", "kw", "spec", "_key")
+
+    def __init__(self, weights, spec: Optional[str] = None):
+        table = quantise_blur_kernel(weights).copy()
+        table.setflags(write=False)
+        key = (table.shape, table.tobytes())
+        if spec is None:
+            import hashlib
+            spec = f"array:{table.shape[0]}x{table.shape[1]}:{hashlib.sha1(key[1]).hexdigest()[:12]}"
+        for name, v in (("table", table), ("kh", int(table.shape[0])), ("kw", int(table.shape[1])), ("spec", str(spec)),
+                        ("_key", key)):
+            object.__setattr__(self, name, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("a BlurKernel is immutable")
+
+    def __eq__(self, other):
+        return isinstance(other, BlurKernel) and self._key == other._key
+
+    def __hash__(self):
+        return hash(self._key)
+
+    def __repr__(self):
+        return f"BlurKernel({self.spec!r}, {self.kh} x {self.kw})"
+
+
+def _blur_side(who: str, what: str, v, odd: bool = True) -> int:
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not 1 <= v <= MAX_BLUR_SIDE \
+            or (odd and v % 2 == 0):
+        raise ValueError(f"{who}: {what} is an{' odd' if odd else ''} integer of 1..{MAX_BLUR_SIDE}, got {v!r}")
+    return int(v)
+
+
+def gaussian_kernel(side: int, sigma: float) -> BlurKernel:
+    """``gaussian:SIDE:SIGMA``: exp(-(dy^2 + dx^2) / (2 sigma^2)) on a SIDE x SIDE grid about its centre, quantised."""
+    side = _blur_side("gaussian_kernel", "the side", side)
+    if isinstance(sigma, bool) or not isinstance(sigma, (int, float, np.integer, np.floating)) \
+            or not (math.isfinite(sigma) and sigma > 0):
+        raise ValueError(f"gaussian_kernel: sigma is a positive number, got {sigma!r}")
+    d = np.arange(side, dtype=np.float64) - (side - 1) / 2
+    return BlurKernel(np.exp(-(d[:, None] ** 2 + d[None, :] ** 2) / (2.0 * float(sigma) ** 2)),
+                      f"gaussian:{side}:{float(sigma):g}")
+
+
+def box_kernel(side: int) -> BlurKernel:
+    """``box:SIDE``: the mean over a SIDE x SIDE window, quantised."""
+    side = _blur_side("box_kernel", "the side", side)
+    return BlurKernel(np.ones((side, side)), f"box:{side}")
+
+
+def motion_kernel(length: int, angle: float) -> BlurKernel:
+    """``motion:LENGTH:ANGLE``: a straight line of LENGTH pixels (an integer of 1..31) through the centre of an s x s
+    grid, s = LENGTH if that is odd, else LENGTH + 1, at ANGLE degrees counter-clockwise with y pointing down.
+    N = 8 LENGTH + 1 points (one for LENGTH 1) at t evenly spaced on [-(LENGTH - 1) / 2, (LENGTH - 1) / 2] are placed
+    at (x, y) = (c + t cos a, c - t sin a), c = (s - 1) / 2, and each adds its bilinear weights to its four
+    neighbouring taps; a neighbour outside the grid gets nothing.  The sum is quantised.
+
+    This is this project's definition, not MATLAB's ``fspecial('motion')``: the two differ in how the line is sampled
+    and weighted.  Two details make it reproducible: the cosine and sine of a multiple of 90 degrees are exact (0 or
+    +-1), and every tap is the correctly rounded sum (math.fsum) of its contributions, so a kernel does not depend on
+    the order of the points: the kernels at 0 and at 90 degrees are transposes of each other."""
+    who = "motion_kernel"
+    length = _blur_side(who, "the length", length, odd=False)
+    if isinstance(angle, bool) or not isinstance(angle, (int, float, np.integer, np.floating)) or not math.isfinite(angle):
+        raise ValueError(f"{who}: the angle is a finite number of degrees, got {angle!r}")
+    s = length if length % 2 else length + 1
+    c = (s - 1) // 2
+    quarter = (float(angle) % 360.0) / 90.0
+    if quarter == int(quarter):
+        cos_a, sin_a = ((1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0))[int(quarter)]
+    else:
+        cos_a, sin_a = math.cos(math.radians(float(angle))), math.sin(math.radians(float(angle)))
+    # t_i = (i - 4 LENGTH) (LENGTH - 1) / (8 LENGTH): exactly antisymmetric about the middle point
+    ts = [0.0] if length == 1 else [(i - 4 * length) * (length - 1) / (8.0 * length) for i in range(8 * length + 1)]
+    parts = [[[] for _ in range(s)] for _ in range(s)]
+    for t in ts:
+        x, y = c + t * cos_a, c - t * sin_a
+        x0, y0 = math.floor(x), math.floor(y)
+        fx, fy = x - x0, y - y0
+        for yy, wy in ((y0, 1.0 - fy), (y0 + 1, fy)):
+            for xx, wx in ((x0, 1.0 - fx), (x0 + 1, fx)):
+                if 0 <= yy < s and 0 <= xx < s:
+                    parts[yy][xx].append(wy * wx)
+    k = np.array([[math.fsum(p) for p in row] for row in parts], dtype=np.float64)
+    return BlurKernel(k, f"motion:{length}:{float(angle):g}")
+
+
+def parse_blur_spec(spec) -> BlurKernel:
+    """The kernel of a spec: a BlurKernel (returned as it is), a 2-D array (quantised), or one of the strings
+    ``gaussian:SIDE:SIGMA``, ``box:SIDE``, ``motion:LENGTH:ANGLE`` and ``file:PATH.npy`` (a 2-D float or integer
+    array with odd sides of at most 31).  ValueError for anything else."""
+    who = "parse_blur_spec"
+    if isinstance(spec, BlurKernel):
+        return spec
+    if isinstance(spec, np.ndarray):
+        return BlurKernel(spec)
+    if not isinstance(spec, str):
+        raise ValueError(f"{who}: a blur spec is a string, a 2-D array or a BlurKernel, got {type(spec).__name__}")
+    name, _, rest = spec.partition(":")
+    if name == "file":
+        if not rest.endswith(".npy"):
+            raise ValueError(f"{who}: file:PATH.npy names a .npy file, got {spec!r}")
+        try:
+            k = np.load(rest, allow_pickle=False)
+        except (OSError, ValueError) as e:
+            raise ValueError(f"{who}: {spec!r} cannot be read: {e}") from None
+        return BlurKernel(k, spec)
+    forms = {"gaussian": (gaussian_kernel, (int, float)), "box": (box_kernel, (int,)), "motion": (motion_kernel, (int, float))}
+    if name not in forms:
+        raise ValueError(f"{who}: a blur spec is gaussian:SIDE:SIGMA, box:SIDE, motion:LENGTH:ANGLE or file:PATH.npy, "
+                         f"got {spec!r}")
+    build, types = forms[name]
+    fields = rest.split(":") if rest else []
+    if len(fields) != len(types):
+        raise ValueError(f"{who}: {name} takes {len(types)} field(s) after its name, got {spec!r}")
+    try:
+        values = [t(f) for t, f in zip(types, fields)]
+    except ValueError:
+        raise ValueError(f"{who}: the fields of {spec!r} are not numbers of the kinds {name} takes") from None
+    return build(*values)
+
+
+def _blur_index(t: np.ndarray, n: int, mode: int) -> np.ndarray:
+    """b(t, n) of include/grr.h for any integers t: 0 wrap, 1 replicate, 2 reflect without the edge sample."""
+    if mode == 0:
+        return t % n
+    if mode == 1:
+        return np.clip(t, 0, n - 1)
+    if n == 1:
+        return np.zeros_like(t)
+    m = t % (2 * (n - 1))
+    return np.where(m < n, m, 2 * (n - 1) - m)
+
+
+def blur_degrade_u8(a: np.ndarray, kernel, boundary="wrap") -> np.ndarray:
+    """The uint8 picture ``a`` (H x W x C with C of 1..4, or H x W) convolved with a blur kernel on the CPU, in the
+    integers of include/grr.h.  ``kernel``: a spec as parse_blur_spec takes it; ``boundary``: "wrap", "replicate",
+    "reflect" or the code 0..2.  The same bytes as kernels.u8_blur, bit for bit: it serves the host DataLoader path
+    and users without a GPU.  One pass over the picture per non-zero tap: seconds for a 25 x 25 kernel."""
+    who = "blur_degrade_u8"
+    kernel = parse_blur_spec(kernel)
+    mode = _bayer_code(who, "boundary", BLUR_BOUNDARIES, boundary)
+    a = np.asarray(a)
+    flat = a.ndim == 2
+    a = a[:, :, None] if flat else a
+    if a.dtype != np.uint8 or a.ndim != 3 or not 1 <= a.shape[2] <= 4 or 0 in a.shape:
+        raise ValueError(f"{who}: expected a uint8 H x W x C (C of 1..4) or H x W picture, got {a.dtype} {a.shape}")
+    h, w = a.shape[:2]
+    kh, kw, table = kernel.kh, kernel.kw, kernel.table
+    rows = _blur_index(np.arange(-(kh // 2), h + kh // 2), h, mode)
+    cols = _blur_index(np.arange(-(kw // 2), w + kw // 2), w, mode)
+    p = a[rows][:, cols].astype(np.int32)              # the picture with its frame: p[r, c] is the sample at (r - kh/2, c - kw/2)
+    acc = np.full(a.shape, 32768, np.int32)            # at most 32768 + 255 * 65536 < 2^31
+    for i, j in zip(*np.nonzero(table)):
+        acc += int(table[i, j]) * p[kh - 1 - i:kh - 1 - i + h, kw - 1 - j:kw - 1 - j + w]
+    out = (acc >> 16).astype(np.uint8)
+    return out[:, :, 0] if flat else out
+
+
+class GaussianMotionDeblurring(_DegradedFromClean):
+    """Deblurring pairs synthesised from clean files under ImageSuperResolution's csv, crop and patch plan and draws:
+    the input of a sample is the same patch of the whole picture blurred (blur_degrade_u8), the target the clean
+    patch.  ``kernel``: one spec for every file (parse_blur_spec: "gaussian:25:1.6", "motion:15:30", "box:5",
+    "file:psf.npy", an array or a BlurKernel), or ``[specs, probabilities]`` with at most 16 specs; the kernel of file
+    i is then drawn once, in file order, from RandomState(seed), so it is a function of (seed, file) alone and is
+    fixed for the run (``kernels`` lists the BlurKernels drawn).  ``boundary``: "wrap" (the circular convolution of
+    the deblurring tables, default), "replicate" or "reflect"; it acts on the whole picture, before a patch is cut.
+    ``dist_mode`` defaults to "none"; the parent's additive modes put their noise on top of the blurred patch, which
+    is the blur-plus-noise setting of the tables.  A DevicePatchLoader decodes only the clean files and makes the
+    blurred arena on the GPU (kernels.u8_blur_images)."""
+
+    def __init__(self, csv_path, kernel, boundary="wrap", dist_mode="none", lambda_noise=None, use_data_aug=False,
+                 patch_size=(64, 64), max_num_patchs=100000, root_folder="", logger=None, device=None, seed=2204,
+                 n_channels=3):
+        who = "GaussianMotionDeblurring"
+        if isinstance(kernel, (list, tuple)):
+            if len(kernel) != 2 or isinstance(kernel[0], (str, np.ndarray, BlurKernel)) \
+                    or not 1 <= len(kernel[0]) <= MAX_BLUR_KERNELS or len(kernel[0]) != len(kernel[1]):
+                raise ValueError(f"{who}: kernel is one spec or [specs, probabilities] with 1..{MAX_BLUR_KERNELS} specs "
+                                 f"and as many probabilities, got {kernel!r}")
+            self.kernel_choices, self.kernel_p = [parse_blur_spec(k) for k in kernel[0]], list(kernel[1])
+        else:
+            self.kernel_choices, self.kernel_p = [parse_blur_spec(kernel)], None
+        if not (isinstance(boundary, str) and boundary in BLUR_BOUNDARIES):
+            raise ValueError(f"{who}: boundary is one of {BLUR_BOUNDARIES}, got {boundary!r}")
+        if n_channels not in (1, 3):
+            raise ValueError(f"{who}: pictures are decoded to 1 or 3 channels, got n_channels {n_channels}")
+        self.kernel, self.boundary = kernel, boundary
+        super().__init__(csv_path, dist_mode, lambda_noise, use_data_aug=use_data_aug, patch_size=patch_size,
+                         max_num_patchs=max_num_patchs, root_folder=root_folder, logger=logger, device=device,
+                         seed=seed, n_channels=n_channels)
+
+    def create_all_images(self):
+        super().create_all_images()
+        n = len(self.paths)
+        if self.kernel_p is not None:
+            drawn = np.random.RandomState(self.seed).choice(len(self.kernel_choices), p=self.kernel_p, size=n)
+            self.kernel_index = [int(k) for k in drawn]
+        else:
+            self.kernel_index = [0] * n
+        self.kernels = [self.kernel_choices[k] for k in self.kernel_index]
+
+    def degrade_host(self, img, clean):
+        return blur_degrade_u8(clean, self.kernels[img], self.boundary)
+
+    def degrade_pack(self, pack, used):
+        from . import kernels
+        return kernels.u8_blur_images(pack, self.kernel_choices, [self.kernel_index[i] for i in used], self.boundary)
+
+    def synthetic_key(self, used):
+        return ("blur", tuple(self.kernels[i] for i in used), self.boundary)
+
+
 class DevicePatchLoader:
     """Batches of an ImageSuperResolution dataset made on the device: yields (noisy, clean) float32
     [B, C, h, w], planar (``channels_first``), in place of a DataLoader.  On first use (or in ``prepare``) every file
@@ -820,7 +1076,7 @@ class DevicePatchLoader:
     goes the same way with kernels.u8_jpeg_images at each file's quality: the switch is the datasets' common base
     class, whose ``degrade_pack`` makes the arena and whose ``synthetic_key`` tells one degradation from another in a
     shared store.  A BayerDemosaicking dataset is a third of the kind (kernels.u8_demosaic_images, each file's
-    pattern)."""
+    pattern), a GaussianMotionDeblurring dataset a fourth (kernels.u8_blur_images, each file's kernel)."""
     channels_first = True
     CHUNK_BYTES = 256 << 20      # decoded pictures staged on the host per transfer
 
@@ -954,7 +1210,7 @@ class DevicePatchLoader:
 
 DATASETS = {c.__name__: c for c in (AddictiveGaussianNoiseImagePair, SyntheticNoisyPatches, ImageSuperResolution,
                                     PairedImageRestoration, BicubicSuperResolution, JpegArtifactRemoval,
-                                    BayerDemosaicking)}
+                                    BayerDemosaicking, GaussianMotionDeblurring)}
 
 
 # ---------------------------------------------------------------------------
@@ -1190,6 +1446,33 @@ def validate_demosaic(model: nn.Module, images, bayer="rggb", fill="malvar", sha
                               metric, pattern=bayer, fill=fill, shave=shave, factor=factor, **tiling_args)
 
 
+VAL_DEBLUR_METRICS = ("psnr", "psnr_y", "ssim")
+
+
+def validate_deblur(model: nn.Module, images, blur, boundary="wrap", noise_sigma: float = 0.0, seed: int = 2204,
+                    shave: int = 0, factor: int = 16, device=None, metric: str = "psnr", **tiling_args) -> float:
+    """Mean score of ``model`` on deblurring over clean test pictures (``images[i]``: uint8 H x W x C, or float32 in
+    [0, 1] on the uint8 grid as TestImagesCSV yields them): restore.evaluate_deblur on this rank's share -- blur with
+    the kernel spec ``blur`` under ``boundary`` on the device, add N(0, noise_sigma / 255) noise where ``noise_sigma``
+    is positive (drawn on the host from RandomState(seed), in the order of this rank's pictures), restore, cut
+    ``shave`` pixels from each side, score against the clean picture.  ``metric``: "psnr" (default), "psnr_y" or
+    "ssim".  tiling_args: tile, halo, micro_batch, ensemble.
+
+    Several ranks: sharded and all-reduced as validate_pairs does."""
+    from . import restore
+    return _validate_degraded("validate_deblur", VAL_DEBLUR_METRICS, restore.evaluate_deblur, model, images, device,
+                              metric, kernel=blur, boundary=boundary, noise_sigma=noise_sigma, seed=seed, shave=shave,
+                              factor=factor, **tiling_args)
+
+
+def _val_blur_spec(v) -> str:
+    """``datasets.val.blur``: a kernel spec string, parsed once here so that a bad one is refused with the config."""
+    if not isinstance(v, str):
+        raise ValueError(f"datasets.val.blur is a kernel spec string such as 'gaussian:25:1.6', got {v!r}")
+    parse_blur_spec(v)
+    return v
+
+
 class _ValProtocol(NamedTuple):
     """A row of _VAL_PROTOCOLS: how a ``datasets.val`` section selects a validator, and which of its keys the
     validator gets (beside factor, tile, halo, micro_batch and metric, which every row has)."""
@@ -1200,6 +1483,7 @@ class _ValProtocol(NamedTuple):
     choices: dict                   # its string keys, the selecting one included, with their allowed values
     metrics: Tuple[str, ...]
     validator: Callable
+    float_keys: Tuple[str, ...] = ()    # the row's own optional float keys
 
 
 _VAL_PROTOCOLS = (      # in order of precedence; a section that selects no row is the noise protocol, validate's
@@ -1207,6 +1491,8 @@ _VAL_PROTOCOLS = (      # in order of precedence; a section that selects no row 
     _ValProtocol("bayer", TestImagesCSV, str, ("shave",), {"bayer": BAYER_PATTERNS, "fill": BAYER_FILLS},
                  VAL_DEMOSAIC_METRICS, validate_demosaic),
     _ValProtocol("scale", TestImagesCSV, int, ("shave",), {}, VAL_SR_METRICS, validate_sr),
+    _ValProtocol("blur", TestImagesCSV, _val_blur_spec, ("shave",), {"boundary": BLUR_BOUNDARIES}, VAL_DEBLUR_METRICS,
+                 validate_deblur, ("noise_sigma",)),
     _ValProtocol(None, TestPairsCSV, None, (), {}, VAL_PAIR_METRICS, validate_pairs),
 )
 
@@ -1229,7 +1515,9 @@ def create_val_dataset(conf: dict):
     {type, dataset_args, jpeg_quality, subsampling, factor, tile, halo, micro_batch, metric}, validate_car's
     arguments, no sigma.  TestImagesCSV with a ``bayer`` key (a pattern name) is demosaicking:
     {type, dataset_args, bayer, fill, shave, factor, tile, halo, micro_batch, metric}, validate_demosaic's arguments,
-    no sigma."""
+    no sigma.  TestImagesCSV with a ``blur`` key (a kernel spec string) is deblurring:
+    {type, dataset_args, blur, boundary, noise_sigma, shave, factor, tile, halo, micro_batch, metric},
+    validate_deblur's arguments; the noise on the blurred picture is ``noise_sigma``, not ``sigma``."""
     vconf = conf.get("datasets", {}).get("val")
     if not vconf:
         return None, {}
@@ -1243,6 +1531,7 @@ def create_val_dataset(conf: dict):
             if vconf.get(k) is not None and vconf[k] not in allowed:
                 raise ValueError(f"datasets.val.{k} is one of {allowed}, got {vconf[k]!r}")
         args = {k: int(vconf[k]) for k in ("tile", "halo", "micro_batch") + p.int_keys if vconf.get(k) is not None}
+        args.update({k: float(vconf[k]) for k in p.float_keys if vconf.get(k) is not None})
         args.update({k: str(vconf[k]) for k in p.choices if k != p.key and vconf.get(k) is not None})
         if vconf.get("metric") is not None:
             if vconf["metric"] not in p.metrics:
@@ -1325,7 +1614,8 @@ class TrainStage:
             # batches made on the device from a packed arena; dataloader_args' num_workers is ignored
             if not isinstance(self.dataset, ImageSuperResolution):
                 raise ValueError(f"training stage {index}: device_resident needs type ImageSuperResolution, "
-                                 "PairedImageRestoration, BicubicSuperResolution, JpegArtifactRemoval or BayerDemosaicking, got "
+                                 "PairedImageRestoration, BicubicSuperResolution, JpegArtifactRemoval, BayerDemosaicking or "
+                                 "GaussianMotionDeblurring, got "
                                  f"{ds_conf['type']}")
             self.loader = DevicePatchLoader(self.dataset, self.sampler, self.batch_size, self.drop_last,
                                             shared=shared)

@@ -1101,6 +1101,48 @@ grr_status grr_u8_demosaic(const uint8_t* src, int H, int W, int src_c, uint8_t*
 grr_status grr_u8_demosaic_images(const uint8_t* arena, int64_t elems, const int64_t* table, int n_img, int max_h,
                                   int max_w, uint8_t* dst_arena, const int32_t* patterns, int fill, void* stream);
 
+/* ---- 2-D blur by an integer point-spread function (csrc/blur_ops.hip): the degradation of deblurring.  No floating
+ * point appears in the definition.
+ *
+ * Kernel: an int32 weight table W[kh][kw], row-major; kh and kw odd, in 1..GRR_BLUR_MAX_SIDE; every W >= 0; the sum of
+ *   W exactly GRR_BLUR_ONE.
+ * Output: for a uint8 H x W x C picture, C in 1..4,
+ *     out[y,x,c] = (32768 + sum_{i<kh, j<kw} W[i][j] * src[b(y + kh/2 - i, H), b(x + kw/2 - j, W), c]) >> 16
+ *   a true convolution: the kernel is flipped, which matters for a motion kernel.  The sum is at most
+ *   255 * 65536 < 2^24: int32 is exact and a valid table needs no clamp.
+ * Boundary b(t, n): wrap (0) t mod n (non-negative), the circular convolution of the deblurring tables; replicate (1)
+ *   t clamped into [0, n - 1]; reflect (2) about the edge sample without repeating it, as the demosaic border above:
+ *   for n >= 2, m = t mod 2(n - 1) (non-negative), then m < n ? m : 2(n - 1) - m; for n = 1 every index maps to 0.
+ *   Each holds for any t, so for a side smaller than the kernel's radius too (several folds).
+ * Quantiser: a table is made from a non-negative real kernel k of positive sum by one rule, in float64 on the host
+ *   (training.quantise_blur_kernel): q = k / sum(k) * 65536, W = floor(q), and the 65536 - sum(W) units left are
+ *   handed out one each to the taps of largest fractional part q - W, ties to the lower flat index.  A table that
+ *   already sums to 65536 passes through unchanged.
+ *
+ * src and dst: HWC uint8 at any byte address, distinct buffers; element offsets are 64-bit.  Each output byte is
+ * written once; no atomics; one launch. */
+#define GRR_BLUR_MAX_SIDE 31
+#define GRR_BLUR_ONE 65536
+
+/* 1 where grr_u8_blur takes the image: C in 1..4, H, W >= 1, C H W < 2^31. */
+int grr_u8_blur_supported(int C, int H, int W);
+/* One image.  weights: int32 [kh * kw] on the device.  GRR_ERR_INVALID_ARG for an even or out-of-range side or a
+ * boundary outside 0..2, before any launch; GRR_ERR_UNSUPPORTED where the query says 0. */
+grr_status grr_u8_blur(const uint8_t* src, int H, int W, int C, uint8_t* dst, const int32_t* weights, int kh, int kw,
+                       int boundary, void* stream);
+/* Every image of an arena of C-channel pictures into the same place of dst_arena (both of elems elements), one launch:
+ * image i is row i of table (int64 [n_img, 3] on the device, 8-byte aligned, rows (element offset, H, W)), blurred by
+ * kernel kernel_of[i] (int32 [n_img] on the device).  weights: int32 [n_kernels, 31 * 31] on the device, each kernel
+ * row-major in the top-left kh x kw of its 31 x 31 slot; sizes: int32 [n_kernels, 2] on the device, rows (kh, kw).
+ * max_h, max_w bound every image's sides.  Device data is clamped -- offsets into the arena, sides into
+ * [1, max_h] x [1, max_w], kernel indices into [0, n_kernels), kernel sides into 1..31 and made odd, weights into
+ * [0, 65536], every element index read into [0, elems), a write at or past elems dropped, the result min-ed to 255 --
+ * so a bad table gives wrong pixels, never an access outside the two arenas; the caller checks its host copies.
+ * n_kernels <= 16 and n_img <= 65535 (one grid row per image), else GRR_ERR_UNSUPPORTED. */
+grr_status grr_u8_blur_images(const uint8_t* arena, int64_t elems, const int64_t* table, int n_img, int max_h, int max_w,
+                              int C, uint8_t* dst_arena, const int32_t* weights, const int32_t* sizes, int n_kernels,
+                              const int32_t* kernel_of, int boundary, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

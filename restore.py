@@ -5,7 +5,8 @@
             | --scale S [--shave N] [--ssim] [--y-channel] | --upscale S
             | --jpeg-quality Q [--jpeg-subsampling 444|420] [--psnrb] [--ssim] [--y-channel]
             | --bayer PATTERN [--demosaic-fill FILL] [--shave N] [--ssim] [--y-channel]
-            | --raw PATTERN [--demosaic-fill FILL]]
+            | --raw PATTERN [--demosaic-fill FILL]
+            | --blur SPEC [--blur-boundary B] [--blur-noise S] [--shave N] [--ssim] [--y-channel]]
            [--tile T --halo H --factor F] [--batch-images]
            [--self-ensemble | --ensemble-modes 0,1,4,5]
 
@@ -52,6 +53,13 @@ is restored and scored against the input after --shave N border pixels (default 
 the three channels is the CPSNR of the demosaicking tables; --ssim and --y-channel apply as above.  With --raw PATTERN
 the inputs are 1-channel mosaic files as a sensor gives them: each is filled to RGB the same way, restored and written
 as RGB; nothing is scored.  Both need a 3-channel model and work with --batch-images and the ensemble options.
+With --blur SPEC (gaussian:SIDE:SIGMA, box:SIDE, motion:LENGTH:ANGLE or file:PATH.npy; not with the other scored modes)
+the inputs are clean files and the deblurring protocol runs on each: it is convolved with the kernel on the GPU in exact
+integers (``irdu_amd.blur_u8``; --blur-boundary wrap, the default and the circular convolution of the deblurring tables,
+replicate or reflect), with --blur-noise S noise of N(0, S/255) is added to the blurred picture (drawn on the host from
+RandomState(--seed) in file order; the model's input is then float32 and is not quantised), the result is restored and
+scored against the input after --shave N border pixels (default 0) are cut from both.  --ssim and --y-channel apply as
+above; it works with --batch-images and the ensemble options.
 """
 import argparse
 import os
@@ -61,6 +69,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 PATTERNS = ("rggb", "grbg", "gbrg", "bggr")     # irdu_amd.kernels.DEMOSAIC_PATTERNS
 FILLS = ("zero", "bilinear", "malvar")          # irdu_amd.kernels.DEMOSAIC_FILLS
+BOUNDARIES = ("wrap", "replicate", "reflect")   # irdu_amd.kernels.BLUR_BOUNDARIES
 EXTENSIONS = (".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff", ".ppm", ".pgm", ".webp")
 
 
@@ -129,6 +138,13 @@ def parse_args(argv=None):
                              "GPU, restore, report PSNR (CPSNR) against the input")
     scored.add_argument("--raw", type=str, default=None, metavar="PATTERN", choices=PATTERNS,
                         help="inputs are 1-channel Bayer mosaics with this pattern: fill to RGB, restore, write")
+    scored.add_argument("--blur", type=str, default=None, metavar="SPEC",
+                        help="inputs are clean: blur with this kernel (gaussian:SIDE:SIGMA, box:SIDE, motion:LENGTH:ANGLE, "
+                             "file:PATH.npy) on the GPU, restore, report PSNR against the input")
+    ap.add_argument("--blur-boundary", type=str, default=None, choices=BOUNDARIES,
+                    help="with --blur: how the picture continues beyond its sides (default wrap)")
+    ap.add_argument("--blur-noise", type=float, default=None, metavar="S",
+                    help="with --blur: add N(0, S/255) noise to the blurred picture (default 0: none)")
     ap.add_argument("--demosaic-fill", type=str, default=None, choices=FILLS,
                     help="with --bayer or --raw: how the missing channels are filled before the model (default malvar)")
     ap.add_argument("--jpeg-subsampling", type=str, default=None, choices=("444", "420"),
@@ -136,14 +152,15 @@ def parse_args(argv=None):
     ap.add_argument("--psnrb", action="store_true",
                     help="with --jpeg-quality or --reference: report PSNR-B beside the PSNR")
     ap.add_argument("--shave", type=int, default=None, metavar="N",
-                    help="with --scale or --bayer: border pixels cut from both pictures before scoring (default: S with "
-                         "--scale, 0 with --bayer)")
+                    help="with --scale, --bayer or --blur: border pixels cut from both pictures before scoring (default: S "
+                         "with --scale, 0 with --bayer and --blur)")
     ap.add_argument("--seed", type=int, default=2204)
     ap.add_argument("--ssim", action="store_true",
-                    help="with --sigma, --reference, --scale, --jpeg-quality or --bayer: report the SSIM beside the PSNR")
+                    help="with --sigma, --reference, --scale, --jpeg-quality, --bayer or --blur: report the SSIM beside the "
+                         "PSNR")
     ap.add_argument("--y-channel", action="store_true",
-                    help="with --sigma, --reference, --scale, --jpeg-quality or --bayer: score on the Y channel of YCbCr "
-                         "(BT.601 luma of RGB images): PSNR-Y, and with --ssim SSIM-Y, in place of the RGB values")
+                    help="with --sigma, --reference, --scale, --jpeg-quality, --bayer or --blur: score on the Y channel of "
+                         "YCbCr (BT.601 luma of RGB images): PSNR-Y, and with --ssim SSIM-Y, in place of the RGB values")
     ap.add_argument("--tile", type=int, default=None)
     ap.add_argument("--halo", type=int, default=None)
     ap.add_argument("--factor", type=int, default=16)
@@ -156,11 +173,11 @@ def parse_args(argv=None):
                        help="average over these modes of 0..7 only, ascending (e.g. 0,1,4,5)")
     args = ap.parse_args(argv)
     args.scored = args.sigma is not None or args.reference is not None or args.scale is not None \
-        or args.jpeg_quality is not None or args.bayer is not None
+        or args.jpeg_quality is not None or args.bayer is not None or args.blur is not None
     if args.ssim and not args.scored:
-        ap.error("--ssim needs --sigma, --reference, --scale, --jpeg-quality or --bayer: there is nothing to compare a restored image with otherwise")
+        ap.error("--ssim needs --sigma, --reference, --scale, --jpeg-quality, --bayer or --blur: there is nothing to compare a restored image with otherwise")
     if args.y_channel and not args.scored:
-        ap.error("--y-channel needs --sigma, --reference, --scale, --jpeg-quality or --bayer: there is nothing to compare a restored image with "
+        ap.error("--y-channel needs --sigma, --reference, --scale, --jpeg-quality, --bayer or --blur: there is nothing to compare a restored image with "
                  "otherwise")
     if args.jpeg_quality is not None and not 1 <= args.jpeg_quality <= 100:
         ap.error(f"--jpeg-quality: the quality is an integer of 1..100, got {args.jpeg_quality}")
@@ -175,11 +192,17 @@ def parse_args(argv=None):
     if args.demosaic_fill is not None and args.bayer is None and args.raw is None:
         ap.error("--demosaic-fill needs --bayer or --raw")
     args.demosaic_fill = args.demosaic_fill or "malvar"
-    if args.shave is not None and ((args.scale is None and args.bayer is None) or args.shave < 0):
-        ap.error("--shave is a non-negative number of pixels and needs --scale or --bayer")
+    for flag, value in (("--blur-boundary", args.blur_boundary), ("--blur-noise", args.blur_noise)):
+        if value is not None and args.blur is None:
+            ap.error(f"{flag} needs --blur")
+    if args.blur_noise is not None and not 0 <= args.blur_noise < float("inf"):
+        ap.error(f"--blur-noise: the noise level is a non-negative number, got {args.blur_noise}")
+    args.blur_boundary, args.blur_noise = args.blur_boundary or "wrap", args.blur_noise or 0.0
+    if args.shave is not None and ((args.scale is None and args.bayer is None and args.blur is None) or args.shave < 0):
+        ap.error("--shave is a non-negative number of pixels and needs --scale, --bayer or --blur")
     if args.scale is not None and args.shave is None:
         args.shave = args.scale
-    if args.bayer is not None and args.shave is None:
+    if (args.bayer is not None or args.blur is not None) and args.shave is None:
         args.shave = 0
     args.ensemble = 8 if args.self_ensemble else 1
     if args.ensemble_modes is not None:
@@ -233,11 +256,17 @@ def main(argv=None) -> None:
         need_three_channels("--raw", "a demosaicked picture has 3 channels (R, G, B)", 1, "a raw mosaic is a 1-channel image")
     # the degrade-from-clean protocol asked for, if any: read, input_of and finish take its crop, degradation, shave
     # and label from the record (parse_args has checked the values)
-    protocol = (restore._sr_protocol("--scale", args.scale, args.shave) if args.scale is not None else
-                restore._car_protocol("--jpeg-quality", args.jpeg_quality, args.jpeg_subsampling)
-                if args.jpeg_quality is not None else
-                restore._demosaic_protocol("--bayer", args.bayer, args.demosaic_fill, args.shave)
-                if args.bayer is not None else None)
+    try:
+        protocol = (restore._sr_protocol("--scale", args.scale, args.shave) if args.scale is not None else
+                    restore._car_protocol("--jpeg-quality", args.jpeg_quality, args.jpeg_subsampling)
+                    if args.jpeg_quality is not None else
+                    restore._demosaic_protocol("--bayer", args.bayer, args.demosaic_fill, args.shave)
+                    if args.bayer is not None else
+                    restore._deblur_protocol("--blur", args.blur, args.blur_boundary, args.blur_noise, args.seed,
+                                             args.shave)
+                    if args.blur is not None else None)
+    except ValueError as e:          # a kernel spec is only parsed here
+        raise SystemExit(str(e))
     if not torch.cuda.is_available():
         raise SystemExit("restore.py needs a GPU: the HIP engine has no CPU path")
     irdu_amd.load_native()
