@@ -56,7 +56,17 @@ One JSON line ("bench": "blur") with the times, the algorithmic GB/s (a byte rea
 rate as a share of the copy's, and the multiply-adds per second (taps of the table, zeros included, per output byte)
 beside the v_dot4_u32_u8 issue ceiling derived from the clock and the SIMD width, not measured.
 
-    python bench_data.py [--paired | --pair-kernel | --bicubic S | --jpeg Q | --demosaic PATTERN | --blur SPEC] [--steps 60] [--warmup 10] [--images 12] [--side 1200] [--workers 4] [--files 8600]
+With --raw-noise SHOT,READ only the batch kernels of the two ways to train a demosaicking model on noisy inputs are
+timed, on the same pictures held in one arena, at the five shapes above with all eight modes and random origins:
+grr_patch_raw_batch (joint denoising and demosaicking: the noise of variance SHOT x + (READ / 255)^2 on the mosaic,
+before the malvar fill, 16 bits, clipped) against grr_patch_pair_batch with sigma READ / 255 (25 / 255 if READ is 0) over
+the arena kernels.u8_demosaic_images filled beforehand -- white noise after the fill -- and grr_patch_raw_batch without a
+noise table.  Device events around runs of 50 launches on preallocated outputs and uploaded tables, the three
+alternating, 10 rounds.  One JSON line per shape ("bench": "raw_noise") with each kernel's median, fastest and slowest
+round in microseconds per launch, its batches per second, and the normals a batch draws: (ph + 4)(pw + 4) per sample
+for the new kernel, 3 ph pw for the existing noise path.
+
+    python bench_data.py [--paired | --pair-kernel | --bicubic S | --jpeg Q | --demosaic PATTERN | --blur SPEC | --raw-noise SHOT,READ] [--steps 60] [--warmup 10] [--images 12] [--side 1200] [--workers 4] [--files 8600]
 """
 from __future__ import annotations
 
@@ -411,6 +421,67 @@ def blur(spec: str, images: int, side: int, rounds: int = 20, boundary: str = "w
                       "share_of_derived_ceiling": round(n * taps / (med * 1e-3) / (dot4_macs / 2), 3)}), flush=True)
 
 
+def raw_noise(spec: str, images: int, side: int, rounds: int = 10, launches: int = 50, pattern: str = "rggb") -> None:
+    import irdu_amd
+    irdu_amd.load_native()
+    from irdu_amd import _native, kernels, restore
+    dev = torch.device("cuda:0")
+    shot, read = (float(v) for v in spec.split(","))
+    a, b = kernels.raw_noise_pair("bench_data --raw-noise", shot, read)
+    pics = synthetic_pictures(images, side)
+    pack = restore.pack_images(pics, dev)
+    filled = kernels.u8_demosaic_images(pack, pattern, "malvar")
+    raw_src = kernels.patch_raw_source(pack, pattern)
+    pair_src = kernels.patch_pair_source(filled, pack)
+    hw = raw_src.hw
+    stream = torch.cuda.current_stream().cuda_stream
+    rs = np.random.RandomState(3)
+    sigma_level = read if read > 0 else 25.0
+    for n, size in SHAPES:
+        img = np.arange(n) % images
+        rows = np.stack([img, rs.randint(0, hw[img, 0] - size), rs.randint(0, hw[img, 1] - size), np.arange(n) % 8], 1)
+        table = torch.from_numpy(rows.astype(np.int32)).to(dev)
+        ids = torch.arange(n, dtype=torch.int64, device=dev)
+        noise = torch.tensor([[a, b]] * n, dtype=torch.float32, device=dev)
+        sigma = torch.full((n,), sigma_level / 255.0, dtype=torch.float32, device=dev)
+        out = [torch.empty((n, 3, size, size), dtype=torch.float32, device=dev) for _ in range(2)]
+        raw = lambda table_of_noise: _native.call(
+            "grr_patch_raw_batch", pack.arena.data_ptr(), pack.arena.numel(), pack.table.data_ptr(), images,
+            raw_src.patterns.data_ptr(), table.data_ptr(), ids.data_ptr(), table_of_noise, n, 2204, size, size, 2, 16, 1,
+            out[0].data_ptr(), out[1].data_ptr(), stream)
+        calls = {"patch_raw_batch": lambda: raw(noise.data_ptr()),
+                 "patch_pair_batch_sigma": lambda: _native.call(
+                     "grr_patch_pair_batch", filled.arena.data_ptr(), pack.arena.data_ptr(), pack.arena.numel(), 3,
+                     pack.table.data_ptr(), images, table.data_ptr(), ids.data_ptr(), sigma.data_ptr(), n, 2204, size, size,
+                     out[0].data_ptr(), out[1].data_ptr(), stream),
+                 "patch_raw_batch_no_noise": lambda: raw(None)}
+        # the entry points on these tables: one target, and without noise the raw input is the filled arena's up to the
+        # rounding to bytes that the arena went through
+        t_raw, i_raw = kernels.patch_raw_batch(raw_src, table, ids, None, 2204, size, size)
+        t_pair, i_pair = kernels.patch_pair_batch(pair_src, table, ids, None, 2204, size, size)
+        assert torch.equal(t_raw, t_pair) and float((i_raw.clamp(0, 1) - i_pair).abs().max()) <= 0.5 / 255 + 1e-6
+        us = {k: [] for k in calls}
+        for r in range(rounds + 1):                      # round 0 warms all up
+            for name, call in calls.items():
+                start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                start.record()
+                for _ in range(launches):
+                    call()
+                end.record()
+                torch.cuda.synchronize()
+                if r:
+                    us[name].append(start.elapsed_time(end) * 1e3 / launches)
+        line = {"bench": "raw_noise", "shot": shot, "read": read, "a": a, "b": b, "pair_sigma_level": sigma_level,
+                "pattern": pattern, "fill": "malvar", "bits": 16, "images": images, "arena_mb": round(pack.arena.numel() / 2 ** 20, 1),
+                "batch": n, "size": size, "rounds": rounds, "launches": launches, "tile": list(kernels.RAW_NOISE_TILE),
+                "normals_per_batch": {"patch_raw_batch": n * (size + 4) * (size + 4), "patch_pair_batch_sigma": n * 3 * size * size}}
+        for name, v in us.items():
+            med = float(np.median(v))
+            line[name] = {"median_us": round(med, 2), "min_us": round(min(v), 2), "max_us": round(max(v), 2),
+                          "batches_per_s": round(1e6 / med, 1)}
+        print(json.dumps(line), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     # the DataLoader's workers hold up to 2 batches each in flight when the clock starts: enough timed batches
@@ -440,7 +511,12 @@ def main():
     ap.add_argument("--blur", type=str, default=None, metavar="SPEC",
                     help="only time the synthesis of the blurred pictures with this kernel (a spec of "
                          "training.parse_blur_spec, or random:SIDE): the device kernel against numpy on the host")
+    ap.add_argument("--raw-noise", type=str, default=None, metavar="SHOT,READ",
+                    help="only time grr_patch_raw_batch (noise on the mosaic, before the fill) against grr_patch_pair_batch "
+                         "with sigma over a pre-filled demosaic arena, at the curriculum's shapes")
     args = ap.parse_args()
+    if args.raw_noise is not None:
+        return raw_noise(args.raw_noise, args.images, args.side)
     if args.blur is not None:
         return blur(args.blur, args.images, args.side)
     if args.pair_kernel:

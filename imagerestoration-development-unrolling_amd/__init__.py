@@ -52,6 +52,8 @@ from .training import JpegArtifactRemoval  # noqa: F401  (JPEG artifact-removal 
 from .restore import evaluate_car, jpeg_degrade_u8, psnrb_u8  # noqa: F401
 from .training import BayerDemosaicking  # noqa: F401  (demosaicking pairs made from clean files)
 from .restore import demosaic_u8, evaluate_demosaic  # noqa: F401
+from .training import NoisyBayerDemosaicking  # noqa: F401  (joint denoising and demosaicking: noise on the mosaic)
+from .restore import evaluate_jdd, raw_noise_demosaic_u8  # noqa: F401
 from .training import GaussianMotionDeblurring  # noqa: F401  (deblurring pairs made from clean files)
 from .training import BlurKernel, blur_degrade_u8, box_kernel, gaussian_kernel, motion_kernel  # noqa: F401
 from .training import parse_blur_spec, quantise_blur_kernel  # noqa: F401

@@ -205,6 +205,11 @@ SIGNATURES = {
     "grr_u8_demosaic_supported": [I, I, I],
     "grr_u8_demosaic": [P, I, I, I, P, I, I, P],
     "grr_u8_demosaic_images": [P, L, P, I, I, I, P, P, I, P],
+    # joint denoising and demosaicking: sensor noise on the mosaic before the fill (rawnoise_ops.hip)
+    "grr_patch_raw_batch_supported": [I, L, I, I, I],
+    "grr_patch_raw_batch": [P, L, P, I, P, P, P, P, I, ctypes.c_uint64, I, I, I, I, I, P, P, P],
+    "grr_u8_raw_noise_demosaic_supported": [I, I],
+    "grr_u8_raw_noise_demosaic": [P, I, I, P, I, I, Fl, Fl, I, I, ctypes.c_uint64, L, P],
     # 2-D blur by an integer point-spread function (blur_ops.hip)
     "grr_u8_blur_supported": [I, I, I],
     "grr_u8_blur": [P, I, I, I, P, P, I, I, I, P],

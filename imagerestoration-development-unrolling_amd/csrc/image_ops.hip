@@ -521,53 +521,6 @@ __device__ __forceinline__ int64_t sym_index(int64_t r, int64_t n) {
   return t < n ? t : 2 * n - 1 - t;
 }
 
-// Philox4x32-10 (Salmon et al., SC'11; Random123's constants)
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
-                                              uint32_t k1, uint32_t (&x)[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    c0 = hi1 ^ c1 ^ k0;
-    c1 = lo1;
-    c2 = hi0 ^ c3 ^ k1;
-    c3 = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  x[0] = c0; x[1] = c1; x[2] = c2; x[3] = c3;
-}
-
-// the two float64 normals of a word pair: u = (x + 0.5) 2^-32 in (0, 1), Box-Muller
-__device__ __forceinline__ void box_muller(uint32_t xa, uint32_t xb, double* za, double* zb) {
-  const double u0 = ((double)xa + 0.5) * 0x1p-32, u1 = ((double)xb + 0.5) * 0x1p-32;
-  const double r = sqrt(-2.0 * log(u0)), th = 6.283185307179586 * u1;
-  *za = r * cos(th);
-  *zb = r * sin(th);
-}
-
-struct NoiseKey {
-  uint32_t id_lo, id_hi, seed_lo, seed_hi;
-};
-
-// the 4 normals of block b = e / 4 of a sample
-__device__ __forceinline__ void normals4(uint32_t b, const NoiseKey& k, double (&z)[4]) {
-  uint32_t x[4];
-  philox4x32_10(b, 0u, k.id_lo, k.id_hi, k.seed_lo, k.seed_hi, x);
-  box_muller(x[0], x[1], &z[0], &z[1]);
-  box_muller(x[2], x[3], &z[2], &z[3]);
-}
-
-// the normal of element e alone (a lane whose 4 C elements do not start on a block)
-__device__ __forceinline__ double normal_at(uint32_t e, const NoiseKey& k) {
-  uint32_t x[4];
-  philox4x32_10(e >> 2, 0u, k.id_lo, k.id_hi, k.seed_lo, k.seed_hi, x);
-  const bool hi = (e & 2u) != 0;
-  double za, zb;
-  box_muller(hi ? x[2] : x[0], hi ? x[3] : x[1], &za, &zb);
-  return (e & 1u) ? zb : za;
-}
-
 // One block per (sample, 32 x 32 tile of the OUTPUT patch).  Pass 1: a lane reads one source pixel (all C
 // channels) through the mirror rule, adjacent lanes adjacent elements of an image row -- for the odd quarter
 // turns that walks down the tile's columns -- and puts it at its output place in LDS (row stride 33 floats:

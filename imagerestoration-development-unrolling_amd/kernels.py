@@ -2813,6 +2813,158 @@ def u8_demosaic_images(pack, patterns, fill="malvar"):
 
 
 # ---------------------------------------------------------------------------
+# Joint denoising and demosaicking (csrc/rawnoise_ops.hip; include/grr.h has the definition): sensor noise of variance
+# a x + b on the Bayer mosaic, quantised to ``bits`` bits, before the fill -- made per batch, inside the patch kernel.
+RAW_NOISE_TILE = (16, 64)     # a workgroup's rows and columns of the patch, in source orientation
+RAW_NOISE_BITS = (8, 16)      # the smallest and the largest depth of the raw samples
+
+
+def patch_raw_batch_ok(n_img: int, arena_elems: int, n: int, ph: int, pw: int) -> bool:
+    """grr_patch_raw_batch_supported in plain Python (tests/test_raw_noise_abi.py checks the two agree): an RGB arena
+    the arena entry points take, n, ph, pw >= 1, 3 n ph pw < 2^31 and a window (ph + 4)(pw + 4) < 2^31."""
+    return image_arena_ok(3, n_img, arena_elems) and arena_elems >= 3 and n >= 1 and ph >= 1 and pw >= 1 \
+        and 3 * n * ph * pw < (1 << 31) and (ph + 4) * (pw + 4) < (1 << 31)
+
+
+def raw_noise_demosaic_ok(h: int, w: int) -> bool:
+    """grr_u8_raw_noise_demosaic_supported in plain Python: sides >= 1, 3 H W < 2^31 and (H + 4)(W + 4) < 2^31."""
+    return h >= 1 and w >= 1 and 3 * h * w < (1 << 31) and (h + 4) * (w + 4) < (1 << 31)
+
+
+def _check_bits(name: str, bits) -> int:
+    if isinstance(bits, (bool, np.bool_)) or not isinstance(bits, (int, np.integer)) \
+            or not RAW_NOISE_BITS[0] <= bits <= RAW_NOISE_BITS[1]:
+        raise ValueError(f"{name}: bits is an integer of {RAW_NOISE_BITS[0]}..{RAW_NOISE_BITS[1]}, got {bits!r}")
+    return int(bits)
+
+
+def _check_level(name: str, what: str, v, top: float) -> float:
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) \
+            or not (np.isfinite(v) and 0 <= v <= top):
+        raise ValueError(f"{name}: {what} is a number of 0..{top:g}, got {v!r}")
+    return float(v)
+
+
+def raw_noise_pair(name: str, shot, read) -> Tuple[float, float]:
+    """The kernel's float32 noise pair (a, b) of a shot-noise gain ``shot`` (0..1) and a read-noise standard deviation
+    ``read`` in 8-bit levels (0..255, as lambda_noise is): a = float32(shot), b = float32((read / 255)^2)."""
+    shot, read = _check_level(name, "shot", shot, 1.0), _check_level(name, "read", read, 255.0)
+    return float(np.float32(shot)), float(np.float32((read / 255.0) ** 2))
+
+
+class PatchRawSource:
+    """A uint8 RGB image pack that patch_raw_batch's checks have passed (patch_raw_source), with the Bayer code of
+    every image as an int32 device tensor: the pack, its image count, the images' (H, W) as an int64 array, the
+    device pattern list and its host copy."""
+    __slots__ = ("pack", "n_img", "hw", "patterns", "host_patterns")
+
+    def __init__(self, pack, n_img: int, hw, patterns: Tensor, host_patterns: tuple):
+        self.pack, self.n_img, self.hw, self.patterns, self.host_patterns = pack, n_img, hw, patterns, host_patterns
+
+
+def patch_raw_source(pack, patterns) -> PatchRawSource:
+    """Check ``pack`` for patch_raw_batch (as patch_source checks its pack; 3 channels) and ``patterns`` -- one name
+    or code for all images, or a sequence of one per image -- and return their PatchRawSource; the pattern list is
+    uploaded once.  The pack's tensors and host table must not change afterwards."""
+    name = "patch_raw_batch"
+    n_img, c = _check_pack(name, pack, placed=False)
+    if pack.arena.dtype != torch.uint8:
+        raise ValueError(f"{name}: the arena must be uint8, got {pack.arena.dtype}")
+    if c != 3:
+        raise ValueError(f"{name}: a Bayer mosaic is made from R, G, B pictures, got {c} channel(s)")
+    if isinstance(patterns, (str, int, np.integer)):
+        patterns = [patterns] * n_img
+    if len(patterns) != n_img:
+        raise ValueError(f"{name}: {len(patterns)} patterns for {n_img} images")
+    codes = tuple(_check_pattern(name, v) for v in patterns)
+    _check_placed(name, pack)
+    hw = np.asarray(pack.host_table, dtype=np.int64).reshape(n_img, 3)[:, 1:3].copy()
+    return PatchRawSource(pack, n_img, hw, torch.tensor(codes, dtype=torch.int32).to(pack.arena.device), codes)
+
+
+def patch_raw_batch(source: PatchRawSource, rows, sample_ids, noise, seed: int, ph: int, pw: int, fill="malvar",
+                    bits: int = 16, clip: bool = True) -> Tuple[Tensor, Tensor]:
+    """(target, input), float32 [n, 3, ph, pw] each, of a patch_raw_source: sample s is the ph x pw patch of image
+    rows[s][0] at (rows[s][1], rows[s][2]) with a 2-pixel frame, continued outside the picture by the reflection that
+    keeps the colour filter array's parity, sampled through the image's Bayer pattern, given noise of variance
+    a x + b (``noise[s]`` = (a, b), float32 in [0, 1]; the normals are patch_batch's function of (seed,
+    sample_ids[s], window element)), clipped to [0, 1] if ``clip``, quantised to ``bits`` bits, filled by ``fill`` and
+    moved by T_mode (include/grr.h).  input is the filled picture, neither clamped nor rounded again; target the clean
+    patch as float(v) / 255.  ``noise`` None: no noise, and no random number is computed.
+    rows [n, 4], sample_ids [n] and noise [n, 2] are host data, checked here as patch_batch checks its own and
+    uploaded; device tensors (int32 [n, 4], int64 [n], float32 [n, 2], contiguous, on the arena's device) are taken as
+    they are: the kernel clamps what it reads from them."""
+    name = "patch_raw_batch"
+    if not isinstance(source, PatchRawSource):
+        raise ValueError(f"{name}: source is what patch_raw_source returns")
+    fill, bits = _check_fill(name, fill), _check_bits(name, bits)
+    if not isinstance(clip, (bool, np.bool_)):
+        raise ValueError(f"{name}: clip is True or False, got {clip!r}")
+    arena = source.pack.arena
+    on_device = isinstance(rows, Tensor) and rows.is_cuda
+    n = int(rows.shape[0]) if on_device and rows.dim() == 2 else (len(rows) if hasattr(rows, "__len__") else 0)
+    if isinstance(ph, int) and isinstance(pw, int) and min(ph, pw) >= 1 and (ph + 4) * (pw + 4) >= (1 << 31):
+        raise ValueError(f"{name}: the window ({ph} + 4) x ({pw} + 4) must have fewer than 2^31 elements")
+    if noise is not None:
+        if on_device:
+            if not isinstance(noise, Tensor) or noise.dtype != torch.float32 or tuple(noise.shape) != (n, 2) \
+                    or noise.device != arena.device or not noise.is_contiguous():
+                raise ValueError(f"{name}: a device noise table is float32 [n, 2] (a, b), contiguous and on the arena's "
+                                 "device")
+        else:
+            noise = np.asarray(noise, dtype=np.float32)
+            if noise.shape != (n, 2) or not (np.isfinite(noise).all() and (noise >= 0).all() and (noise <= 1).all()):
+                raise ValueError(f"{name}: noise is [n, 2] rows (a, b) of [0, 1], one per row ({n})")
+    table, ids, _ = _patch_tables(name, arena, source.n_img, 3, source.hw, rows, sample_ids, None, seed, ph, pw,
+                                  no_sigma=True)
+    if noise is not None and not on_device:
+        noise = torch.from_numpy(np.ascontiguousarray(noise)).to(arena.device)
+    return _patch_raw_batch(source, table, ids, noise, seed, ph, pw, fill, bits, bool(clip))
+
+
+def _patch_raw_batch(source: PatchRawSource, table: Tensor, ids: Tensor, noise: Optional[Tensor], seed: int, ph: int,
+                     pw: int, fill: int, bits: int, clip: bool) -> Tuple[Tensor, Tensor]:
+    """patch_raw_batch after its checks, on device tables."""
+    arena, n = source.pack.arena, table.shape[0]
+    target = torch.empty((n, 3, ph, pw), dtype=torch.float32, device=arena.device)
+    inp = torch.empty_like(target)
+    _launch("patch_raw_batch", target.numel() * 8 + n * (ph + 4) * (pw + 4), "grr_patch_raw_batch", arena.data_ptr(),
+            arena.numel(), source.pack.table.data_ptr(), source.n_img, source.patterns.data_ptr(), table.data_ptr(),
+            ids.data_ptr(), None if noise is None else noise.data_ptr(), n, int(seed), ph, pw, fill, bits, int(clip),
+            target.data_ptr(), inp.data_ptr(), _stream(arena.device))
+    return target, inp
+
+
+def u8_raw_noise_demosaic(img: Tensor, pattern, fill="malvar", a: float = 0.0, b: float = 0.0, bits: int = 16,
+                          clip: bool = True, seed: int = 2204, sample_id: int = 0) -> Tensor:
+    """The noisy Bayer mosaic of a uint8 H x W x 3 device picture, filled: float32 H x W x 3 (HWC), patch_raw_batch's
+    input of the whole picture (row = col = 0, ph = H, pw = W, mode 0) up to layout.  ``a``, ``b``: the noise pair in
+    [0, 1] (raw_noise_pair makes it from a shot gain and a read level); ``sample_id``: a 64-bit integer.  One launch.
+    A non-contiguous image is copied first."""
+    name = "u8_raw_noise_demosaic"
+    pattern, fill, bits = _check_pattern(name, pattern), _check_fill(name, fill), _check_bits(name, bits)
+    a, b = _check_level(name, "a", a, 1.0), _check_level(name, "b", b, 1.0)
+    if not isinstance(clip, (bool, np.bool_)):
+        raise ValueError(f"{name}: clip is True or False, got {clip!r}")
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < (1 << 64):
+        raise ValueError(f"{name}: seed must fit 64 bits, got {seed!r}")
+    if isinstance(sample_id, bool) or not isinstance(sample_id, (int, np.integer)) or not -(1 << 63) <= sample_id < (1 << 63):
+        raise ValueError(f"{name}: sample_id is a 64-bit integer, got {sample_id!r}")
+    if isinstance(img, Tensor) and img.dtype != torch.uint8:
+        raise ValueError(f"{name}: the image must be uint8, got {img.dtype}")
+    if isinstance(img, Tensor) and img.dim() == 3 and img.shape[2] != 3:
+        raise ValueError(f"{name}: needs 3 channels (R, G, B), got {tuple(img.shape)}")
+    h, w, _ = _check_image(name, img)
+    if not raw_noise_demosaic_ok(h, w):
+        raise ValueError(f"{name}: needs 3 H W < 2^31 and (H + 4)(W + 4) < 2^31, got {tuple(img.shape)}")
+    img = img.contiguous()
+    out = torch.empty((h, w, 3), dtype=torch.float32, device=img.device)
+    _launch("u8_raw_noise_demosaic", img.numel() + out.numel() * 4, "grr_u8_raw_noise_demosaic", img.data_ptr(), h, w,
+            out.data_ptr(), pattern, fill, a, b, bits, int(clip), int(seed), int(sample_id), _stream(img.device))
+    return out
+
+
+# ---------------------------------------------------------------------------
 # 2-D blur by an integer point-spread function (csrc/blur_ops.hip; include/grr.h has the definition): the degradation
 # of deblurring.  A kernel is an int32 table of odd sides up to 31, non-negative, of sum 65536.
 BLUR_TILE = (16, 64)          # a workgroup's rows and columns of the picture

@@ -907,6 +907,78 @@ def evaluate_demosaic(model: Callable, images, pattern="rggb", fill="malvar", sh
                               metrics, device, tile, halo, micro_batch)
 
 
+def _raw_noise_args(who: str, pattern, fill, shot, read, bits, clip, seed):
+    """(pattern code, fill code, a, b, bits, clip, seed) of a joint denoising and demosaicking call, checked in this
+    order; (a, b) is the kernel's float32 noise pair of the shot gain and the read level (kernels.raw_noise_pair)."""
+    pattern, fill = kernels._check_pattern(who, pattern), kernels._check_fill(who, fill)
+    a, b = kernels.raw_noise_pair(who, shot, read)
+    bits = kernels._check_bits(who, bits)
+    if not isinstance(clip, (bool, np.bool_)):
+        raise ValueError(f"{who}: clip is True or False, got {clip!r}")
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 2 ** 64:
+        raise ValueError(f"{who}: seed is an integer of 0..2^64 - 1, got {seed!r}")
+    return pattern, fill, a, b, bits, bool(clip), int(seed)
+
+
+def raw_noise_demosaic_u8(a, pattern="rggb", fill="malvar", shot: float = 0.0, read: float = 0.0, bits: int = 16,
+                          clip: bool = True, seed: int = 2204, sample_id: int = 0):
+    """The input of joint denoising and demosaicking of the uint8 H x W x 3 picture ``a`` (numpy array or tensor, host
+    or device), float32 H x W x 3 of the same kind, on the GPU (kernels.u8_raw_noise_demosaic; include/grr.h has the
+    definition): the Bayer mosaic of ``a`` with sensor noise of variance ``shot`` x + (``read`` / 255)^2 on it -- ``shot``
+    in 0..1, ``read`` in 8-bit levels 0..255 -- clipped to [0, 1] if ``clip``, quantised to ``bits`` (8..16) bits and
+    then filled by ``fill``.  The noise is a function of (seed, sample_id, pixel) alone.  With shot = read = 0 and
+    bits = 8 it is demosaic_u8 before its rounding to bytes."""
+    who = "raw_noise_demosaic_u8"
+    pattern, fill, na, nb, bits, clip, seed = _raw_noise_args(who, pattern, fill, shot, read, bits, clip, seed)
+    if isinstance(sample_id, bool) or not isinstance(sample_id, (int, np.integer)) or not -2 ** 63 <= sample_id < 2 ** 63:
+        raise ValueError(f"{who}: sample_id is a 64-bit integer, got {sample_id!r}")
+    if isinstance(a, (np.ndarray, torch.Tensor)) and a.ndim == 3 and a.shape[2] != 3:
+        raise ValueError(f"{who}: needs 3 channels (R, G, B), got {tuple(a.shape)}")
+    return _resized_u8(who, a, lambda t: kernels.u8_raw_noise_demosaic(t, pattern, fill, na, nb, bits, clip, seed,
+                                                                       int(sample_id)))
+
+
+def _jdd_protocol(who: str, pattern, fill, shot, read, bits, clip, seed, shave) -> _Protocol:
+    """Joint denoising and demosaicking: the whole R, G, B picture mosaicked, noised on the mosaic, quantised and
+    filled, a shave of ``shave``.  The model's input is float32 and not quantised; picture i of the call has sample id
+    i, so its noise is a function of (seed, i) and does not depend on the pictures before it."""
+    pattern, fill, a, b, bits, clip, seed = _raw_noise_args(who, pattern, fill, shot, read, bits, clip, seed)
+    shave = _check_shave(who, shave)
+    count = iter(range(1 << 62))        # degrade is called once per picture, in picture order
+
+    def admit(i, t):
+        if t.shape[2] != 3 or not kernels.raw_noise_demosaic_ok(t.shape[0], t.shape[1]):
+            raise ValueError(f"{who}: image {i} is {tuple(t.shape)}; the protocol takes clean R, G, B pictures")
+
+    label = f"bayer {kernels.DEMOSAIC_PATTERNS[pattern]} {kernels.DEMOSAIC_FILLS[fill]} raw noise shot {float(shot):g} " \
+            f"read {float(read):g} {bits} bits{'' if clip else ' unclipped'} shave {shave}"
+    return _Protocol(who, label=label, defined_on="the mosaic is defined on", admit=admit, crop=lambda h, w: (h, w),
+                     shave=shave, left_after=f"after a shave of {shave}", scored="image {i} after the shave",
+                     degrade=lambda clean: kernels.u8_raw_noise_demosaic(clean, pattern, fill, a, b, bits, clip, seed,
+                                                                         next(count)))
+
+
+def evaluate_jdd(model: Callable, images, pattern="rggb", fill="malvar", shot: float = 0.0, read: float = 0.0,
+                 bits: int = 16, clip: bool = True, seed: int = 2204, shave: int = 0, factor: int = 16, ensemble=1,
+                 metrics=("psnr", "ssim"), **tiling_args) -> dict:
+    """Score ``model`` on joint denoising and demosaicking (the protocol of the Gharbi et al. / Kodak / McMaster
+    tables) over clean uint8 H x W x 3 pictures (numpy arrays or tensors, host or device).  Per picture i: the Bayer
+    mosaic with sensor noise of variance ``shot`` x + (``read`` / 255)^2 on it (``read`` in 8-bit levels), clipped if
+    ``clip``, quantised to ``bits`` bits and filled on the device (kernels.u8_raw_noise_demosaic, sample id i under
+    ``seed``), that float32 picture restored as ``restore_image(..., quantise=True)`` does, ``shave`` pixels cut from
+    each side of the restored and the clean picture, and the two scored with the exact-integer kernels.  "psnr" is the
+    CPSNR.  Returns {metric: (mean, per-image values)} as evaluate_pairs does.  Nothing is drawn on the host: a
+    picture's noise is a function of (seed, i), so a score does not depend on the pictures before it.  tiling_args:
+    tile, halo, micro_batch, device; ``ensemble`` as in restore_image.
+
+    Everything is checked before any launch: the shared arguments, then the pattern, the fill, shot, read, bits, the
+    seed, the shave, uint8 pictures of 3 channels, a picture smaller than the shave leaves, and what the metrics need
+    of the shaved picture."""
+    modes, metrics, device, tile, halo, micro_batch = _evaluate_args("evaluate_jdd", model, ensemble, metrics, tiling_args)
+    return _evaluate_degraded(_jdd_protocol("evaluate_jdd", pattern, fill, shot, read, bits, clip, seed, shave), model,
+                              images, factor, modes, metrics, device, tile, halo, micro_batch)
+
+
 def _blur_kernel(who: str, kernel):
     """The training.BlurKernel of a spec; its refusal under the caller's name."""
     from .training import parse_blur_spec

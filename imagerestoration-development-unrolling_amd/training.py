@@ -753,24 +753,12 @@ class BayerDemosaicking(_DegradedFromClean):
     Two properties to know.  Patches are cut from the filled whole picture at any origin, odd ones included, and the
     8 augmentation modes turn them, so the model sees every phase of the colour filter array under one pattern.  An
     additive ``dist_mode`` (default "none") adds its noise on top of the filled patch, as the sibling datasets do:
-    noise on the mosaic before the fill (joint denoising and demosaicking) is not modelled."""
+    noise on the mosaic before the fill (joint denoising and demosaicking) is NoisyBayerDemosaicking's."""
 
     def __init__(self, csv_path, pattern="rggb", fill="malvar", dist_mode="none", lambda_noise=None,
                  use_data_aug=False, patch_size=(64, 64), max_num_patchs=100000, root_folder="", logger=None,
                  device=None, seed=2204, n_channels=3):
-        who = "BayerDemosaicking"
-        ok = lambda p: isinstance(p, str) and p in BAYER_PATTERNS
-        if isinstance(pattern, (list, tuple)):
-            if len(pattern) != 2 or isinstance(pattern[0], str) or len(pattern[0]) < 1 \
-                    or len(pattern[0]) != len(pattern[1]) or not all(ok(p) for p in pattern[0]):
-                raise ValueError(f"{who}: pattern is one of {BAYER_PATTERNS} or [names, probabilities] with as many "
-                                 f"probabilities as names, got {pattern!r}")
-        elif not ok(pattern):
-            raise ValueError(f"{who}: pattern is one of {BAYER_PATTERNS} or [names, probabilities], got {pattern!r}")
-        if not (isinstance(fill, str) and fill in BAYER_FILLS):
-            raise ValueError(f"{who}: fill is one of {BAYER_FILLS}, got {fill!r}")
-        if n_channels != 3:
-            raise ValueError(f"{who}: a Bayer mosaic is made from R, G, B pictures, got n_channels {n_channels}")
+        _check_bayer_args("BayerDemosaicking", pattern, fill, n_channels)
         self.pattern, self.fill = pattern, fill
         super().__init__(csv_path, dist_mode, lambda_noise, use_data_aug=use_data_aug, patch_size=patch_size,
                          max_num_patchs=max_num_patchs, root_folder=root_folder, logger=logger, device=device,
@@ -778,12 +766,7 @@ class BayerDemosaicking(_DegradedFromClean):
 
     def create_all_images(self):
         super().create_all_images()
-        n = len(self.paths)
-        if isinstance(self.pattern, (list, tuple)):
-            drawn = np.random.RandomState(self.seed).choice(len(self.pattern[0]), p=self.pattern[1], size=n)
-            self.patterns = [str(self.pattern[0][int(k)]) for k in drawn]
-        else:
-            self.patterns = [self.pattern] * n
+        self.patterns = _draw_patterns(self.pattern, self.seed, len(self.paths))
 
     def degrade_host(self, img, clean):
         return demosaic_degrade_u8(clean, self.patterns[img], self.fill)
@@ -794,6 +777,175 @@ class BayerDemosaicking(_DegradedFromClean):
 
     def synthetic_key(self, used):
         return ("bayer", tuple(self.patterns[i] for i in used), self.fill)
+
+
+RAW_NOISE_BITS = (8, 16)      # kernels.RAW_NOISE_BITS
+
+
+def _reflect_any(i: np.ndarray, n: int) -> np.ndarray:
+    """Any indices reflected about the edge samples of a side n, which are not repeated (_mirror for any index)."""
+    if n == 1:
+        return np.zeros_like(i)
+    t = i % (2 * (n - 1))
+    return np.where(t < n, t, 2 * (n - 1) - t)
+
+
+def raw_noise_demosaic_patch(a: np.ndarray, pattern, row: int, col: int, ph: int, pw: int, shot_a: float, read_b: float,
+                             z: Optional[np.ndarray], fill="malvar", bits: int = 16, clip: bool = True):
+    """(target, input) float32 ph x pw x 3 of the joint denoising and demosaicking degradation on the CPU, before
+    T_mode (include/grr.h has the definition): the (ph + 4) x (pw + 4) window of the uint8 H x W x 3 picture ``a`` at
+    (row - 2, col - 2), continued by the reflection that keeps the colour filter array's parity, sampled through
+    ``pattern``, given noise sqrt(shot_a x + read_b) z (``z``: float64 normals [ph + 4, pw + 4], or None for none),
+    clipped, quantised to ``bits`` bits and filled by ``fill``.  With kernels.patch_raw_batch's normals it gives the
+    kernel's floats; the host DataLoader path draws its own."""
+    who = "raw_noise_demosaic_patch"
+    a = np.asarray(a)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or 0 in a.shape:
+        raise ValueError(f"{who}: expected a uint8 H x W x 3 picture, got {a.dtype} {a.shape}")
+    code, fill = _bayer_code(who, "pattern", BAYER_PATTERNS, pattern), _bayer_code(who, "fill", BAYER_FILLS, fill)
+    h, w = a.shape[:2]
+    ry, rx = code >> 1, code & 1
+    ys, xs = _reflect_any(row - 2 + np.arange(ph + 4), h), _reflect_any(col - 2 + np.arange(pw + 4), w)
+    py, px = ((ys ^ ry) & 1)[:, None], ((xs ^ rx) & 1)[None, :]       # 0 in an R row / column
+    x = a[ys[:, None], xs[None, :], py + px].astype(np.float64) / 255.0
+    full = float((1 << bits) - 1)
+    var = float(np.float32(shot_a)) * x + float(np.float32(read_b))
+    t = x if z is None else np.where(var != 0, x + np.sqrt(var) * np.asarray(z, dtype=np.float64), x)
+    if clip:
+        t = np.clip(t, 0.0, 1.0)
+    q = np.clip(np.nan_to_num(np.rint(t * full), nan=0.0), -2.0 ** 24, 2.0 ** 24).astype(np.int64)
+    at = lambda dy, dx: q[2 + dy:2 + dy + ph, 2 + dx:2 + dx + pw]
+    ctr = at(0, 0)
+    if fill == 0:
+        green = other = inrow = incol = np.zeros_like(ctr)
+    else:
+        h1, v1 = at(0, -1) + at(0, 1), at(-1, 0) + at(1, 0)
+        diag = at(-1, -1) + at(-1, 1) + at(1, -1) + at(1, 1)
+        if fill == 1:
+            green, other, inrow, incol = 4 * (h1 + v1), 4 * diag, 8 * h1, 8 * v1
+        else:
+            h2, v2 = at(0, -2) + at(0, 2), at(-2, 0) + at(2, 0)
+            green = 8 * ctr + 4 * (h1 + v1) - 2 * (h2 + v2)
+            other = 12 * ctr + 4 * diag - 3 * (h2 + v2)
+            inrow = 10 * ctr + 8 * h1 - 2 * diag - 2 * h2 + v2
+            incol = 10 * ctr + 8 * v1 - 2 * diag - 2 * v2 + h2
+    cy, cx = py[2:-2], px[:, 2:-2]
+    site, g = cy + cx, cy != cx
+    s = np.stack([np.where(g, np.where(cy == 1, incol, inrow), other), green,
+                  np.where(g, np.where(cy == 1, inrow, incol), other)], axis=2)                # sixteenths
+    s = np.where(site[:, :, None] == np.arange(3), 16 * ctr[:, :, None], s)
+    target = a[ys[2:-2, None], xs[None, 2:-2]].astype(np.float32) / np.float32(255.0)
+    return target, (s.astype(np.float64) / (16.0 * full)).astype(np.float32)
+
+
+def _check_bayer_args(who: str, pattern, fill, n_channels) -> None:
+    """BayerDemosaicking's refusals of pattern, fill and n_channels."""
+    ok = lambda p: isinstance(p, str) and p in BAYER_PATTERNS
+    if isinstance(pattern, (list, tuple)):
+        if len(pattern) != 2 or isinstance(pattern[0], str) or len(pattern[0]) < 1 \
+                or len(pattern[0]) != len(pattern[1]) or not all(ok(p) for p in pattern[0]):
+            raise ValueError(f"{who}: pattern is one of {BAYER_PATTERNS} or [names, probabilities] with as many "
+                             f"probabilities as names, got {pattern!r}")
+    elif not ok(pattern):
+        raise ValueError(f"{who}: pattern is one of {BAYER_PATTERNS} or [names, probabilities], got {pattern!r}")
+    if not (isinstance(fill, str) and fill in BAYER_FILLS):
+        raise ValueError(f"{who}: fill is one of {BAYER_FILLS}, got {fill!r}")
+    if n_channels != 3:
+        raise ValueError(f"{who}: a Bayer mosaic is made from R, G, B pictures, got n_channels {n_channels}")
+
+
+def _draw_patterns(pattern, seed: int, n: int) -> List[str]:
+    """The pattern name of each of n files: the one name, or drawn once, in file order, from RandomState(seed)."""
+    if isinstance(pattern, (list, tuple)):
+        drawn = np.random.RandomState(seed).choice(len(pattern[0]), p=pattern[1], size=n)
+        return [str(pattern[0][int(k)]) for k in drawn]
+    return [pattern] * n
+
+
+def _check_levels(who: str, what: str, v, top: float) -> None:
+    """A noise level: a number of 0..top, or [levels, probabilities] as lambda_noise of vary_addictive_noise is."""
+    ok = lambda q: isinstance(q, (int, float, np.integer, np.floating)) and not isinstance(q, (bool, np.bool_)) \
+        and np.isfinite(q) and 0 <= q <= top
+    if isinstance(v, (list, tuple)):
+        if len(v) != 2 or not isinstance(v[0], (list, tuple)) or len(v[0]) < 1 or len(v[0]) != len(v[1]) \
+                or not all(ok(q) for q in v[0]):
+            raise ValueError(f"{who}: {what} is a number of 0..{top:g} or [levels, probabilities] with as many "
+                             f"probabilities as levels, got {v!r}")
+    elif not ok(v):
+        raise ValueError(f"{who}: {what} is a number of 0..{top:g} or [levels, probabilities], got {v!r}")
+
+
+def _draw_levels(rs: np.random.RandomState, v, n: int) -> np.ndarray:
+    """n levels of a _check_levels value as float64: drawn from ``rs`` if it is a distribution, else repeated."""
+    if isinstance(v, (list, tuple)):
+        return np.asarray(rs.choice(v[0], p=v[1], size=n), dtype=np.float64)
+    return np.full(n, float(v))
+
+
+def raw_noise_pairs(shot: np.ndarray, read: np.ndarray) -> np.ndarray:
+    """The kernel's float32 [n, 2] noise pairs (a, b) of shot gains and read levels (8-bit units, as lambda_noise):
+    a = float32(shot), b = float32((read / 255)^2)."""
+    shot, read = np.asarray(shot, dtype=np.float64), np.asarray(read, dtype=np.float64)
+    return np.stack([shot.astype(np.float32), ((read / 255.0) ** 2).astype(np.float32)], axis=1)
+
+
+class NoisyBayerDemosaicking(ImageSuperResolution):
+    """Joint denoising and demosaicking pairs synthesised from clean RGB files under ImageSuperResolution's csv, crop
+    and patch plan: the input of a sample is the patch sampled through a Bayer colour filter array, given sensor noise
+    ON THE MOSAIC -- variance ``shot`` x + (``read`` / 255)^2 for a signal x in [0, 1] -- clipped to [0, 1] if ``clip``,
+    quantised to ``bits`` bits and only then filled (raw_noise_demosaic_patch; include/grr.h has the definition), so
+    the fill spreads and correlates the noise as a camera pipeline does; the target is the clean patch.  ``pattern``
+    and ``fill`` as BayerDemosaicking takes them, with the same per-file draw.  ``shot`` (0..1) and ``read`` (0..255,
+    8-bit levels like ``lambda_noise``): a number, or ``[levels, probabilities]`` drawn per sample.  ``dist_mode`` must
+    be "none": the noise is the sensor's.  A patch that sticks out of its picture is continued by the reflection that
+    keeps the array's parity, not by the siblings' edge-repeating mirror.
+
+    The noise is fresh per sample and per epoch and lies under the fill, so there is no degraded arena: a
+    DevicePatchLoader holds the clean arena and the files' pattern codes, and a batch is one kernels.patch_raw_batch
+    call.  ``__getitem__`` is the host path: the same formula in numpy with normals from the dataset's RandomState
+    (after the mode and the level draws); its noise is not the device's."""
+
+    DIST_MODES = ("none",)
+
+    def __init__(self, csv_path, pattern="rggb", fill="malvar", shot=0.0, read=0.0, bits=16, clip=True, dist_mode="none",
+                 lambda_noise=None, use_data_aug=False, patch_size=(64, 64), max_num_patchs=100000, root_folder="",
+                 logger=None, device=None, seed=2204, n_channels=3):
+        who = "NoisyBayerDemosaicking"
+        _check_bayer_args(who, pattern, fill, n_channels)
+        _check_levels(who, "shot", shot, 1.0)
+        _check_levels(who, "read", read, 255.0)
+        if isinstance(bits, bool) or not isinstance(bits, int) or not RAW_NOISE_BITS[0] <= bits <= RAW_NOISE_BITS[1]:
+            raise ValueError(f"{who}: bits is an integer of {RAW_NOISE_BITS[0]}..{RAW_NOISE_BITS[1]}, got {bits!r}")
+        if not isinstance(clip, bool):
+            raise ValueError(f"{who}: clip is true or false, got {clip!r}")
+        if dist_mode != "none":
+            raise ValueError(f"{who}: dist_mode must be 'none' (the noise is shot and read, on the mosaic), got "
+                             f"{dist_mode!r}")
+        self.pattern, self.fill, self.shot, self.read, self.bits, self.clip = pattern, fill, shot, read, bits, clip
+        super().__init__(csv_path, dist_mode, lambda_noise, use_data_aug=use_data_aug, patch_size=patch_size,
+                         max_num_patchs=max_num_patchs, root_folder=root_folder, logger=logger, device=device,
+                         seed=seed, n_channels=n_channels)
+
+    def create_all_images(self):
+        super().create_all_images()
+        self.patterns = _draw_patterns(self.pattern, self.seed, len(self.paths))
+
+    @property
+    def noise_free(self) -> bool:
+        """shot and read are both the number 0: no generator runs."""
+        return not isinstance(self.shot, (list, tuple)) and not isinstance(self.read, (list, tuple)) \
+            and self.shot == 0 and self.read == 0
+
+    def __getitem__(self, idx):
+        row, col, _, img_i = self.patchs_data[idx]
+        h, w = self.out_size()
+        rs = self.random_state
+        mode = rs.randint(0, 7) if self.use_data_augmentation else 0
+        pair = raw_noise_pairs(_draw_levels(rs, self.shot, 1), _draw_levels(rs, self.read, 1))[0]
+        z = None if self.noise_free else rs.standard_normal((h + 4, w + 4))
+        tgt, inp = raw_noise_demosaic_patch(self.load_image(img_i), self.patterns[img_i], row, col, h, w, pair[0], pair[1],
+                                            z, self.fill, self.bits, self.clip)
+        return torch.from_numpy(data_augmentation(inp, mode)), torch.from_numpy(data_augmentation(tgt, mode))
 
 
 BLUR_BOUNDARIES = ("wrap", "replicate", "reflect")      # kernels.BLUR_BOUNDARIES: the index is the code
@@ -1076,7 +1228,12 @@ class DevicePatchLoader:
     goes the same way with kernels.u8_jpeg_images at each file's quality: the switch is the datasets' common base
     class, whose ``degrade_pack`` makes the arena and whose ``synthetic_key`` tells one degradation from another in a
     shared store.  A BayerDemosaicking dataset is a third of the kind (kernels.u8_demosaic_images, each file's
-    pattern), a GaussianMotionDeblurring dataset a fourth (kernels.u8_blur_images, each file's kernel)."""
+    pattern), a GaussianMotionDeblurring dataset a fourth (kernels.u8_blur_images, each file's kernel).
+
+    A NoisyBayerDemosaicking dataset yields (input, target) from the clean arena alone: its degradation -- noise on the
+    mosaic, then the fill -- is made per batch inside kernels.patch_raw_batch, so the device holds one arena (shared
+    with any other stage over the same files) and the files' pattern codes.  After the draws above the epoch stream
+    gives the per-sample shot and then read levels where they are distributions (``epoch_noise``)."""
     channels_first = True
     CHUNK_BYTES = 256 << 20      # decoded pictures staged on the host per transfer
 
@@ -1093,8 +1250,10 @@ class DevicePatchLoader:
         self.shared = shared
         self.synthetic = isinstance(dataset, _DegradedFromClean)         # the input arena is made on the device
         self.paired = self.synthetic or isinstance(dataset, PairedImageRestoration)
+        self.raw = isinstance(dataset, NoisyBayerDemosaicking)          # the degradation is made per batch
         self.source = None           # kernels.PatchSource (PatchPairSource if paired): the arena(s), checked once
-        self._draws = (None, None, None)
+        self.raw_source = None       # raw: kernels.PatchRawSource over source's pack
+        self._draws = (None, None, None, None)
 
     def __len__(self):
         n = len(self.sampler)
@@ -1158,6 +1317,11 @@ class DevicePatchLoader:
                     packs = (ds.degrade_pack(packs[0], used), packs[0])
                 store[key] = kernels.patch_pair_source(*packs) if self.paired else kernels.patch_source(*packs)
             self.source = store[key]
+            if self.raw:             # the one clean arena, under its plain key, and this dataset's pattern codes
+                raw_key = key + ("raw", tuple(ds.patterns[i] for i in used))
+                if raw_key not in store:
+                    store[raw_key] = kernels.patch_raw_source(self.source.pack, [ds.patterns[i] for i in used])
+                self.raw_source = store[raw_key]
         return (self.source.input, self.source.target) if self.paired else self.source.pack
 
     def epoch_draws(self, epoch: int) -> Tuple[np.ndarray, np.ndarray]:
@@ -1174,8 +1338,15 @@ class DevicePatchLoader:
             else:
                 levels = np.full(n, ds.lambda_noise)
             sigma = (np.asarray(levels, dtype=np.float64) / 255.0).astype(np.float32)
-            self._draws = ((epoch, n), modes.astype(np.int64), sigma)
+            noise = raw_noise_pairs(_draw_levels(rs, ds.shot, n), _draw_levels(rs, ds.read, n)) if self.raw else None
+            self._draws = ((epoch, n), modes.astype(np.int64), sigma, noise)
         return self._draws[1], self._draws[2]
+
+    def epoch_noise(self, epoch: int) -> np.ndarray:
+        """The float32 [n, 2] noise pairs (a, b) of the epoch of a NoisyBayerDemosaicking dataset, in dataset order:
+        drawn from the epoch's stream after epoch_draws' own draws, the shot levels first."""
+        self.epoch_draws(epoch)
+        return self._draws[3]
 
     def batch(self, positions: Sequence[int]):
         """(noisy, clean) -- (input, target) of a paired dataset -- of the samples at these positions of the current
@@ -1190,6 +1361,11 @@ class DevicePatchLoader:
         rows = np.stack([self._slot[plan[:, 0]], plan[:, 1], plan[:, 2], modes[pos]], axis=1)
         h, w = ds.out_size()
         ids = (np.int64(epoch) << 32) | pos
+        if self.raw:
+            target, inp = kernels.patch_raw_batch(self.raw_source, rows, ids,
+                                                  None if ds.noise_free else self.epoch_noise(epoch)[pos], ds.seed, h, w,
+                                                  ds.fill, ds.bits, ds.clip)
+            return inp, target
         if self.paired:
             target, inp = kernels.patch_pair_batch(self.source, rows, ids, None if ds.dist_mode == "none" else sigma[pos],
                                                    ds.seed, h, w)
@@ -1210,7 +1386,7 @@ class DevicePatchLoader:
 
 DATASETS = {c.__name__: c for c in (AddictiveGaussianNoiseImagePair, SyntheticNoisyPatches, ImageSuperResolution,
                                     PairedImageRestoration, BicubicSuperResolution, JpegArtifactRemoval,
-                                    BayerDemosaicking, GaussianMotionDeblurring)}
+                                    BayerDemosaicking, NoisyBayerDemosaicking, GaussianMotionDeblurring)}
 
 
 # ---------------------------------------------------------------------------
@@ -1446,6 +1622,25 @@ def validate_demosaic(model: nn.Module, images, bayer="rggb", fill="malvar", sha
                               metric, pattern=bayer, fill=fill, shave=shave, factor=factor, **tiling_args)
 
 
+def validate_jdd(model: nn.Module, images, raw_noise=(0.0, 0.0), bayer="rggb", fill="malvar", bits: int = 16,
+                 clip: bool = True, seed: int = 2204, shave: int = 0, factor: int = 16, device=None, metric: str = "psnr",
+                 **tiling_args) -> float:
+    """Mean score of ``model`` on joint denoising and demosaicking over clean RGB test pictures (``images[i]``: uint8
+    H x W x 3, or float32 in [0, 1] on the uint8 grid as TestImagesCSV yields them): restore.evaluate_jdd on this
+    rank's share -- mosaic with the pattern ``bayer``, sensor noise ``raw_noise`` = (shot, read) on the mosaic, ``bits``
+    bits, ``fill``, all on the device, restore, cut ``shave`` pixels from each side, score against the clean picture.
+    ``metric``: "psnr" (default, the CPSNR), "psnr_y" or "ssim".  The noise of a picture is a function of (seed, its
+    index in this rank's share); nothing is drawn on the host.  tiling_args: tile, halo, micro_batch, ensemble.
+
+    Several ranks: sharded and all-reduced as validate_pairs does."""
+    from . import restore
+    if not isinstance(raw_noise, (list, tuple)) or len(raw_noise) != 2:
+        raise ValueError(f"validate_jdd: raw_noise is (shot, read), got {raw_noise!r}")
+    return _validate_degraded("validate_jdd", VAL_DEMOSAIC_METRICS, restore.evaluate_jdd, model, images, device, metric,
+                              pattern=bayer, fill=fill, shot=raw_noise[0], read=raw_noise[1], bits=bits, clip=clip,
+                              seed=seed, shave=shave, factor=factor, **tiling_args)
+
+
 VAL_DEBLUR_METRICS = ("psnr", "psnr_y", "ssim")
 
 
@@ -1473,6 +1668,15 @@ def _val_blur_spec(v) -> str:
     return v
 
 
+def _val_raw_noise(v) -> List[float]:
+    """``datasets.val.raw_noise``: [shot, read], checked here so that a bad pair is refused with the config."""
+    from . import kernels
+    if not isinstance(v, (list, tuple)) or len(v) != 2:
+        raise ValueError(f"datasets.val.raw_noise is [shot, read] (a gain of 0..1, 8-bit levels of 0..255), got {v!r}")
+    kernels.raw_noise_pair("datasets.val.raw_noise", v[0], v[1])
+    return [float(v[0]), float(v[1])]
+
+
 class _ValProtocol(NamedTuple):
     """A row of _VAL_PROTOCOLS: how a ``datasets.val`` section selects a validator, and which of its keys the
     validator gets (beside factor, tile, halo, micro_batch and metric, which every row has)."""
@@ -1497,10 +1701,25 @@ _VAL_PROTOCOLS = (      # in order of precedence; a section that selects no row 
 )
 
 
+# Joint denoising and demosaicking refines the ``bayer`` row: a section with a ``raw_noise`` key is taken here, directly
+# before that row, and a section without one never sees this record
+_VAL_RAW_NOISE = _ValProtocol("raw_noise", TestImagesCSV, _val_raw_noise, ("shave", "bits"),
+                              {"bayer": BAYER_PATTERNS, "fill": BAYER_FILLS}, VAL_DEMOSAIC_METRICS, validate_jdd)
+
+
+def _val_protocols() -> Iterator[_ValProtocol]:
+    """The rows a ``datasets.val`` section is matched against, in order of precedence: _VAL_PROTOCOLS with
+    _VAL_RAW_NOISE directly before the ``bayer`` row."""
+    for p in _VAL_PROTOCOLS:
+        if p.key == "bayer":
+            yield _VAL_RAW_NOISE
+        yield p
+
+
 def val_check(val_set, val_args: dict) -> Callable:
     """The validator of what create_val_dataset returned: ``val_check(val_set, val_args)(model, val_set, device=device,
     **val_args)`` is the validation run() makes."""
-    for p in _VAL_PROTOCOLS:
+    for p in _val_protocols():
         if (p.key in val_args) if p.key else isinstance(val_set, p.dataset):
             return p.validator
     return validate
@@ -1515,7 +1734,9 @@ def create_val_dataset(conf: dict):
     {type, dataset_args, jpeg_quality, subsampling, factor, tile, halo, micro_batch, metric}, validate_car's
     arguments, no sigma.  TestImagesCSV with a ``bayer`` key (a pattern name) is demosaicking:
     {type, dataset_args, bayer, fill, shave, factor, tile, halo, micro_batch, metric}, validate_demosaic's arguments,
-    no sigma.  TestImagesCSV with a ``blur`` key (a kernel spec string) is deblurring:
+    no sigma.  With a ``raw_noise`` key ([shot, read]) as well, or alone, it is joint denoising and demosaicking:
+    {type, dataset_args, raw_noise, bayer, fill, shave, bits, factor, tile, halo, micro_batch, metric}, validate_jdd's
+    arguments; ``raw_noise`` takes precedence over ``bayer``.  TestImagesCSV with a ``blur`` key (a kernel spec string) is deblurring:
     {type, dataset_args, blur, boundary, noise_sigma, shave, factor, tile, halo, micro_batch, metric},
     validate_deblur's arguments; the noise on the blurred picture is ``noise_sigma``, not ``sigma``."""
     vconf = conf.get("datasets", {}).get("val")
@@ -1524,7 +1745,7 @@ def create_val_dataset(conf: dict):
     cls = VAL_DATASETS.get(vconf["type"])
     if cls is None:
         raise ValueError(f"Validation dataset {vconf['type']} is not found.")
-    for p in _VAL_PROTOCOLS:
+    for p in _val_protocols():
         if cls is not p.dataset or (p.key is not None and vconf.get(p.key) is None):
             continue
         for k, allowed in p.choices.items():
@@ -1614,8 +1835,8 @@ class TrainStage:
             # batches made on the device from a packed arena; dataloader_args' num_workers is ignored
             if not isinstance(self.dataset, ImageSuperResolution):
                 raise ValueError(f"training stage {index}: device_resident needs type ImageSuperResolution, "
-                                 "PairedImageRestoration, BicubicSuperResolution, JpegArtifactRemoval, BayerDemosaicking or "
-                                 "GaussianMotionDeblurring, got "
+                                 "PairedImageRestoration, BicubicSuperResolution, JpegArtifactRemoval, BayerDemosaicking, "
+                                 "NoisyBayerDemosaicking or GaussianMotionDeblurring, got "
                                  f"{ds_conf['type']}")
             self.loader = DevicePatchLoader(self.dataset, self.sampler, self.batch_size, self.drop_last,
                                             shared=shared)

@@ -1101,6 +1101,58 @@ grr_status grr_u8_demosaic(const uint8_t* src, int H, int W, int src_c, uint8_t*
 grr_status grr_u8_demosaic_images(const uint8_t* arena, int64_t elems, const int64_t* table, int n_img, int max_h,
                                   int max_w, uint8_t* dst_arena, const int32_t* patterns, int fill, void* stream);
 
+/* ---- joint denoising and demosaicking (csrc/rawnoise_ops.hip): sensor noise on the Bayer mosaic, BEFORE the fill.  A
+ * sensor measures one noisy sample per pixel; the fill above then spreads and correlates that noise over the three
+ * channels.  Because the noise must be fresh per sample and lie under a 5 x 5 filter, the degradation is made at batch
+ * time, inside the patch kernel: cut, mosaic, noise, quantise, fill, turn, one launch.  It ends in exact integers:
+ * floating point appears only before one rounding.
+ *
+ * Per sample s: a table row (img, row, col, mode) and a sample id, as grr_patch_batch takes them; a noise pair (a, b),
+ *   float32: the noise variance is a x + b for a signal x in [0, 1], a the shot-noise gain and b the read-noise
+ *   variance, both in [0, 1]; the Bayer code 0..3 of image img, as grr_u8_demosaic takes it; the H x W x 3 uint8
+ *   picture.  Call-wide: fill 0..2, bits 8..16 with full = 2^bits - 1, clip 0 / 1, a uint64 seed.
+ * Window: (ph + 4) x (pw + 4).  Window position (wy, wx) has image coordinates Y = row + wy - 2, X = col + wx - 2 and
+ *   reads picture pixel (y', x') = (reflect(Y, H), reflect(X, W)), reflect the border rule of the demosaic section
+ *   above taken for any index: no repeated edge sample, parity kept for a side >= 2, index 0 for a side of 1.  The
+ *   channel it measures is the site of (y', x').  A patch that sticks out of its picture is therefore continued by
+ *   this reflection, not by grr_patch_batch's sym, which would break the colour filter array's parity.
+ * Raw sample: with v the byte read, x = v / 255 and var = a x + b, t = x + sqrt(var) z_e, where e = wy (pw + 4) + wx
+ *   and z_e is grr_patch_batch's normal of (seed, sample id, element e): block e / 4, lane e % 4.  If clip, t is
+ *   clamped to [0, 1].  q is the integer nearest to t full, ties to even, then clamped to +-2^24; a NaN gives 0 (the
+ *   clamp cannot bind for a, b in [0, 1]: |z| < 6.8).  Where var == 0 no random number is computed.  Everything
+ *   before the rounding is float64, in any association or contraction.
+ * Fill: the demosaic section's sums with m replaced by q: s an int32 in sixteenths (|s| <= 40 * 2^24), the site's own
+ *   channel s = 16 q, the filter set chosen by the site of (y', x').  The value is (float)((double)s / (16.0 full)):
+ *   one float64 division, one conversion; no clamp and no rounding to bytes.  The 2-sample halo of the window is
+ *   exactly what the 5 x 5 filters need: the fill itself has no border rule.
+ * Outputs: patch pixel (i, j) is window position (i + 2, j + 2), moved by T_mode exactly as grr_patch_batch moves it
+ *   (odd quarter turns need ph == pw; an illegal mode is read as mode & 5).  input holds the three filled channels,
+ *   target is float(v) / 255.0f of the same picture pixel's three channels; both float32 [n, 3, ph, pw], planar.
+ *   noise == NULL means a = b = 0 for every sample.  A sample does not depend on the batch it is in.
+ *
+ * arena, arena_elems, img_table, n_img, table, sample_ids: as grr_patch_batch takes them, C = 3 understood; patterns:
+ * int32 [n_img] on the device; noise: float32 [n, 2] on the device, rows (a, b), or NULL.  Every table value is
+ * clamped as in grr_patch_batch, the pattern into 0..3: a bad table gives wrong pixels, never an access outside the
+ * buffers.  No atomics. */
+
+/* 1 where grr_patch_raw_batch takes the call: grr_image_arena_supported(3, n_img, arena_elems), n, ph, pw >= 1,
+ * 3 n ph pw < 2^31 and (ph + 4)(pw + 4) < 2^31. */
+int grr_patch_raw_batch_supported(int n_img, int64_t arena_elems, int n, int ph, int pw);
+/* GRR_ERR_INVALID_ARG for a fill outside 0..2, bits outside 8..16 or a clip that is not 0 or 1, before any launch;
+ * GRR_ERR_UNSUPPORTED where the query says 0. */
+grr_status grr_patch_raw_batch(const uint8_t* arena, int64_t arena_elems, const int64_t* img_table, int n_img,
+                               const int32_t* patterns, const int32_t* table, const int64_t* sample_ids,
+                               const float* noise /* [n, 2] or NULL */, int n, uint64_t seed, int ph, int pw, int fill,
+                               int bits, int clip, float* target, float* input, void* stream);
+/* 1 where grr_u8_raw_noise_demosaic takes the image: H, W >= 1, 3 H W < 2^31 and (H + 4)(W + 4) < 2^31. */
+int grr_u8_raw_noise_demosaic_supported(int H, int W);
+/* One picture: the same kernel body with row = col = 0, ph = H, pw = W, mode 0, no device tables and no target.  src:
+ * H x W x 3 uint8 at any byte address; dst: float32 H x W x 3, HWC (the patch form's input up to layout).
+ * GRR_ERR_INVALID_ARG for a pattern outside 0..3, a fill, bits or clip as above, or a, b outside [0, 1]. */
+grr_status grr_u8_raw_noise_demosaic(const uint8_t* src, int H, int W, float* dst /* float32 H x W x 3, HWC */,
+                                     int pattern, int fill, float a, float b, int bits, int clip, uint64_t seed,
+                                     int64_t sample_id, void* stream);
+
 /* ---- 2-D blur by an integer point-spread function (csrc/blur_ops.hip): the degradation of deblurring.  No floating
  * point appears in the definition.
  *

@@ -5,6 +5,7 @@
             | --scale S [--shave N] [--ssim] [--y-channel] | --upscale S
             | --jpeg-quality Q [--jpeg-subsampling 444|420] [--psnrb] [--ssim] [--y-channel]
             | --bayer PATTERN [--demosaic-fill FILL] [--shave N] [--ssim] [--y-channel]
+              [--raw-noise SHOT,READ [--raw-bits N] [--raw-no-clip] [--raw-seed N]]
             | --raw PATTERN [--demosaic-fill FILL]
             | --blur SPEC [--blur-boundary B] [--blur-noise S] [--shave N] [--ssim] [--y-channel]]
            [--tile T --halo H --factor F] [--batch-images]
@@ -50,7 +51,12 @@ With --bayer PATTERN (rggb, grbg, gbrg or bggr; not with the other scored modes)
 demosaicking protocol runs on each: it is sampled through the Bayer colour filter array and its missing channels are
 filled on the GPU (``irdu_amd.demosaic_u8``; --demosaic-fill zero, bilinear or malvar, the default), the filled picture
 is restored and scored against the input after --shave N border pixels (default 0) are cut from both.  The PSNR over
-the three channels is the CPSNR of the demosaicking tables; --ssim and --y-channel apply as above.  With --raw PATTERN
+the three channels is the CPSNR of the demosaicking tables; --ssim and --y-channel apply as above.  With --raw-noise
+SHOT,READ beside --bayer the protocol is joint denoising and demosaicking (``irdu_amd.evaluate_jdd``): sensor noise of
+variance SHOT x + (READ / 255)^2 -- SHOT a gain of 0..1, READ in 8-bit levels -- is put on the mosaic, which is clipped
+to [0, 1] (unless --raw-no-clip), quantised to --raw-bits N bits (8..16, default 16) and only then filled
+(``irdu_amd.raw_noise_demosaic_u8``); the model's input is that float32 picture.  File i has sample id i under
+--raw-seed N (default 2204), so its noise does not depend on the other files.  With --raw PATTERN
 the inputs are 1-channel mosaic files as a sensor gives them: each is filled to RGB the same way, restored and written
 as RGB; nothing is scored.  Both need a 3-channel model and work with --batch-images and the ensemble options.
 With --blur SPEC (gaussian:SIDE:SIGMA, box:SIDE, motion:LENGTH:ANGLE or file:PATH.npy; not with the other scored modes)
@@ -147,6 +153,13 @@ def parse_args(argv=None):
                     help="with --blur: add N(0, S/255) noise to the blurred picture (default 0: none)")
     ap.add_argument("--demosaic-fill", type=str, default=None, choices=FILLS,
                     help="with --bayer or --raw: how the missing channels are filled before the model (default malvar)")
+    ap.add_argument("--raw-noise", type=str, default=None, metavar="SHOT,READ",
+                    help="with --bayer: joint denoising and demosaicking -- noise of variance SHOT x + (READ / 255)^2 on the "
+                         "mosaic, before the fill (SHOT 0..1, READ in 8-bit levels 0..255)")
+    ap.add_argument("--raw-bits", type=int, default=None, metavar="N",
+                    help="with --raw-noise: the depth of the raw samples, 8..16 (default 16)")
+    ap.add_argument("--raw-no-clip", action="store_true", help="with --raw-noise: do not clip the noisy mosaic to [0, 1]")
+    ap.add_argument("--raw-seed", type=int, default=None, metavar="N", help="with --raw-noise: the noise seed (default 2204)")
     ap.add_argument("--jpeg-subsampling", type=str, default=None, choices=("444", "420"),
                     help="with --jpeg-quality: the chroma subsampling of RGB files (default 444)")
     ap.add_argument("--psnrb", action="store_true",
@@ -192,6 +205,26 @@ def parse_args(argv=None):
     if args.demosaic_fill is not None and args.bayer is None and args.raw is None:
         ap.error("--demosaic-fill needs --bayer or --raw")
     args.demosaic_fill = args.demosaic_fill or "malvar"
+    if args.raw_noise is not None:
+        if args.bayer is None:
+            ap.error("--raw-noise needs --bayer")
+        try:
+            shot, read = (float(v) for v in args.raw_noise.split(","))
+        except ValueError:
+            ap.error(f"--raw-noise: expected SHOT,READ, two numbers separated by a comma, got {args.raw_noise!r}")
+        if not (0 <= shot <= 1 and 0 <= read <= 255):
+            ap.error(f"--raw-noise: SHOT is a gain of 0..1 and READ a level of 0..255, got {args.raw_noise!r}")
+        args.raw_noise = (shot, read)
+    for flag, value in (("--raw-bits", args.raw_bits), ("--raw-no-clip", args.raw_no_clip or None),
+                        ("--raw-seed", args.raw_seed)):
+        if value is not None and args.raw_noise is None:
+            ap.error(f"{flag} needs --raw-noise")
+    if args.raw_bits is not None and not 8 <= args.raw_bits <= 16:
+        ap.error(f"--raw-bits: the depth is an integer of 8..16, got {args.raw_bits}")
+    if args.raw_seed is not None and not 0 <= args.raw_seed < 2 ** 64:
+        ap.error(f"--raw-seed: the seed is an integer of 0..2^64 - 1, got {args.raw_seed}")
+    args.raw_bits = 16 if args.raw_bits is None else args.raw_bits
+    args.raw_seed = 2204 if args.raw_seed is None else args.raw_seed
     for flag, value in (("--blur-boundary", args.blur_boundary), ("--blur-noise", args.blur_noise)):
         if value is not None and args.blur is None:
             ap.error(f"{flag} needs --blur")
@@ -260,6 +293,9 @@ def main(argv=None) -> None:
         protocol = (restore._sr_protocol("--scale", args.scale, args.shave) if args.scale is not None else
                     restore._car_protocol("--jpeg-quality", args.jpeg_quality, args.jpeg_subsampling)
                     if args.jpeg_quality is not None else
+                    restore._jdd_protocol("--bayer", args.bayer, args.demosaic_fill, args.raw_noise[0], args.raw_noise[1],
+                                          args.raw_bits, not args.raw_no_clip, args.raw_seed, args.shave)
+                    if args.raw_noise is not None else
                     restore._demosaic_protocol("--bayer", args.bayer, args.demosaic_fill, args.shave)
                     if args.bayer is not None else
                     restore._deblur_protocol("--blur", args.blur, args.blur_boundary, args.blur_noise, args.seed,
