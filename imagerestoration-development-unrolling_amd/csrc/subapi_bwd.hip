@@ -296,7 +296,8 @@ grr_status grr_normalize_features_bwd(const float* f, const float* multiM, const
   clear_error();
   GRR_REQUIRE(f && multiM && gout && gf && gM && B > 0 && G > 0 && F > 0 && H > 0 && W > 0, GRR_ERR_INVALID_ARG,
               "grr_normalize_features_bwd: bad args");
-  GRR_REQUIRE(F <= 16 && (int64_t)B * G < 65536, GRR_ERR_UNSUPPORTED, "grr_normalize_features_bwd: F > 16");
+  GRR_REQUIRE(F <= 16, GRR_ERR_UNSUPPORTED, "grr_normalize_features_bwd: F > 16");
+  GRR_REQUIRE((int64_t)B * G < 65536, GRR_ERR_UNSUPPORTED, "grr_normalize_features_bwd: B*G >= 65536");
   const dim3 grid = grid2((int64_t)H * W, (int64_t)B * G);
   RedScratch rs((hipStream_t)stream);
   const int im = rs.plan(gM, G * F, (uint32_t)B * grid.x);
