@@ -66,7 +66,15 @@ alternating, 10 rounds.  One JSON line per shape ("bench": "raw_noise") with eac
 round in microseconds per launch, its batches per second, and the normals a batch draws: (ph + 4)(pw + 4) per sample
 for the new kernel, 3 ph pw for the existing noise path.
 
-    python bench_data.py [--paired | --pair-kernel | --bicubic S | --jpeg Q | --demosaic PATTERN | --blur SPEC | --raw-noise SHOT,READ] [--steps 60] [--warmup 10] [--images 12] [--side 1200] [--workers 4] [--files 8600]
+With --inpaint KEEP the inpainting batches are timed at the five shapes above: training.RandomMaskInpainting (conv fill,
+flat 7 x 7) under a DataLoader and under the DevicePatchLoader, as the first paragraph times the noise set, and then the
+kernels alone on one uploaded table with all eight modes and random origins -- grr_patch_mask_batch with the zero fill
+and with the conv fill at sides 7 and 15, and grr_patch_batch (sigma 25 / 255) on the same arena -- device events around
+runs of 50 launches on preallocated outputs, the four alternating, 10 rounds.  One JSON line per shape ("bench":
+"inpaint") with both loaders' batches per second, each kernel's median, fastest and slowest round in microseconds per
+launch and the ratio of each fill to grr_patch_batch.
+
+    python bench_data.py [--paired | --pair-kernel | --bicubic S | --jpeg Q | --demosaic PATTERN | --blur SPEC | --raw-noise SHOT,READ | --inpaint KEEP] [--steps 60] [--warmup 10] [--images 12] [--side 1200] [--workers 4] [--files 8600]
 """
 from __future__ import annotations
 
@@ -482,6 +490,88 @@ def raw_noise(spec: str, images: int, side: int, rounds: int = 10, launches: int
         print(json.dumps(line), flush=True)
 
 
+def inpaint(keep: float, images: int, side: int, steps: int, warmup: int, device_steps: int, workers: int,
+            rounds: int = 10, launches: int = 50) -> None:
+    import irdu_amd
+    irdu_amd.load_native()
+    from irdu_amd import _native, kernels, training
+    dev = torch.device("cuda:0")
+    log = logging.getLogger("bench_data")
+    units = kernels.keep_units(keep)
+    stream = torch.cuda.current_stream().cuda_stream
+    tables = {"zero": (kernels.mask_weights(1), 0), "conv7": (kernels.mask_weights(7), 1), "conv15": (kernels.mask_weights(15), 1)}
+    tables = {k: (torch.from_numpy(w).to(dev), w.shape[0], fill) for k, (w, fill) in tables.items()}
+
+    def planar(pair):        # what Trainer.step does with a host batch
+        return [t.to(dev, non_blocking=True).permute(0, 3, 1, 2).contiguous() for t in pair]
+
+    shared: dict = {}
+    rs = np.random.RandomState(3)
+    with tempfile.TemporaryDirectory() as folder:
+        csv_path = write_pictures(folder, images, side)
+        for batch, size in SHAPES:
+            n = (steps + warmup + 1) * batch
+            ds = training.RandomMaskInpainting(csv_path=csv_path, root_folder=folder, keep=keep, fill="conv", fill_side=7,
+                                               use_data_aug=True, patch_size=(size, size), max_num_patchs=n, logger=log)
+            host = torch.utils.data.DataLoader(ds, sampler=training.ResumeableSampler(ds, batch), batch_size=batch,
+                                               num_workers=workers)
+            host_s = timed(host, warmup, steps, planar)
+            del host
+
+            def passes():
+                while True:
+                    yield from training.DevicePatchLoader(ds, training.ResumeableSampler(ds, batch), batch, device=dev,
+                                                          shared=shared)
+            dev_s = timed(passes(), warmup, device_steps, lambda pair: pair)
+            # the kernels alone, on one uploaded table and preallocated outputs: the three fills and grr_patch_batch
+            loader = training.DevicePatchLoader(ds, training.ResumeableSampler(ds, batch), batch, device=dev, shared=shared)
+            pack = loader.prepare()
+            hw, n_img = loader.source.hw, loader.source.n_img
+            img = np.arange(batch) % n_img
+            rows = np.stack([img, rs.randint(0, hw[img, 0] - size), rs.randint(0, hw[img, 1] - size), np.arange(batch) % 8], 1)
+            table = torch.from_numpy(rows.astype(np.int32)).to(dev)
+            ids = torch.arange(batch, dtype=torch.int64, device=dev)
+            keeps = torch.full((batch,), units, dtype=torch.int32, device=dev)
+            sigma = torch.full((batch,), 25.0 / 255.0, dtype=torch.float32, device=dev)
+            out = [torch.empty((batch, 3, size, size), dtype=torch.float32, device=dev) for _ in range(2)]
+            mask = torch.empty((batch, 1, size, size), dtype=torch.float32, device=dev)
+
+            def masked(name):
+                w, k, fill = tables[name]
+                return lambda: _native.call(
+                    "grr_patch_mask_batch", pack.arena.data_ptr(), pack.arena.numel(), 3, pack.table.data_ptr(), n_img,
+                    table.data_ptr(), ids.data_ptr(), keeps.data_ptr(), batch, 2204, size, size, w.data_ptr(), k, k, fill, 128,
+                    out[0].data_ptr(), out[1].data_ptr(), mask.data_ptr(), stream)
+            calls = {"patch_mask_batch_" + name: masked(name) for name in tables}
+            calls["patch_batch"] = lambda: _native.call(
+                "grr_patch_batch", pack.arena.data_ptr(), pack.arena.numel(), 3, pack.table.data_ptr(), n_img, table.data_ptr(),
+                ids.data_ptr(), sigma.data_ptr(), batch, 2204, size, size, out[0].data_ptr(), out[1].data_ptr(), stream)
+            us = {k: [] for k in calls}
+            for r in range(rounds + 1):                      # round 0 warms all up
+                for name, call in calls.items():
+                    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    start.record()
+                    for _ in range(launches):
+                        call()
+                    end.record()
+                    torch.cuda.synchronize()
+                    if r:
+                        us[name].append(start.elapsed_time(end) * 1e3 / launches)
+            line = {"bench": "inpaint", "keep": keep, "keep_units": units, "batch": batch, "size": size, "steps": steps,
+                    "device_steps": device_steps, "workers": workers, "images": images,
+                    "arena_mb": round(pack.arena.numel() / 2 ** 20, 1), "rounds": rounds, "launches": launches,
+                    "tile": list(kernels.MASK_TILE), "host_ms_per_batch": round(host_s * 1e3, 3),
+                    "host_batches_per_s": round(1.0 / host_s, 2), "device_ms_per_batch": round(dev_s * 1e3, 4),
+                    "device_batches_per_s": round(1.0 / dev_s, 1), "device_over_host": round(host_s / dev_s, 1)}
+            for name, v in us.items():
+                med = float(np.median(v))
+                line[name] = {"median_us": round(med, 2), "min_us": round(min(v), 2), "max_us": round(max(v), 2),
+                              "batches_per_s": round(1e6 / med, 1)}
+            base = line["patch_batch"]["median_us"]
+            line["ratio_to_patch_batch"] = {name: round(line["patch_mask_batch_" + name]["median_us"] / base, 2) for name in tables}
+            print(json.dumps(line), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     # the DataLoader's workers hold up to 2 batches each in flight when the clock starts: enough timed batches
@@ -514,7 +604,13 @@ def main():
     ap.add_argument("--raw-noise", type=str, default=None, metavar="SHOT,READ",
                     help="only time grr_patch_raw_batch (noise on the mosaic, before the fill) against grr_patch_pair_batch "
                          "with sigma over a pre-filled demosaic arena, at the curriculum's shapes")
+    ap.add_argument("--inpaint", type=float, default=None, metavar="KEEP",
+                    help="only time grr_patch_mask_batch (zero fill, conv at sides 7 and 15) with this known share against "
+                         "grr_patch_batch on the same arena, and RandomMaskInpainting on both loader paths, at the "
+                         "curriculum's shapes")
     args = ap.parse_args()
+    if args.inpaint is not None:
+        return inpaint(args.inpaint, args.images, args.side, args.steps, args.warmup, args.device_steps, args.workers)
     if args.raw_noise is not None:
         return raw_noise(args.raw_noise, args.images, args.side)
     if args.blur is not None:

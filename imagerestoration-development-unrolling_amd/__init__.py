@@ -58,5 +58,7 @@ from .training import GaussianMotionDeblurring  # noqa: F401  (deblurring pairs 
 from .training import BlurKernel, blur_degrade_u8, box_kernel, gaussian_kernel, motion_kernel  # noqa: F401
 from .training import parse_blur_spec, quantise_blur_kernel  # noqa: F401
 from .restore import blur_u8, evaluate_deblur  # noqa: F401
+from .training import RandomMaskInpainting  # noqa: F401  (inpainting pairs: a drawn mask and its fill, per batch)
+from .restore import evaluate_inpaint, mask_fill_u8, psnr_missing_u8  # noqa: F401
 
 __version__ = "0.1.0"

@@ -214,6 +214,11 @@ SIGNATURES = {
     "grr_u8_blur_supported": [I, I, I],
     "grr_u8_blur": [P, I, I, I, P, P, I, I, I, P],
     "grr_u8_blur_images": [P, L, P, I, I, I, I, P, P, P, I, P, I, P],
+    # inpainting: a drawn or given mask and the initial fill of the missing pixels (inpaint_ops.hip)
+    "grr_patch_mask_batch_supported": [I, I, L, I, I, I],
+    "grr_patch_mask_batch": [P, L, I, P, I, P, P, P, I, ctypes.c_uint64, I, I, P, I, I, I, I, P, P, P, P],
+    "grr_u8_mask_fill_supported": [I, I, I],
+    "grr_u8_mask_fill": [P, P, I, I, I, I, ctypes.c_uint64, L, P, I, I, I, I, P, P, P],
 }
 _RESTYPES = {"grr_version": c_int, "grr_last_error": ctypes.c_char_p, "grr_lnb_workspace_bytes": c_int64,
              "grr_conv1x1_workspace_bytes": c_int64, "grr_wgrad_workspace_bytes": c_int64,

@@ -3081,3 +3081,174 @@ def u8_blur_images(pack, kernels, kernel_of, boundary="wrap"):
                 of.data_ptr() + at * 4, boundary, _stream(dev))
     return ImagePack(arena, pack.table, tuple(tuple(int(v) for v in row) for row in pack.host_table), c,
                      tuple(getattr(pack, "kinds", ())))
+
+
+# ---------------------------------------------------------------------------
+# Inpainting (csrc/inpaint_ops.hip; include/grr.h has the definition): a Bernoulli mask that is a function of (seed,
+# sample id, window element), or a given one, and the initial fill of the missing pixels -- zero, or a normalised
+# convolution of the known ones under a uint8 weight table -- made per batch, inside the patch kernel.
+MASK_TILE = (16, 64)          # a workgroup's rows and columns of the patch, in source orientation
+MASK_FILLS = ("zero", "conv")                             # the index is the code
+MASK_HALO = 7                 # GRR_MASK_HALO
+MAX_MASK_SIDE = 15            # GRR_MASK_MAX_SIDE
+MASK_ONE = 1 << 24            # GRR_MASK_ONE
+
+
+def patch_mask_batch_ok(c: int, n_img: int, arena_elems: int, n: int, ph: int, pw: int) -> bool:
+    """grr_patch_mask_batch_supported in plain Python (tests/test_inpaint_abi.py checks the two agree): what
+    patch_batch takes, and a window (ph + 14)(pw + 14) < 2^31."""
+    return patch_batch_ok(c, n_img, arena_elems, n, ph, pw) and (ph + 14) * (pw + 14) < (1 << 31)
+
+
+def mask_fill_ok(c: int, h: int, w: int) -> bool:
+    """grr_u8_mask_fill_supported in plain Python: 1..4 channels, sides >= 1, C H W < 2^31 and (H + 14)(W + 14) < 2^31."""
+    return image_io_ok(c, h, w) and (h + 14) * (w + 14) < (1 << 31)
+
+
+def keep_units(fraction) -> int:
+    """The known share ``fraction`` of [0, 1] in the kernel's units of 2^-24: round(fraction 2^24)."""
+    if isinstance(fraction, (bool, np.bool_)) or not isinstance(fraction, (int, float, np.integer, np.floating)) \
+            or not (np.isfinite(fraction) and 0 <= fraction <= 1):
+        raise ValueError(f"keep_units: the known share is a number of 0..1, got {fraction!r}")
+    return int(round(float(fraction) * MASK_ONE))
+
+
+def mask_weights(side, sigma=None) -> np.ndarray:
+    """The uint8 weight table of the conv fill, ``side`` x ``side`` (or (kh, kw)), odd and at most 15:
+    round(255 exp(-d^2 / (2 sigma^2))) with d the distance to the centre, made in float64 on the host; ``sigma`` None
+    gives a flat table of 255.  The table is data handed to the kernel: the fill itself is exact integers."""
+    sides = tuple(side) if isinstance(side, (list, tuple)) else (side, side)
+    if len(sides) != 2 or any(isinstance(s, (bool, np.bool_)) or not isinstance(s, (int, np.integer)) or s < 1
+                              or s > MAX_MASK_SIDE or s % 2 == 0 for s in sides):
+        raise ValueError(f"mask_weights: a weight table's sides are odd and lie in 1..{MAX_MASK_SIDE}, got {side!r}")
+    kh, kw = int(sides[0]), int(sides[1])
+    if sigma is None:
+        return np.full((kh, kw), 255, np.uint8)
+    if isinstance(sigma, (bool, np.bool_)) or not isinstance(sigma, (int, float, np.integer, np.floating)) \
+            or not (np.isfinite(sigma) and sigma > 0):
+        raise ValueError(f"mask_weights: sigma is a positive number or None, got {sigma!r}")
+    y, x = np.meshgrid(np.arange(kh, dtype=np.float64) - kh // 2, np.arange(kw, dtype=np.float64) - kw // 2, indexing="ij")
+    return np.round(255.0 * np.exp(-(y * y + x * x) / (2.0 * float(sigma) ** 2))).astype(np.uint8)
+
+
+def _check_mask_fill(name: str, fill) -> int:
+    """The code of a mask fill given by name or code; ValueError otherwise."""
+    return _check_code(name, "fill", MASK_FILLS, fill)
+
+
+def _check_mask_table(name: str, weights) -> np.ndarray:
+    """A conv fill's weight table as a contiguous uint8 [kh, kw] host array; ValueError otherwise."""
+    w = weights
+    if isinstance(w, Tensor):
+        if w.is_cuda:
+            raise ValueError(f"{name}: a weight table is a host table; it is checked before it is sent to the device")
+        w = w.numpy()
+    w = np.asarray(w)
+    if w.ndim != 2 or w.dtype != np.uint8 or w.size == 0:
+        raise ValueError(f"{name}: a weight table is a 2-D uint8 table, got {w.dtype} {w.shape}")
+    if any(s % 2 == 0 or s > MAX_MASK_SIDE for s in w.shape):
+        raise ValueError(f"{name}: a weight table's sides are odd and at most {MAX_MASK_SIDE}, got {w.shape}")
+    return np.ascontiguousarray(w)
+
+
+def _check_hole(name: str, hole) -> int:
+    if isinstance(hole, (bool, np.bool_)) or not isinstance(hole, (int, np.integer)) or not 0 <= hole <= 255:
+        raise ValueError(f"{name}: the hole is an integer of 0..255, got {hole!r}")
+    return int(hole)
+
+
+def _mask_call_args(name: str, weights, fill, hole) -> Tuple[np.ndarray, int, int]:
+    """(table, fill code, hole) of a call, checked; ``weights`` None: the flat 7 x 7 table (the zero fill reads none)."""
+    fill, hole = _check_mask_fill(name, fill), _check_hole(name, hole)
+    table = _check_mask_table(name, mask_weights(7) if weights is None else weights)
+    return table, fill, hole
+
+
+def patch_mask_batch(pack, rows, sample_ids, keep, seed: int, ph: int, pw: int, weights=None, fill="conv",
+                     hole: int = 128, with_mask: bool = True):
+    """(target, input, mask) of a uint8 ``pack`` (or the PatchSource that patch_source made of it): sample s is
+    patch_batch's clean patch of rows[s] as target; input is the same patch with a pixel known with probability
+    keep[s] / 2^24 -- a bit that is a function of (seed, sample_ids[s], window element) alone -- and the missing ones
+    filled by ``fill``: "zero", or "conv", the normalised convolution of the known pixels under the uint8 table
+    ``weights`` (odd sides up to 15; None: flat 7 x 7), ``hole`` where no known pixel lies under the table
+    (include/grr.h).  target and input are float32 [n, C, ph, pw]; mask is float32 [n, 1, ph, pw], 1 known and 0
+    missing, or None without ``with_mask``.
+    rows [n, 4], sample_ids [n] and keep [n] (integers, units of 2^-24; keep_units makes one from a fraction) are host
+    data, checked here as patch_batch checks its own and uploaded; device tensors (int32 [n, 4], int64 [n], int32 [n],
+    contiguous, on the arena's device) are taken as they are: the kernel clamps what it reads from them."""
+    name = "patch_mask_batch"
+    table, fill, hole = _mask_call_args(name, weights, fill, hole)
+    src = pack if isinstance(pack, PatchSource) else patch_source(pack)
+    arena = src.pack.arena
+    on_device = isinstance(rows, Tensor) and rows.is_cuda
+    n = int(rows.shape[0]) if on_device and rows.dim() == 2 else (len(rows) if hasattr(rows, "__len__") else 0)
+    if isinstance(ph, int) and isinstance(pw, int) and min(ph, pw) >= 1 and (ph + 14) * (pw + 14) >= (1 << 31):
+        raise ValueError(f"{name}: the window ({ph} + 14) x ({pw} + 14) must have fewer than 2^31 elements")
+    if on_device:
+        if not isinstance(keep, Tensor) or keep.dtype != torch.int32 or tuple(keep.shape) != (n,) \
+                or keep.device != arena.device or not keep.is_contiguous():
+            raise ValueError(f"{name}: a device keep list is int32 [n], contiguous and on the arena's device")
+    else:
+        keep = np.asarray(keep)
+        if keep.shape != (n,) or keep.dtype.kind not in "iu" or (keep.astype(np.int64) < 0).any() \
+                or (keep.astype(np.int64) > MASK_ONE).any():
+            raise ValueError(f"{name}: keep is integers of 0..2^24, one per row ({n})")
+    tab, ids, _ = _patch_tables(name, arena, src.n_img, src.c, src.hw, rows, sample_ids, None, seed, ph, pw, no_sigma=True)
+    if not on_device:
+        keep = torch.from_numpy(np.ascontiguousarray(keep.astype(np.int32))).to(arena.device)
+    wd = torch.from_numpy(table).to(arena.device)
+    return _patch_mask_batch(src, tab, ids, keep, seed, ph, pw, wd, table.shape, fill, hole, bool(with_mask))
+
+
+def _patch_mask_batch(src: PatchSource, table: Tensor, ids: Tensor, keep: Tensor, seed: int, ph: int, pw: int,
+                      weights: Tensor, sides, fill: int, hole: int, with_mask: bool):
+    """patch_mask_batch after its checks, on device tables; ``weights``: the uint8 device table of ``sides``."""
+    arena, n, c = src.pack.arena, table.shape[0], src.c
+    target = torch.empty((n, c, ph, pw), dtype=torch.float32, device=arena.device)
+    inp = torch.empty_like(target)
+    mask = torch.empty((n, 1, ph, pw), dtype=torch.float32, device=arena.device) if with_mask else None
+    _launch("patch_mask_batch", target.numel() * 8 + (mask.numel() * 4 if with_mask else 0) + n * c * (ph + 14) * (pw + 14),
+            "grr_patch_mask_batch", arena.data_ptr(), arena.numel(), c, src.pack.table.data_ptr(), src.n_img,
+            table.data_ptr(), ids.data_ptr(), keep.data_ptr(), n, int(seed), ph, pw, weights.data_ptr(), int(sides[0]),
+            int(sides[1]), fill, hole, target.data_ptr(), inp.data_ptr(), mask.data_ptr() if with_mask else None,
+            _stream(arena.device))
+    return target, inp, mask
+
+
+def u8_mask_fill(img: Tensor, mask: Optional[Tensor] = None, keep: int = MASK_ONE, weights=None, fill="conv",
+                 hole: int = 128, seed: int = 2204, sample_id: int = 0) -> Tuple[Tensor, Tensor]:
+    """(filled, mask_out) of a uint8 H x W x C device picture: the missing pixels filled as patch_mask_batch fills
+    them, one launch.  ``mask``: a uint8 H x W device tensor, nonzero known (read by the mirror outside the picture),
+    or None: the mask of (seed, sample_id) is drawn with the share ``keep`` (units of 2^-24), patch_mask_batch's mask
+    of the whole picture for the same id.  mask_out (uint8 H x W) carries ``mask``'s nonzero values through (1 for a
+    drawn known pixel), is 2 where this call filled a pixel from at least one known one and 0 where a hole is left:
+    feeding both results back in is a second pass, which grows the filled region by one table radius.  A
+    non-contiguous picture or mask is copied first."""
+    name = "u8_mask_fill"
+    table, fill, hole = _mask_call_args(name, weights, fill, hole)
+    if isinstance(keep, (bool, np.bool_)) or not isinstance(keep, (int, np.integer)) or not 0 <= keep <= MASK_ONE:
+        raise ValueError(f"{name}: keep is an integer of 0..2^24, got {keep!r}")
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < (1 << 64):
+        raise ValueError(f"{name}: seed must fit 64 bits, got {seed!r}")
+    if isinstance(sample_id, bool) or not isinstance(sample_id, (int, np.integer)) or not -(1 << 63) <= sample_id < (1 << 63):
+        raise ValueError(f"{name}: sample_id is a 64-bit integer, got {sample_id!r}")
+    if isinstance(img, Tensor) and img.dtype != torch.uint8:
+        raise ValueError(f"{name}: the image must be uint8, got {img.dtype}")
+    if mask is not None and (not isinstance(mask, Tensor) or mask.dtype != torch.uint8 or mask.dim() != 2
+                             or not isinstance(img, Tensor) or tuple(mask.shape) != tuple(img.shape[:2])):
+        raise ValueError(f"{name}: a mask is a uint8 H x W tensor of the picture's sides, got "
+                         f"{getattr(mask, 'dtype', None)} {tuple(getattr(mask, 'shape', ()))}")
+    h, w, c = _check_image(name, img)
+    if mask is not None and mask.device != img.device:
+        raise ValueError(f"{name}: the mask must be on the picture's device")
+    if not mask_fill_ok(c, h, w):
+        raise ValueError(f"{name}: needs H W C < 2^31 and (H + 14)(W + 14) < 2^31, got {tuple(img.shape)}")
+    img = img.contiguous()
+    mask = None if mask is None else mask.contiguous()
+    out = torch.empty_like(img)
+    mask_out = torch.empty((h, w), dtype=torch.uint8, device=img.device)
+    wd = torch.from_numpy(table).to(img.device)
+    _launch("u8_mask_fill", 2 * img.numel() + 2 * h * w, "grr_u8_mask_fill", img.data_ptr(),
+            None if mask is None else mask.data_ptr(), h, w, c, int(keep), int(seed), int(sample_id), wd.data_ptr(),
+            table.shape[0], table.shape[1], fill, hole, out.data_ptr(), mask_out.data_ptr(), _stream(img.device))
+    return out, mask_out

@@ -73,7 +73,7 @@ from __future__ import annotations
 import math
 from dataclasses import dataclass
 from functools import partial
-from typing import Callable, List, NamedTuple, Sequence, Tuple
+from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -575,12 +575,14 @@ def _check_metric_shape(who: str, what: str, shape, metrics) -> None:
         _check_psnrb_shape(who, what, shape)
 
 
-def _evaluate_args(who: str, model: Callable, ensemble, metrics, tiling_args: dict):
-    """(modes, metrics, device, tile, halo, micro_batch) of an evaluate call, checked; tiling_args is emptied."""
+def _evaluate_args(who: str, model: Callable, ensemble, metrics, tiling_args: dict, extra: Tuple[str, ...] = ()):
+    """(modes, metrics, device, tile, halo, micro_batch) of an evaluate call, checked; tiling_args is emptied.
+    ``extra``: metric names the caller scores itself, beside the shared ones."""
     modes = _ensemble_modes(who, ensemble)
     metrics = (metrics,) if isinstance(metrics, str) else tuple(metrics)
-    if not metrics or any(m not in METRICS + BLOCKING_METRICS for m in metrics) or len(set(metrics)) != len(metrics):
-        raise ValueError(f"{who}: metrics are distinct names of {METRICS + BLOCKING_METRICS}, got {metrics!r}")
+    names = METRICS + BLOCKING_METRICS + tuple(extra)
+    if not metrics or any(m not in names for m in metrics) or len(set(metrics)) != len(metrics):
+        raise ValueError(f"{who}: metrics are distinct names of {names}, got {metrics!r}")
     device = tiling_args.pop("device", None) or _model_device(model)
     tile, halo = tiling_args.pop("tile", TILE), tiling_args.pop("halo", HALO)
     micro_batch = tiling_args.pop("micro_batch", MICRO_BATCH)
@@ -977,6 +979,177 @@ def evaluate_jdd(model: Callable, images, pattern="rggb", fill="malvar", shot: f
     modes, metrics, device, tile, halo, micro_batch = _evaluate_args("evaluate_jdd", model, ensemble, metrics, tiling_args)
     return _evaluate_degraded(_jdd_protocol("evaluate_jdd", pattern, fill, shot, read, bits, clip, seed, shave), model,
                               images, factor, modes, metrics, device, tile, halo, micro_batch)
+
+
+INPAINT_METRICS = ("psnr_missing",)      # beside METRICS: the PSNR over the missing pixels alone
+
+
+def _check_passes(who: str, passes) -> int:
+    if isinstance(passes, (bool, np.bool_)) or not isinstance(passes, (int, np.integer)) or passes < 1:
+        raise ValueError(f"{who}: passes is a positive integer, got {passes!r}")
+    return int(passes)
+
+
+def _mask_fill_args(who: str, fill, weights, hole, seed, sample_id, passes):
+    """(weight table, fill code, hole, seed, sample id, passes) of a mask fill, checked in this order."""
+    fill = kernels._check_mask_fill(who, fill)
+    table = kernels._check_mask_table(who, kernels.mask_weights(7) if weights is None else weights)
+    hole = kernels._check_hole(who, hole)
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 2 ** 64:
+        raise ValueError(f"{who}: seed is an integer of 0..2^64 - 1, got {seed!r}")
+    if isinstance(sample_id, bool) or not isinstance(sample_id, (int, np.integer)) or not -2 ** 63 <= sample_id < 2 ** 63:
+        raise ValueError(f"{who}: sample_id is a 64-bit integer, got {sample_id!r}")
+    return table, fill, hole, int(seed), int(sample_id), _check_passes(who, passes)
+
+
+def _mask_fill_device(t: torch.Tensor, mask: Optional[torch.Tensor], units: int, table, fill: int, hole: int, seed: int,
+                      sample_id: int, passes: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(filled, known) on the device: kernels.u8_mask_fill ``passes`` times, each pass taking the last one's picture
+    and mask; ``known`` is the uint8 0 / 1 plane of what was known before the first."""
+    out, code = kernels.u8_mask_fill(t, mask, units, table, fill, hole, seed, sample_id)
+    known = ((code == 1) if mask is None else (mask != 0)).to(torch.uint8)
+    for _ in range(passes - 1):
+        out, code = kernels.u8_mask_fill(out, code, 0, table, fill, hole, seed, sample_id)
+    return out, known
+
+
+def mask_fill_u8(a, mask=None, keep=None, fill="conv", weights=None, hole: int = 128, seed: int = 2204,
+                 sample_id: int = 0, passes: int = 1):
+    """(filled, mask) of the uint8 H x W x C picture ``a`` (numpy array or tensor, host or device), both of its kind, on
+    the GPU (kernels.u8_mask_fill; include/grr.h has the definition): the missing pixels of ``a`` filled for a
+    restoration model.  Exactly one of ``mask`` and ``keep`` is given.  ``mask``: H x W, nonzero (or True) where the
+    pixel is known -- scratches, text, a mask file.  ``keep``: the known share of 0..1; the mask is then drawn, a
+    function of (seed, sample_id, pixel) alone.  ``fill``: "zero", or "conv", the normalised convolution of the known
+    pixels under the uint8 table ``weights`` (kernels.mask_weights; None: flat 7 x 7), ``hole`` where no known pixel
+    lies under the table.  ``passes``: each further pass takes the filled pixels as known and so grows the filled
+    region by the table's radius.  The mask returned is the uint8 0 / 1 plane of the pixels known at the start."""
+    who = "mask_fill_u8"
+    if (mask is None) == (keep is None):
+        raise ValueError(f"{who}: exactly one of mask and keep is given")
+    table, fill, hole, seed, sample_id, passes = _mask_fill_args(who, fill, weights, hole, seed, sample_id, passes)
+    units = 0
+    if keep is not None:
+        try:
+            units = kernels.keep_units(keep)
+        except ValueError:
+            raise ValueError(f"{who}: keep is the known share, a number of 0..1, got {keep!r}") from None
+    try:
+        t, kind = _checked_image(a)
+    except ValueError as e:
+        raise ValueError(f"{who}: {e}") from None
+    if t.dtype != torch.uint8:
+        raise ValueError(f"{who}: expected a uint8 picture, got {t.dtype}")
+    m = None
+    if mask is not None:
+        m = torch.from_numpy(np.ascontiguousarray(mask)) if isinstance(mask, np.ndarray) else mask
+        if not isinstance(m, torch.Tensor) or m.dtype not in (torch.uint8, torch.bool) or tuple(m.shape) != tuple(t.shape[:2]):
+            raise ValueError(f"{who}: a mask is uint8 or bool H x W of the picture's sides {tuple(t.shape[:2])}, got "
+                             f"{getattr(m, 'dtype', type(m).__name__)} {tuple(getattr(m, 'shape', ()))}")
+        m = (m != 0).to(torch.uint8)
+    dev = _to_device(t, None)
+    out, known = _mask_fill_device(dev, None if m is None else _to_device(m, dev.device), units, table, fill, hole, seed,
+                                   sample_id, passes)
+    if kind == "numpy":
+        return out.cpu().numpy(), known.cpu().numpy()
+    return (out.cpu(), known.cpu()) if kind == "cpu" else (out, known)
+
+
+def _psnr_missing(est: torch.Tensor, ref: torch.Tensor, known: torch.Tensor) -> float:
+    """10 log10(255^2 n / SSE) over the n bytes of the missing pixels of two uint8 H x W x C device pictures: the exact
+    integer SSE (kernels.u8_sse) of the estimate with the known pixels put back, and n = C times the integer count of
+    the zeros of ``known``; inf where nothing is missing."""
+    missing = int((known == 0).sum().item())
+    if missing == 0:
+        return float("inf")
+    merged = torch.where(known[:, :, None] != 0, ref, est).contiguous()
+    return _psnr(kernels.u8_sse(merged, ref.contiguous()), missing * int(ref.shape[2]))
+
+
+def psnr_missing_u8(est, ref, known) -> float:
+    """PSNR of the uint8 H x W x C picture ``est`` against ``ref`` over the missing pixels alone -- those where the
+    H x W plane ``known`` is zero: 10 log10(255^2 n / SSE) with the SSE and the n bytes of these pixels, exact integers
+    both; inf where nothing is missing or the pixels agree."""
+    who = "psnr_missing_u8"
+    ta, tb = _u8_pair(who, est, ref)
+    k = torch.from_numpy(np.ascontiguousarray(known)) if isinstance(known, np.ndarray) else known
+    if ta.dim() != 3 or not isinstance(k, torch.Tensor) or tuple(k.shape) != tuple(ta.shape[:2]):
+        raise ValueError(f"{who}: expected H x W x C pictures and an H x W plane of the known pixels, got "
+                         f"{tuple(ta.shape)} and {tuple(getattr(k, 'shape', ()))}")
+    return _psnr_missing(ta, tb, k.to(ta.device))
+
+
+def _inpaint_table(who: str, fill_side, fill_sigma):
+    try:
+        return kernels.mask_weights(fill_side, fill_sigma)
+    except ValueError as e:
+        raise ValueError(f"{who}: {str(e).split(': ', 1)[1]}") from None
+
+
+def evaluate_inpaint(model: Callable, images, keep, fill="conv", fill_side: int = 7, fill_sigma: Optional[float] = None,
+                     hole: int = 128, seed: int = 2204, passes: int = 1, keep_known: bool = True, shave: int = 0,
+                     factor: int = 16, ensemble=1, metrics=("psnr",), **tiling_args) -> dict:
+    """Score ``model`` on inpainting (the "x % of the pixels missing" tables) over clean uint8 H x W x C pictures
+    (numpy arrays or tensors, host or device).  Per picture i: a pixel is known with probability ``keep`` -- the mask
+    is drawn on the device with sample id i under ``seed`` -- the missing ones are filled (kernels.u8_mask_fill:
+    ``fill`` "zero" or "conv" under kernels.mask_weights(fill_side, fill_sigma), ``hole``, ``passes``), the filled
+    picture is restored as ``restore_image`` does, with ``keep_known`` the known pixels are put back into the result,
+    ``shave`` pixels are cut from each side, and the result is scored against the clean picture with the exact-integer
+    kernels.  Metrics: those of the other protocols and "psnr_missing", the PSNR over the missing pixels alone (inf
+    where none is missing).  Returns {metric: (mean, per-image values)} as evaluate_pairs does.  Nothing is drawn on
+    the host: a picture's mask is a function of (seed, i).  tiling_args: tile, halo, micro_batch, device;
+    ``ensemble`` as in restore_image.
+
+    Everything is checked before any launch: the shared arguments, then keep, the fill, the table, the hole, the seed,
+    passes, keep_known, the shave, uint8 pictures, a picture smaller than the shave leaves, and what the metrics need
+    of the shaved picture."""
+    who = "evaluate_inpaint"
+    modes, metrics, device, tile, halo, micro_batch = _evaluate_args(who, model, ensemble, metrics, tiling_args,
+                                                                     INPAINT_METRICS)
+    try:
+        units = kernels.keep_units(keep)
+    except ValueError:
+        raise ValueError(f"{who}: keep is the known share, a number of 0..1, got {keep!r}") from None
+    fill_code = kernels._check_mask_fill(who, fill)
+    table, fill_code, hole, seed, _, passes = _mask_fill_args(who, fill_code, _inpaint_table(who, fill_side, fill_sigma),
+                                                              hole, seed, 0, passes)
+    if not isinstance(keep_known, (bool, np.bool_)):
+        raise ValueError(f"{who}: keep_known is True or False, got {keep_known!r}")
+    shave = _check_shave(who, shave)
+    if len(images) < 1:
+        raise ValueError(f"{who}: no images")
+    shared = tuple(m for m in metrics if m not in INPAINT_METRICS)
+    cleans = []
+    for i in range(len(images)):
+        try:
+            t, _ = _checked_image(images[i])
+        except ValueError as e:
+            raise ValueError(f"{who}: image {i}: {e}") from None
+        if t.dtype != torch.uint8:
+            raise ValueError(f"{who}: image {i} is {t.dtype}; the mask is defined on uint8 pictures")
+        h, w = int(t.shape[0]), int(t.shape[1])
+        if not kernels.mask_fill_ok(int(t.shape[2]), h, w):
+            raise ValueError(f"{who}: image {i} is {tuple(t.shape)}; the fill takes pictures of 1..4 channels")
+        if min(h, w) <= 2 * shave:
+            raise ValueError(f"{who}: image {i} is {tuple(t.shape)}: nothing is left after a shave of {shave}")
+        _check_metric_shape(who, f"image {i} after the shave", (h - 2 * shave, w - 2 * shave, t.shape[2]), shared)
+        plan(h, w, factor, tile, halo)                          # raises what the restoration would
+        cleans.append(t)
+    if device is None:
+        device = next((t.device for t in cleans if t.is_cuda), None)
+    cut = (lambda a: a[shave:a.shape[0] - shave, shave:a.shape[1] - shave].contiguous()) if shave else (lambda a: a)
+    values = {m: [] for m in metrics}
+    for i, t in enumerate(cleans):
+        clean = _to_device(t, device)
+        filled, known = _mask_fill_device(clean, None, units, table, fill_code, hole, seed, i, passes)
+        restored = _restore_device(model, filled, None, factor, tile, halo, micro_batch, True, modes)
+        if restored.shape != clean.shape:
+            raise ValueError(f"{who}: the model returns {restored.shape[2]} channel(s) for {clean.shape[2]}; no score")
+        if keep_known:      # integer ATen ops: exact and order-free
+            restored = torch.where(known[:, :, None] != 0, clean, restored)
+        restored, clean, known = cut(restored.contiguous()), cut(clean), cut(known)
+        for m in metrics:
+            values[m].append(_psnr_missing(restored, clean, known) if m == "psnr_missing" else _SCORE[m](restored, clean))
+    return _means(values, metrics)
 
 
 def _blur_kernel(who: str, kernel):

@@ -948,6 +948,101 @@ class NoisyBayerDemosaicking(ImageSuperResolution):
         return torch.from_numpy(data_augmentation(inp, mode)), torch.from_numpy(data_augmentation(tgt, mode))
 
 
+MASK_FILLS = ("zero", "conv")                           # kernels.MASK_FILLS: the index is the code
+MASK_HALO = 7                 # GRR_MASK_HALO
+
+
+def _mask_sym(n_from: int, count: int, n: int) -> np.ndarray:
+    """sym(r, n) of r = n_from .. n_from + count - 1: the edge-repeating mirror for any index."""
+    t = np.arange(n_from, n_from + count) % (2 * n)
+    return np.where(t < n, t, 2 * n - 1 - t)
+
+
+def mask_fill_patch(a: np.ndarray, row: int, col: int, ph: int, pw: int, known: np.ndarray, weights, fill="conv",
+                    hole: int = 128) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(target, input, mask) of one inpainting sample before the augmentation (include/grr.h has the definition):
+    uint8 ph x pw x C twice and the bool ph x pw plane of the known pixels.  ``a``: the uint8 H x W x C picture;
+    ``known``: the bool (ph + 14) x (pw + 14) bits of the window, whose position (wy, wx) is picture pixel
+    (sym(row + wy - 7), sym(col + wx - 7)); ``weights``: the uint8 table of the conv fill.  A known pixel passes
+    through; a missing one is 0 under the zero fill and (2 num + den) / (2 den) under conv -- den and num the sums of
+    w k and w k v under the table -- or ``hole`` where den is 0.  With kernels.patch_mask_batch's bits it gives the
+    kernel's bytes; the host DataLoader path draws its own."""
+    who = "mask_fill_patch"
+    fill = _bayer_code(who, "fill", MASK_FILLS, fill)
+    known = np.asarray(known, dtype=bool)
+    if known.shape != (ph + 2 * MASK_HALO, pw + 2 * MASK_HALO):
+        raise ValueError(f"{who}: the known bits are ({ph} + 14) x ({pw} + 14), got {known.shape}")
+    win = a[np.ix_(_mask_sym(row - MASK_HALO, ph + 2 * MASK_HALO, a.shape[0]),
+                   _mask_sym(col - MASK_HALO, pw + 2 * MASK_HALO, a.shape[1]))]
+    core = (slice(MASK_HALO, MASK_HALO + ph), slice(MASK_HALO, MASK_HALO + pw))
+    target, kc = win[core], known[core]
+    if fill == 0:
+        return target, target * kc[:, :, None].astype(np.uint8), kc
+    w = np.asarray(weights)
+    if w.ndim != 2 or w.dtype != np.uint8 or any(s % 2 == 0 or s > 2 * MASK_HALO + 1 for s in w.shape):
+        raise ValueError(f"{who}: a weight table is uint8 with odd sides of at most 15, got {w.dtype} {w.shape}")
+    k = known.astype(np.int64)
+    vk = win.astype(np.int64) * k[:, :, None]
+    den, num = np.zeros((ph, pw), np.int64), np.zeros(target.shape, np.int64)
+    for i in range(w.shape[0]):
+        for j in range(w.shape[1]):
+            ys, xs = MASK_HALO + i - w.shape[0] // 2, MASK_HALO + j - w.shape[1] // 2
+            den += int(w[i, j]) * k[ys:ys + ph, xs:xs + pw]
+            num += int(w[i, j]) * vk[ys:ys + ph, xs:xs + pw]
+    d = den[:, :, None]
+    filled = np.where(d > 0, (2 * num + d) // (2 * np.maximum(d, 1)), int(hole))
+    return target, np.where(kc[:, :, None], target, filled).astype(np.uint8), kc
+
+
+class RandomMaskInpainting(ImageSuperResolution):
+    """Inpainting pairs synthesised from clean files under ImageSuperResolution's csv, crop and patch plan: the input
+    of a sample is the patch with a random share of its pixels missing -- one Bernoulli bit per pixel, shared by the
+    channels -- and the missing ones filled (mask_fill_patch; include/grr.h has the definition); the target is the
+    clean patch.  ``keep``: the known share of 0..1, a number, or ``[levels, probabilities]`` drawn per sample.
+    ``fill``: "zero", or "conv", the normalised convolution of the known pixels under a ``fill_side`` x ``fill_side``
+    table (odd, at most 15) that is flat, or a Gaussian of ``fill_sigma`` (kernels.mask_weights), with ``hole`` (a
+    byte) where no known pixel lies under the table.  ``dist_mode`` must be "none": noise on top is not made.
+
+    The mask is fresh per sample and per epoch and lies under the fill, so there is no degraded arena: a
+    DevicePatchLoader holds the clean arena alone and a batch is one kernels.patch_mask_batch call.  ``__getitem__``
+    is the host path: the same formula in numpy with bits from the dataset's RandomState (after the mode and the
+    level draws: random_sample((h + 14, w + 14)) < keep); its mask is not the device's."""
+
+    DIST_MODES = ("none",)
+
+    def __init__(self, csv_path, keep=0.5, fill="conv", fill_side=7, fill_sigma=None, hole=128, dist_mode="none",
+                 lambda_noise=None, use_data_aug=False, patch_size=(64, 64), max_num_patchs=100000, root_folder="",
+                 logger=None, device=None, seed=2204, n_channels=3):
+        from . import kernels
+        who = "RandomMaskInpainting"
+        _check_levels(who, "keep", keep, 1.0)
+        if fill not in MASK_FILLS:
+            raise ValueError(f"{who}: fill is one of {MASK_FILLS}, got {fill!r}")
+        try:
+            self.weights = kernels.mask_weights(fill_side, fill_sigma)
+            hole = kernels._check_hole(who, hole)
+        except ValueError as e:
+            raise ValueError(f"{who}: {e}") from None
+        if dist_mode != "none":
+            raise ValueError(f"{who}: dist_mode must be 'none' (noise on top of the masked input is not made), got "
+                             f"{dist_mode!r}")
+        self.keep, self.fill, self.fill_side, self.fill_sigma, self.hole = keep, fill, fill_side, fill_sigma, hole
+        super().__init__(csv_path, dist_mode, lambda_noise, use_data_aug=use_data_aug, patch_size=patch_size,
+                         max_num_patchs=max_num_patchs, root_folder=root_folder, logger=logger, device=device,
+                         seed=seed, n_channels=n_channels)
+
+    def __getitem__(self, idx):
+        row, col, _, img_i = self.patchs_data[idx]
+        h, w = self.out_size()
+        rs = self.random_state
+        mode = rs.randint(0, 7) if self.use_data_augmentation else 0
+        keep = float(_draw_levels(rs, self.keep, 1)[0])
+        known = rs.random_sample((h + 2 * MASK_HALO, w + 2 * MASK_HALO)) < keep
+        tgt, inp, _ = mask_fill_patch(self.load_image(img_i), row, col, h, w, known, self.weights, self.fill, self.hole)
+        as_f32 = lambda p: data_augmentation(p, mode).astype(np.float32) / np.float32(255.0)      # noqa: E731
+        return torch.from_numpy(as_f32(inp)), torch.from_numpy(as_f32(tgt))
+
+
 BLUR_BOUNDARIES = ("wrap", "replicate", "reflect")      # kernels.BLUR_BOUNDARIES: the index is the code
 MAX_BLUR_SIDE = 31            # GRR_BLUR_MAX_SIDE
 BLUR_ONE = 65536              # GRR_BLUR_ONE
@@ -1233,7 +1328,13 @@ class DevicePatchLoader:
     A NoisyBayerDemosaicking dataset yields (input, target) from the clean arena alone: its degradation -- noise on the
     mosaic, then the fill -- is made per batch inside kernels.patch_raw_batch, so the device holds one arena (shared
     with any other stage over the same files) and the files' pattern codes.  After the draws above the epoch stream
-    gives the per-sample shot and then read levels where they are distributions (``epoch_noise``)."""
+    gives the per-sample shot and then read levels where they are distributions (``epoch_noise``).
+
+    A RandomMaskInpainting dataset goes the same way: the clean arena alone, and a batch is one
+    kernels.patch_mask_batch call that draws the mask and fills the missing pixels.  After the draws above the epoch
+    stream gives the per-sample known shares where ``keep`` is a distribution (``epoch_keep``, in units of 2^-24).  The
+    loader still yields (input, target); the mask of the last batch, float32 [B, 1, h, w] with 1 for a known pixel, is
+    kept as ``last_mask`` for a masked loss."""
     channels_first = True
     CHUNK_BYTES = 256 << 20      # decoded pictures staged on the host per transfer
 
@@ -1253,6 +1354,8 @@ class DevicePatchLoader:
         self.raw = isinstance(dataset, NoisyBayerDemosaicking)          # the degradation is made per batch
         self.source = None           # kernels.PatchSource (PatchPairSource if paired): the arena(s), checked once
         self.raw_source = None       # raw: kernels.PatchRawSource over source's pack
+        self.masked = isinstance(dataset, RandomMaskInpainting)         # so is the mask and its fill
+        self.last_mask = None        # masked: the mask of the last batch, float32 [B, 1, h, w]
         self._draws = (None, None, None, None)
 
     def __len__(self):
@@ -1339,12 +1442,20 @@ class DevicePatchLoader:
                 levels = np.full(n, ds.lambda_noise)
             sigma = (np.asarray(levels, dtype=np.float64) / 255.0).astype(np.float32)
             noise = raw_noise_pairs(_draw_levels(rs, ds.shot, n), _draw_levels(rs, ds.read, n)) if self.raw else None
+            if self.masked:          # the known shares in the kernel's units, in the noise pairs' place
+                noise = np.rint(_draw_levels(rs, ds.keep, n) * float(1 << 24)).astype(np.int64)
             self._draws = ((epoch, n), modes.astype(np.int64), sigma, noise)
         return self._draws[1], self._draws[2]
 
     def epoch_noise(self, epoch: int) -> np.ndarray:
         """The float32 [n, 2] noise pairs (a, b) of the epoch of a NoisyBayerDemosaicking dataset, in dataset order:
         drawn from the epoch's stream after epoch_draws' own draws, the shot levels first."""
+        self.epoch_draws(epoch)
+        return self._draws[3]
+
+    def epoch_keep(self, epoch: int) -> np.ndarray:
+        """The int64 [n] known shares of the epoch of a RandomMaskInpainting dataset in units of 2^-24, in dataset
+        order: round(keep 2^24), the levels drawn from the epoch's stream after epoch_draws' own draws."""
         self.epoch_draws(epoch)
         return self._draws[3]
 
@@ -1366,6 +1477,10 @@ class DevicePatchLoader:
                                                   None if ds.noise_free else self.epoch_noise(epoch)[pos], ds.seed, h, w,
                                                   ds.fill, ds.bits, ds.clip)
             return inp, target
+        if self.masked:
+            target, inp, self.last_mask = kernels.patch_mask_batch(self.source, rows, ids, self.epoch_keep(epoch)[pos],
+                                                                   ds.seed, h, w, ds.weights, ds.fill, ds.hole)
+            return inp, target
         if self.paired:
             target, inp = kernels.patch_pair_batch(self.source, rows, ids, None if ds.dist_mode == "none" else sigma[pos],
                                                    ds.seed, h, w)
@@ -1386,7 +1501,8 @@ class DevicePatchLoader:
 
 DATASETS = {c.__name__: c for c in (AddictiveGaussianNoiseImagePair, SyntheticNoisyPatches, ImageSuperResolution,
                                     PairedImageRestoration, BicubicSuperResolution, JpegArtifactRemoval,
-                                    BayerDemosaicking, NoisyBayerDemosaicking, GaussianMotionDeblurring)}
+                                    BayerDemosaicking, NoisyBayerDemosaicking, GaussianMotionDeblurring,
+                                    RandomMaskInpainting)}
 
 
 # ---------------------------------------------------------------------------
@@ -1641,6 +1757,28 @@ def validate_jdd(model: nn.Module, images, raw_noise=(0.0, 0.0), bayer="rggb", f
                               seed=seed, shave=shave, factor=factor, **tiling_args)
 
 
+VAL_INPAINT_METRICS = ("psnr", "psnr_y", "ssim", "psnr_missing")
+
+
+def validate_inpaint(model: nn.Module, images, inpaint_keep: float = 0.5, fill="conv", fill_side: int = 7,
+                     fill_sigma: Optional[float] = None, hole: int = 128, seed: int = 2204, passes: int = 1,
+                     shave: int = 0, factor: int = 16, device=None, metric: str = "psnr", **tiling_args) -> float:
+    """Mean score of ``model`` on inpainting over clean test pictures (``images[i]``: uint8 H x W x C, or float32 in
+    [0, 1] on the uint8 grid as TestImagesCSV yields them): restore.evaluate_inpaint on this rank's share -- a pixel
+    is known with probability ``inpaint_keep``, the missing ones are filled by ``fill`` (``fill_side``, ``fill_sigma``,
+    ``hole``, ``passes``), all on the device, the filled picture is restored, the known pixels are put back, ``shave``
+    pixels are cut from each side and the result is scored against the clean picture.  ``metric``: "psnr" (default),
+    "psnr_y", "ssim" or "psnr_missing" (the PSNR over the missing pixels alone).  The mask of a picture is a function
+    of (seed, its index in this rank's share); nothing is drawn on the host.  tiling_args: tile, halo, micro_batch,
+    ensemble.
+
+    Several ranks: sharded and all-reduced as validate_pairs does."""
+    from . import restore
+    return _validate_degraded("validate_inpaint", VAL_INPAINT_METRICS, restore.evaluate_inpaint, model, images, device,
+                              metric, keep=inpaint_keep, fill=fill, fill_side=fill_side, fill_sigma=fill_sigma, hole=hole,
+                              seed=seed, passes=passes, shave=shave, factor=factor, **tiling_args)
+
+
 VAL_DEBLUR_METRICS = ("psnr", "psnr_y", "ssim")
 
 
@@ -1707,6 +1845,29 @@ _VAL_RAW_NOISE = _ValProtocol("raw_noise", TestImagesCSV, _val_raw_noise, ("shav
                               {"bayer": BAYER_PATTERNS, "fill": BAYER_FILLS}, VAL_DEMOSAIC_METRICS, validate_jdd)
 
 
+def _val_keep(v) -> float:
+    """``datasets.val.inpaint_keep``: the known share, checked here so that a bad one is refused with the config."""
+    from . import kernels
+    try:
+        kernels.keep_units(v)
+    except ValueError:
+        raise ValueError(f"datasets.val.inpaint_keep is the known share of the pixels, a number of 0..1, got {v!r}") from None
+    return float(v)
+
+
+# Inpainting stands before every other row: a section with an ``inpaint_keep`` key is taken here, and a section without
+# one never sees this record
+_VAL_INPAINT = _ValProtocol("inpaint_keep", TestImagesCSV, _val_keep, ("shave", "fill_side", "hole", "passes", "seed"),
+                            {"fill": MASK_FILLS}, VAL_INPAINT_METRICS, validate_inpaint, ("fill_sigma",))
+
+
+def _val_rows() -> Iterator[_ValProtocol]:
+    """Every row a ``datasets.val`` section is matched against, in order of precedence: _VAL_INPAINT, then
+    _val_protocols' rows."""
+    yield _VAL_INPAINT
+    yield from _val_protocols()
+
+
 def _val_protocols() -> Iterator[_ValProtocol]:
     """The rows a ``datasets.val`` section is matched against, in order of precedence: _VAL_PROTOCOLS with
     _VAL_RAW_NOISE directly before the ``bayer`` row."""
@@ -1719,7 +1880,7 @@ def _val_protocols() -> Iterator[_ValProtocol]:
 def val_check(val_set, val_args: dict) -> Callable:
     """The validator of what create_val_dataset returned: ``val_check(val_set, val_args)(model, val_set, device=device,
     **val_args)`` is the validation run() makes."""
-    for p in _val_protocols():
+    for p in _val_rows():
         if (p.key in val_args) if p.key else isinstance(val_set, p.dataset):
             return p.validator
     return validate
@@ -1738,14 +1899,17 @@ def create_val_dataset(conf: dict):
     {type, dataset_args, raw_noise, bayer, fill, shave, bits, factor, tile, halo, micro_batch, metric}, validate_jdd's
     arguments; ``raw_noise`` takes precedence over ``bayer``.  TestImagesCSV with a ``blur`` key (a kernel spec string) is deblurring:
     {type, dataset_args, blur, boundary, noise_sigma, shave, factor, tile, halo, micro_batch, metric},
-    validate_deblur's arguments; the noise on the blurred picture is ``noise_sigma``, not ``sigma``."""
+    validate_deblur's arguments; the noise on the blurred picture is ``noise_sigma``, not ``sigma``.  TestImagesCSV with
+    an ``inpaint_keep`` key (the known share of 0..1) is inpainting and takes precedence over all of them:
+    {type, dataset_args, inpaint_keep, fill, fill_side, fill_sigma, hole, passes, seed, shave, factor, tile, halo,
+    micro_batch, metric}, validate_inpaint's arguments."""
     vconf = conf.get("datasets", {}).get("val")
     if not vconf:
         return None, {}
     cls = VAL_DATASETS.get(vconf["type"])
     if cls is None:
         raise ValueError(f"Validation dataset {vconf['type']} is not found.")
-    for p in _val_protocols():
+    for p in _val_rows():
         if cls is not p.dataset or (p.key is not None and vconf.get(p.key) is None):
             continue
         for k, allowed in p.choices.items():
@@ -1812,7 +1976,7 @@ class ResumeableSampler(Sampler):
 def create_dataset(dataset_conf: dict, environ_conf: dict):
     cls = DATASETS.get(dataset_conf["type"])
     if cls is None:
-        raise ValueError(f"Dataset {dataset_conf['type']} is not found.")
+        raise ValueError(f"Dataset {dataset_conf['type']} is not found (the datasets are {sorted(DATASETS)}).")
     return cls(**dataset_conf["dataset_args"])
 
 

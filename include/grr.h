@@ -1195,6 +1195,69 @@ grr_status grr_u8_blur_images(const uint8_t* arena, int64_t elems, const int64_t
                               int C, uint8_t* dst_arena, const int32_t* weights, const int32_t* sizes, int n_kernels,
                               const int32_t* kernel_of, int boundary, void* stream);
 
+/* ---- inpainting (csrc/inpaint_ops.hip): a random share of the pixels is missing and an initial fill stands in for
+ * them.  The mask must be fresh per sample and per epoch and lies under a spatial filter, so the degradation is made
+ * at batch time, inside the patch kernel: cut, mask, fill, turn, one launch.  No floating point appears in the
+ * definition.
+ *
+ * Per sample s: a table row (img, row, col, mode) and a sample id, as grr_patch_batch takes them; keep[s], an int32
+ *   on the device, clamped into [0, GRR_MASK_ONE]: the known share of the pixels in units of 2^-24.
+ * Call-wide: C in 1..4; fill 0 (zero) or 1 (conv); hole, a byte 0..255; a uint64 seed; a weight table w[kh][kw] of
+ *   uint8 on the device, row-major, kh and kw odd, in 1..GRR_MASK_MAX_SIDE.
+ * Window: (ph + 14) x (pw + 14), whatever the table's sides: the mask is a function of (seed, id, ph, pw) alone, never
+ *   of the fill.  Window position (wy, wx) has image coordinates Y = row + wy - 7, X = col + wx - 7 and reads picture
+ *   pixel (sym(Y, H), sym(X, W)), sym grr_patch_batch's edge-repeating mirror taken for any index (t = r mod 2n,
+ *   non-negative; t < n ? t : 2n - 1 - t) -- not the parity-keeping reflection of grr_patch_raw_batch: there is no
+ *   colour filter array here.  With every pixel known the outputs equal grr_patch_batch's clean patch bit for bit.
+ * Mask: one bit per pixel, shared by the channels.  With e = wy (pw + 14) + wx, block e / 4 is Philox4x32-10 of
+ *   counter (e / 4, 1, low32(id), high32(id)) and key (low32(seed), high32(seed)) -- the second counter word is 1
+ *   where the noise of grr_patch_batch has 0, so the two streams never share a block -- and the pixel is known if
+ *   (x_{e % 4} >> 8) < keep[s].  keep = 2^24 makes every pixel known and keep = 0 none;
+ *   in both cases no generator runs.  A mirrored position draws its own bit.
+ * Fill: a known pixel passes through, in every channel.  A missing pixel is, for the zero fill, 0 in every channel;
+ *   for conv, with ry = kh / 2, rx = kw / 2, k the known bit and v_c the byte of channel c,
+ *     den   = sum_{i<kh, j<kw} w[i][j] k(wy + i - ry, wx + j - rx)
+ *     num_c = sum_{i<kh, j<kw} w[i][j] k(wy + i - ry, wx + j - rx) v_c(wy + i - ry, wx + j - rx)
+ *   and the byte is (2 num_c + den) / (2 den), floor, when den > 0, otherwise hole.  num_c <= 255 den and
+ *   den <= 225 * 255, so int32 is exact and the result needs no clamp.  A normalised convolution; the taps stay
+ *   within radius 7, so the window's halo is all it reads: the fill itself has no border rule.
+ * Outputs: patch pixel (i, j) is window position (i + 7, j + 7), moved by T_mode exactly as grr_patch_batch moves it
+ *   (odd quarter turns need ph == pw; an illegal mode is read as mode & 5).  input and target: float32
+ *   [n, C, ph, pw], planar, each value float(byte) / 255.0f; mask: float32 [n, 1, ph, pw], 1.0 known and 0.0 missing,
+ *   turned the same way; mask == NULL skips it.  A sample does not depend on the batch it is in.
+ *
+ * arena, arena_elems, C, img_table, n_img, table, sample_ids: as grr_patch_batch takes them.  Every table value is
+ * clamped as in grr_patch_batch: a bad table gives wrong pixels, never an access outside the buffers.  No atomics;
+ * every output element is written once. */
+#define GRR_MASK_HALO 7
+#define GRR_MASK_MAX_SIDE 15
+#define GRR_MASK_ONE (1 << 24)
+
+/* 1 where grr_patch_mask_batch takes the call: grr_patch_batch_supported(C, n_img, arena_elems, n, ph, pw) and
+ * (ph + 14)(pw + 14) < 2^31. */
+int grr_patch_mask_batch_supported(int C, int n_img, int64_t arena_elems, int n, int ph, int pw);
+/* GRR_ERR_INVALID_ARG for C outside 1..4, an even or out-of-range side, a fill outside 0..1 or a hole outside 0..255,
+ * before any launch; GRR_ERR_UNSUPPORTED where the query says 0. */
+grr_status grr_patch_mask_batch(const uint8_t* arena, int64_t arena_elems, int C, const int64_t* img_table, int n_img,
+                                const int32_t* table, const int64_t* sample_ids, const int32_t* keep /* int32 [n] */,
+                                int n, uint64_t seed, int ph, int pw, const uint8_t* weights /* uint8 [kh kw] */, int kh,
+                                int kw, int fill, int hole, float* target, float* input, float* mask /* or NULL */,
+                                void* stream);
+/* 1 where grr_u8_mask_fill takes the picture: C in 1..4, H, W >= 1, C H W < 2^31 and (H + 14)(W + 14) < 2^31. */
+int grr_u8_mask_fill_supported(int C, int H, int W);
+/* One picture: the same kernel body with row = col = 0, ph = H, pw = W, mode 0 and no device tables.  src, dst: HWC
+ * uint8 at any byte address, distinct buffers.  mask_in == NULL: the mask of (seed, sample_id) is drawn with the
+ * share keep, the patch form's mask for the same id.  mask_in given (uint8 H x W): nonzero means known; outside the
+ * picture mask_in is read by sym, like the pixels; no generator runs.  mask_out (uint8 H x W) carries through
+ * mask_in's nonzero values, is 1 for known pixels when the mask is drawn,
+ * 2 where this call filled a pixel with den > 0 and 0 where a hole is left: feeding dst and mask_out back in as src and mask_in is a second pass, in which
+ * every nonzero is known and the 1s and 2s are kept, and which grows the filled region by one table radius.  The pass
+ * loop is the caller's: each pass is one launch with distinct buffers.  GRR_ERR_INVALID_ARG as above and for a keep
+ * outside [0, 2^24]. */
+grr_status grr_u8_mask_fill(const uint8_t* src, const uint8_t* mask_in /* uint8 H x W, or NULL */, int H, int W, int C,
+                            int keep, uint64_t seed, int64_t sample_id, const uint8_t* weights, int kh, int kw, int fill,
+                            int hole, uint8_t* dst /* uint8 HWC */, uint8_t* mask_out /* uint8 H x W */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,10 @@
             | --bayer PATTERN [--demosaic-fill FILL] [--shave N] [--ssim] [--y-channel]
               [--raw-noise SHOT,READ [--raw-bits N] [--raw-no-clip] [--raw-seed N]]
             | --raw PATTERN [--demosaic-fill FILL]
-            | --blur SPEC [--blur-boundary B] [--blur-noise S] [--shave N] [--ssim] [--y-channel]]
+            | --blur SPEC [--blur-boundary B] [--blur-noise S] [--shave N] [--ssim] [--y-channel]
+            | --inpaint-keep F [--mask-seed N] [--ssim] [--y-channel]]
+           [--mask MASK_DIR [--mask-white-missing] [--reference DIR]]
+           [--mask-fill zero|conv --mask-fill-side N --mask-fill-sigma S --mask-fill-passes P --no-keep-known]
            [--tile T --halo H --factor F] [--batch-images]
            [--self-ensemble | --ensemble-modes 0,1,4,5]
 
@@ -66,6 +69,17 @@ replicate or reflect), with --blur-noise S noise of N(0, S/255) is added to the 
 RandomState(--seed) in file order; the model's input is then float32 and is not quantised), the result is restored and
 scored against the input after --shave N border pixels (default 0) are cut from both.  --ssim and --y-channel apply as
 above; it works with --batch-images and the ensemble options.
+With --inpaint-keep F (0..1; not with the other scored modes) the inputs are clean files and the inpainting protocol
+runs on each: a pixel is known with probability F -- file i has sample id i under --mask-seed N (default 2204), so its
+mask does not depend on the other files -- the missing pixels are filled on the GPU (``irdu_amd.mask_fill_u8``:
+--mask-fill conv, the default, a normalised convolution of the known pixels under a flat --mask-fill-side N table (odd,
+at most 15, default 7) or a Gaussian of --mask-fill-sigma S, or zero; --mask-fill-passes P repeats the fill, each pass
+taking the filled pixels as known), the filled picture is restored, the known pixels are put back (unless
+--no-keep-known) and the result is scored against the input; each line also carries PSNR-missing, the PSNR over the
+missing pixels alone.  With --mask MASK_DIR the inputs are pictures with holes: the 1-channel file of the same stem and
+size in MASK_DIR says which pixels are known -- nonzero, or zero with --mask-white-missing -- the others are filled the
+same way, the picture is restored, the known pixels are put back and the result is written; with --reference DIR it is
+also scored.  Both work with --batch-images and the ensemble options.
 """
 import argparse
 import os
@@ -76,6 +90,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 PATTERNS = ("rggb", "grbg", "gbrg", "bggr")     # irdu_amd.kernels.DEMOSAIC_PATTERNS
 FILLS = ("zero", "bilinear", "malvar")          # irdu_amd.kernels.DEMOSAIC_FILLS
 BOUNDARIES = ("wrap", "replicate", "reflect")   # irdu_amd.kernels.BLUR_BOUNDARIES
+MASK_FILLS = ("zero", "conv")                   # irdu_amd.kernels.MASK_FILLS
 EXTENSIONS = (".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff", ".ppm", ".pgm", ".webp")
 
 
@@ -147,6 +162,25 @@ def parse_args(argv=None):
     scored.add_argument("--blur", type=str, default=None, metavar="SPEC",
                         help="inputs are clean: blur with this kernel (gaussian:SIDE:SIGMA, box:SIDE, motion:LENGTH:ANGLE, "
                              "file:PATH.npy) on the GPU, restore, report PSNR against the input")
+    scored.add_argument("--inpaint-keep", type=float, default=None, metavar="F",
+                        help="inputs are clean: keep each pixel with probability F (0..1), fill the others on the GPU, "
+                             "restore, report PSNR against the input")
+    ap.add_argument("--mask", type=str, default=None, metavar="MASK_DIR",
+                    help="inputs have holes: the 1-channel file of the same stem in MASK_DIR is nonzero where a pixel is "
+                         "known; fill the others, restore, put the known pixels back, write")
+    ap.add_argument("--mask-white-missing", action="store_true", help="with --mask: nonzero means missing")
+    ap.add_argument("--mask-fill", type=str, default=None, choices=MASK_FILLS,
+                    help="with --inpaint-keep or --mask: how the missing pixels are filled before the model (default conv)")
+    ap.add_argument("--mask-fill-side", type=int, default=None, metavar="N",
+                    help="with --mask-fill conv: the side of the weight table, odd, 1..15 (default 7)")
+    ap.add_argument("--mask-fill-sigma", type=float, default=None, metavar="S",
+                    help="with --mask-fill conv: a Gaussian table of this sigma (default: a flat table)")
+    ap.add_argument("--mask-fill-passes", type=int, default=None, metavar="P",
+                    help="with --inpaint-keep or --mask: fill P times, each pass taking the filled pixels as known "
+                         "(default 1)")
+    ap.add_argument("--mask-seed", type=int, default=None, metavar="N", help="with --inpaint-keep: the mask seed (default 2204)")
+    ap.add_argument("--no-keep-known", action="store_true",
+                    help="with --inpaint-keep or --mask: do not put the known pixels back into the restored picture")
     ap.add_argument("--blur-boundary", type=str, default=None, choices=BOUNDARIES,
                     help="with --blur: how the picture continues beyond its sides (default wrap)")
     ap.add_argument("--blur-noise", type=float, default=None, metavar="S",
@@ -186,7 +220,8 @@ def parse_args(argv=None):
                        help="average over these modes of 0..7 only, ascending (e.g. 0,1,4,5)")
     args = ap.parse_args(argv)
     args.scored = args.sigma is not None or args.reference is not None or args.scale is not None \
-        or args.jpeg_quality is not None or args.bayer is not None or args.blur is not None
+        or args.jpeg_quality is not None or args.bayer is not None or args.blur is not None \
+        or args.inpaint_keep is not None
     if args.ssim and not args.scored:
         ap.error("--ssim needs --sigma, --reference, --scale, --jpeg-quality, --bayer or --blur: there is nothing to compare a restored image with otherwise")
     if args.y_channel and not args.scored:
@@ -237,6 +272,39 @@ def parse_args(argv=None):
         args.shave = args.scale
     if (args.bayer is not None or args.blur is not None) and args.shave is None:
         args.shave = 0
+    if args.inpaint_keep is not None and not 0 <= args.inpaint_keep <= 1:
+        ap.error(f"--inpaint-keep: the known share is a number of 0..1, got {args.inpaint_keep}")
+    if args.mask is not None:
+        for flag, value in (("--sigma", args.sigma), ("--scale", args.scale), ("--upscale", args.upscale),
+                            ("--jpeg-quality", args.jpeg_quality), ("--bayer", args.bayer), ("--raw", args.raw),
+                            ("--blur", args.blur), ("--inpaint-keep", args.inpaint_keep)):
+            if value is not None:
+                ap.error(f"--mask: not allowed with {flag}")
+    args.inpaint = args.inpaint_keep is not None or args.mask is not None
+    for flag, value in (("--mask-fill", args.mask_fill), ("--mask-fill-side", args.mask_fill_side),
+                        ("--mask-fill-sigma", args.mask_fill_sigma), ("--mask-fill-passes", args.mask_fill_passes),
+                        ("--no-keep-known", args.no_keep_known or None)):
+        if value is not None and not args.inpaint:
+            ap.error(f"{flag} needs --inpaint-keep or --mask")
+    if args.mask_white_missing and args.mask is None:
+        ap.error("--mask-white-missing needs --mask")
+    if args.mask_seed is not None and args.inpaint_keep is None:
+        ap.error("--mask-seed needs --inpaint-keep")
+    if args.mask_seed is not None and not 0 <= args.mask_seed < 2 ** 64:
+        ap.error(f"--mask-seed: the seed is an integer of 0..2^64 - 1, got {args.mask_seed}")
+    args.mask_fill = args.mask_fill or "conv"
+    for flag, value in (("--mask-fill-side", args.mask_fill_side), ("--mask-fill-sigma", args.mask_fill_sigma)):
+        if value is not None and args.mask_fill != "conv":
+            ap.error(f"{flag} needs --mask-fill conv")
+    if args.mask_fill_side is not None and not (1 <= args.mask_fill_side <= 15 and args.mask_fill_side % 2 == 1):
+        ap.error(f"--mask-fill-side: the side is an odd integer of 1..15, got {args.mask_fill_side}")
+    if args.mask_fill_sigma is not None and not 0 < args.mask_fill_sigma < float("inf"):
+        ap.error(f"--mask-fill-sigma: sigma is a positive number, got {args.mask_fill_sigma}")
+    if args.mask_fill_passes is not None and args.mask_fill_passes < 1:
+        ap.error(f"--mask-fill-passes: the number of passes is a positive integer, got {args.mask_fill_passes}")
+    args.mask_fill_side = 7 if args.mask_fill_side is None else args.mask_fill_side
+    args.mask_fill_passes = 1 if args.mask_fill_passes is None else args.mask_fill_passes
+    args.mask_seed = 2204 if args.mask_seed is None else args.mask_seed
     args.ensemble = 8 if args.self_ensemble else 1
     if args.ensemble_modes is not None:
         try:
@@ -266,6 +334,19 @@ def main(argv=None) -> None:
         found = reference_files(files, args.reference)
         check_references(files, found)
         refs = dict(zip(files, found))
+    masks = {}
+    if args.mask is not None:
+        if not os.path.isdir(args.mask):
+            raise SystemExit(f"--mask: {args.mask} is not a directory")
+        try:
+            masks = dict(zip(files, reference_files(files, args.mask)))
+        except SystemExit as e:
+            raise SystemExit(str(e).replace("--reference", "--mask").replace("reference(s)", "mask(s)"))
+        for path, mask_path in masks.items():
+            with Image.open(path) as a, Image.open(mask_path) as b:
+                if a.size != b.size or len(b.getbands()) != 1:
+                    raise SystemExit(f"--mask: {mask_path} is {b.size[1]}x{b.size[0]}x{len(b.getbands())}, its input {path} "
+                                     f"is {a.size[1]}x{a.size[0]}; a mask is a 1-channel file of the input's size")
     conf = training.parse_options(args.yaml_path)
 
     def need_three_channels(flag, model_needs, bands, files_need):
@@ -317,7 +398,7 @@ def main(argv=None) -> None:
     halo = restore.HALO if args.halo is None else args.halo
     os.makedirs(args.output, exist_ok=True)
     rs = np.random.RandomState(seed=args.seed)
-    psnrs, ssims, psnrbs = [], [], []
+    psnrs, ssims, psnrbs, missing = [], [], [], []
     psnr_of, ssim_of, tag = ((irdu_amd.psnr_y_u8, irdu_amd.ssim_y_u8, "-Y") if args.y_channel else
                              (irdu_amd.psnr_u8, irdu_amd.ssim_u8, ""))
 
@@ -341,9 +422,24 @@ def main(argv=None) -> None:
             img = irdu_amd.demosaic_u8(img, args.raw, args.demosaic_fill)
         return img
 
-    def input_of(img):
+    known_of = {}       # inpainting: the 0 / 1 plane of the known pixels of each file
+    mask_table = irdu_amd.kernels.mask_weights(args.mask_fill_side, args.mask_fill_sigma) if args.inpaint else None
+
+    def input_of(img, path):
         if args.sigma is not None:
             return noisy_of(img)
+        if args.inpaint:
+            given = None
+            if args.mask is not None:
+                given = np.array(Image.open(masks[path]))
+                given = (given == 0) if args.mask_white_missing else (given != 0)
+            try:
+                filled, known_of[path] = irdu_amd.mask_fill_u8(
+                    img, mask=given, keep=args.inpaint_keep, fill=args.mask_fill, weights=mask_table,
+                    seed=args.mask_seed, sample_id=files.index(path), passes=args.mask_fill_passes)
+            except ValueError as e:
+                raise SystemExit(f"{path}: {e}")
+            return filled
         if protocol is None:
             return img
         try:
@@ -358,6 +454,8 @@ def main(argv=None) -> None:
 
     def finish(path, img, out):
         out_path = os.path.join(args.output, os.path.splitext(os.path.basename(path))[0] + ".png")
+        if path in known_of and not args.no_keep_known and out.shape == img.shape:
+            out = np.where(known_of[path][:, :, None] != 0, img, out)
         if not args.scored:
             print(f"{path} -> {out_path}  {img.shape[0]}x{img.shape[1]}x{img.shape[2]}")
         else:
@@ -374,6 +472,8 @@ def main(argv=None) -> None:
             except ValueError as e:
                 raise SystemExit(f"{path}: {e}")
             against = (protocol.label if protocol is not None else
+                       f"inpaint keep {args.inpaint_keep:g} {args.mask_fill} seed {args.mask_seed}"
+                       if args.inpaint_keep is not None else
                        f"sigma {args.sigma:g}" if args.reference is None else f"reference {refs[path]}")
             line = f"{path} -> {out_path}  {against}  PSNR{tag} {psnrs[-1]:.4f} dB"
             if args.ssim:
@@ -382,6 +482,9 @@ def main(argv=None) -> None:
                 except ValueError as e:
                     raise SystemExit(f"{path}: {e}")
                 line += f"  SSIM{tag} {ssims[-1]:.4f}"
+            if path in known_of:
+                missing.append(irdu_amd.psnr_missing_u8(scored, truth, known_of[path]))
+                line += f"  PSNR-missing {missing[-1]:.4f} dB"
             if args.psnrb:
                 try:
                     psnrbs.append(irdu_amd.psnrb_u8(scored, truth))
@@ -393,7 +496,7 @@ def main(argv=None) -> None:
 
     if args.batch_images:
         imgs = [read(path) for path in files]
-        inputs = [input_of(img) for img in imgs]                                       # draws in file order
+        inputs = [input_of(img, path) for img, path in zip(imgs, files)]               # draws in file order
         try:
             outs = irdu_amd.restore_images(model, inputs, factor=args.factor, tile=tile, halo=halo, ensemble=ensemble)
         except ValueError as e:
@@ -403,13 +506,15 @@ def main(argv=None) -> None:
     else:
         for path in files:
             img = read(path)
-            out = irdu_amd.restore_image(model, input_of(img), factor=args.factor,
+            out = irdu_amd.restore_image(model, input_of(img, path), factor=args.factor,
                                          tile=tile, halo=halo, ensemble=ensemble)
             finish(path, img, out)
     if psnrs:
         print(f"mean PSNR{tag} over {len(psnrs)} image(s): {float(np.mean(psnrs)):.4f} dB")
     if ssims:
         print(f"mean SSIM{tag} over {len(ssims)} image(s): {float(np.mean(ssims)):.4f}")
+    if missing:
+        print(f"mean PSNR-missing over {len(missing)} image(s): {float(np.mean(missing)):.4f} dB")
     if psnrbs:
         print(f"mean PSNR-B over {len(psnrbs)} image(s): {float(np.mean(psnrbs)):.4f} dB")
 
