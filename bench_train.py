@@ -2,7 +2,7 @@
 gradient all-reduce when launched with torchrun), on synthetic sigma=25 patches resident in HBM.
 
     python bench_train.py [--model abstract|msgf] [--size 256] [--batch 8] [--stages 10]
-                          [--steps 5] [--warmup 2] [--breakdown]
+                          [--steps 5] [--warmup 2] [--ssim-weight 0] [--breakdown]
 
 Not the headline metric (bench.py is); prints one JSON line with training MPix/s (input
 pixels of the optimisation step per second, whole job) and the per-kernel-kind time of the
@@ -139,6 +139,8 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--aux-losses", action="store_true", help="add the enc-dec / latent-perturbation losses")
+    ap.add_argument("--ssim-weight", type=float, default=0.0,
+                    help="train.ssim_weight: add W (1 - SSIM) on the HIP loss kernels to the L1 term (0: never called)")
     ap.add_argument("--breakdown", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-size", type=int, default=None,
@@ -202,7 +204,10 @@ def main():
         model = irdu_amd.MultiScaleGraphFilter(3, 3, ngraphs=32, n_cgd_iters=args.stages)
         desc = "MultiScaleGraphFilter G=32 F=3 (v13 feature CNN)"
     w = 0.1 if args.aux_losses else 0.0
-    tr = T.Trainer(model, {"loss02_weight": w, "loss03_weight": 5 * w}, dev)
+    tconf = {"loss02_weight": w, "loss03_weight": 5 * w}
+    if args.ssim_weight:
+        tconf["ssim_weight"] = args.ssim_weight
+    tr = T.Trainer(model, tconf, dev)
     clean, noisy = synthetic_patches(args.batch, seed=2204 + rank, h=args.size, w=args.size)
     noisy_hwc = noisy.permute(0, 2, 3, 1).contiguous().to(dev)
     clean_hwc = clean.permute(0, 2, 3, 1).contiguous().to(dev)
@@ -238,6 +243,8 @@ def main():
                "loss": loss, "hip_kernel_ms_per_step": round(hip_ms, 2),
                "peak_mem_gb": round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 1),
                "kernel_ms_per_step": {k: round(v["total_ms"] / args.steps, 3) for k, v in kern.items()}}
+        if args.ssim_weight:
+            res["config"]["ssim_weight"] = args.ssim_weight
         if world > 1:
             res.update(ranks)
         res["roofline"] = reverse_roofline(kern, args.model, args.batch, args.size)

@@ -60,5 +60,7 @@ from .training import parse_blur_spec, quantise_blur_kernel  # noqa: F401
 from .restore import blur_u8, evaluate_deblur  # noqa: F401
 from .training import RandomMaskInpainting  # noqa: F401  (inpainting pairs: a drawn mask and its fill, per batch)
 from .restore import evaluate_inpaint, mask_fill_u8, psnr_missing_u8  # noqa: F401
+from . import losses  # noqa: F401  (training losses on the HIP kernels)
+from .losses import SSIMLoss, ssim_loss, ssim_loss_sums  # noqa: F401  (1 - SSIM, forward and reverse in float64)
 
 __version__ = "0.1.0"

@@ -185,6 +185,10 @@ SIGNATURES = {
     "grr_u8_luma_sse_images": [P, P, L, P, I, P, P],
     "grr_u8_luma_ssim": [P, P, I, I, P, P],
     "grr_u8_luma_ssim_images": [P, P, L, P, I, I, I, P, P],
+    # the SSIM training loss on float32 planar batches, forward and reverse (ssim_loss_ops.hip)
+    "grr_ssim_loss_supported": [I, I, I, I],
+    "grr_ssim_loss_forward": [P, P, I, I, I, I, P, P, P],
+    "grr_ssim_loss_backward": [P, P, P, P, P, I, I, I, I, P],
     # training batches from an image arena (training.DevicePatchLoader)
     "grr_patch_batch_supported": [I, I, L, I, I, I],
     "grr_patch_batch": [P, L, I, P, I, P, P, P, I, ctypes.c_uint64, I, I, P, P, P],

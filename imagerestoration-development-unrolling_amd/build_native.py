@@ -19,7 +19,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgrr.so")
-SOURCES = ["graph_ops.hip", "feature_ops.hip", "lnb_ops.hip", "graph_bwd.hip", "lnb_bwd.hip", "window_ops.hip", "window_bwd.hip", "subapi_ops.hip", "subapi_bwd.hip", "wgrad_ops.hip", "feature_edge.hip", "codec_ops.hip", "image_ops.hip", "metric_ops.hip", "resize_ops.hip", "jpeg_ops.hip", "demosaic_ops.hip", "rawnoise_ops.hip", "blur_ops.hip", "inpaint_ops.hip", "runtime.hip"]
+SOURCES = ["graph_ops.hip", "feature_ops.hip", "lnb_ops.hip", "graph_bwd.hip", "lnb_bwd.hip", "window_ops.hip", "window_bwd.hip", "subapi_ops.hip", "subapi_bwd.hip", "wgrad_ops.hip", "feature_edge.hip", "codec_ops.hip", "image_ops.hip", "metric_ops.hip", "resize_ops.hip", "jpeg_ops.hip", "demosaic_ops.hip", "rawnoise_ops.hip", "blur_ops.hip", "inpaint_ops.hip", "ssim_loss_ops.hip", "runtime.hip"]
 # every header of csrc/ (a new one can never go stale unnoticed) and the public ABI
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(ROOT, "include", "grr.h")]
 ARCH = "gfx950"

@@ -2410,6 +2410,83 @@ def u8_luma_ssim_images(a_pack, b_pack) -> List[int]:
 
 
 # ---------------------------------------------------------------------------
+# The SSIM training loss on float32 planar batches (csrc/ssim_loss_ops.hip; include/grr.h has the definition): the
+# index above on [B, C, H, W] planes of data range 1, x the prediction and y the target.  The forward returns the
+# exact integer sum q per batch item and, on request, the float64 coefficient planes [3, B, C, H - 10, W - 10] the
+# reverse gathers the gradient from (losses.py wraps the two for autograd).
+SSIM_LOSS_TILE = (32, 256)        # a workgroup's rows and columns: valid positions (forward), pixels (reverse)
+MAX_SSIM_LOSS_PLANES = 65535      # B C: one grid row per plane
+
+
+def ssim_loss_ok(b: int, c: int, h: int, w: int) -> bool:
+    """grr_ssim_loss_supported in plain Python (tests/test_ssim_loss_abi.py checks the two agree): B, C >= 1, both
+    sides at least 11, B C <= 65535, B C H W < 2^31."""
+    return (b >= 1 and c >= 1 and h >= SSIM_WINDOW and w >= SSIM_WINDOW and b * c <= MAX_SSIM_LOSS_PLANES
+            and b * c * h * w < (1 << 31))
+
+
+def ssim_loss_count(b: int, c: int, h: int, w: int) -> int:
+    """N: the values the loss is one minus the mean of."""
+    return b * c * (h - SSIM_WINDOW + 1) * (w - SSIM_WINDOW + 1)
+
+
+def _check_ssim_loss(name: str, x: Tensor, y: Tensor, placed: bool = True) -> Tuple[int, int, int, int]:
+    """(B, C, H, W) of a prediction / target pair the loss takes; placed: they must also be on one GPU."""
+    for t in (x, y):
+        if not isinstance(t, Tensor) or t.dim() != 4:
+            raise ValueError(f"{name}: expected [B, C, H, W] tensors, got {tuple(getattr(t, 'shape', ()))}")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name}: expected float32, got {t.dtype}")
+    if x.shape != y.shape:
+        raise ValueError(f"{name}: shapes {tuple(x.shape)} / {tuple(y.shape)} must match")
+    b, c, h, w = x.shape
+    if min(h, w) < SSIM_WINDOW:
+        raise ValueError(f"{name}: both sides must be at least {SSIM_WINDOW}, the window's (got {h} x {w})")
+    if not ssim_loss_ok(b, c, h, w):
+        raise ValueError(f"{name}: needs B C <= {MAX_SSIM_LOSS_PLANES} and below 2^31 elements (got {tuple(x.shape)})")
+    if not (x.is_contiguous() and y.is_contiguous()):
+        raise ValueError(f"{name}: expected contiguous tensors")
+    if placed and not (x.is_cuda and y.is_cuda and x.device == y.device):
+        raise RuntimeError(f"{name}: tensors must be on one GPU; the HIP engine has no CPU path")
+    return b, c, h, w
+
+
+def ssim_loss_forward(x: Tensor, y: Tensor, want_coef: bool) -> Tuple[Tensor, Optional[Tensor]]:
+    """(qsum, coef): qsum int64 [B] on the device, the exact sum of rint(2^32 s) over each item's positions (no
+    synchronisation); coef the float64 planes [3, B, C, H - 10, W - 10] of ds/dmx, ds/dE[x^2], ds/dE[xy], or None
+    (nothing allocated or written) unless want_coef."""
+    b, c, h, w = _check_ssim_loss("ssim_loss_forward", x, y)
+    n = ssim_loss_count(b, c, h, w)
+    qsum = torch.empty(b, dtype=torch.int64, device=x.device)
+    coef = torch.empty((3, b, c, h - SSIM_WINDOW + 1, w - SSIM_WINDOW + 1), dtype=torch.float64,
+                       device=x.device) if want_coef else None
+    _launch("ssim_loss_forward", 8 * x.numel() + 8 * b + (24 * n if want_coef else 0), "grr_ssim_loss_forward",
+            x.data_ptr(), y.data_ptr(), b, c, h, w, qsum.data_ptr(), _ptr(coef), _stream(x.device),
+            flops=_ssim_flops(n) + (30 + (20 if want_coef else 0)) * n)
+    return qsum, coef
+
+
+def ssim_loss_backward(x: Tensor, y: Tensor, coef: Tensor, gout: Tensor) -> Tensor:
+    """gx = gout dloss/dx, float32 like x, from the forward's coefficient planes; gout: one float32 on the device,
+    read by the kernel."""
+    b, c, h, w = _check_ssim_loss("ssim_loss_backward", x, y, placed=False)
+    shape = (3, b, c, h - SSIM_WINDOW + 1, w - SSIM_WINDOW + 1)
+    if not isinstance(coef, Tensor) or coef.dtype != torch.float64 or tuple(coef.shape) != shape or not coef.is_contiguous():
+        raise ValueError(f"ssim_loss_backward: coef must be the forward's contiguous float64 {shape} planes, got "
+                         f"{tuple(getattr(coef, 'shape', ()))} {getattr(coef, 'dtype', type(coef))}")
+    if not isinstance(gout, Tensor) or gout.dtype != torch.float32 or gout.numel() != 1:
+        raise ValueError("ssim_loss_backward: gout must be one float32 value, got "
+                         f"{tuple(getattr(gout, 'shape', ()))} {getattr(gout, 'dtype', type(gout))}")
+    if not (x.is_cuda and all(t.device == x.device for t in (y, coef, gout))):
+        raise RuntimeError("ssim_loss_backward: tensors must be on one GPU; the HIP engine has no CPU path")
+    gx = torch.empty_like(x)
+    _launch("ssim_loss_backward", 12 * x.numel() + 8 * coef.numel() + 4, "grr_ssim_loss_backward", x.data_ptr(),
+            y.data_ptr(), coef.data_ptr(), gout.data_ptr(), gx.data_ptr(), b, c, h, w, _stream(x.device),
+            flops=(2 * 66 + 8) * x.numel())
+    return gx
+
+
+# ---------------------------------------------------------------------------
 # Exact bicubic resize of uint8 images by an integer scale (csrc/resize_ops.hip; include/grr.h has the definition):
 # MATLAB imresize's convention with fixed-point weights, every tap set summing to 2^30.  The tap sets are computed
 # here from exact rationals and handed to the library as host arrays, as the mode lists above are.

@@ -64,7 +64,7 @@ import torch.nn as nn
 import yaml
 from torch.utils.data import Dataset, Sampler
 
-from . import sharding, stream_guard
+from . import losses, sharding, stream_guard
 
 LOG = logging.getLogger("irdu_amd.train")
 
@@ -2075,6 +2075,11 @@ class Trainer:
         self.w_perturb = float(tconf.get("loss03_weight", 0.5))
         self.latent_noise = float(tconf.get("latent_noise", 0.05))
         self.bucket_mb = float(tconf.get("allreduce_bucket_mb", 32.0))
+        # train.ssim_weight w > 0: the loss gains w (1 - SSIM(out, clean)) on the HIP kernels (losses.ssim_loss);
+        # 0 or absent: the op is never called
+        self.w_ssim = float(tconf.get("ssim_weight", 0.0) or 0.0)
+        if not (math.isfinite(self.w_ssim) and self.w_ssim >= 0.0):
+            raise ValueError(f"train.ssim_weight must be a finite number >= 0 (got {tconf.get('ssim_weight')!r})")
         # train.native_convs: the v1.0 model's plain convolutions on libgrr (graph_filter.NATIVE_CONVS); absent:
         # the process-wide switch (GRR_NATIVE_CONVS, default off) is left as it is
         if tconf.get("native_convs") is not None:
@@ -2097,6 +2102,8 @@ class Trainer:
         if _out is not None:
             _out.append(out)
         loss = nn.functional.l1_loss(out, clean)
+        if self.w_ssim:
+            loss = loss + self.w_ssim * losses.ssim_loss(out, clean)
         if hasattr(m, "encode") and (self.w_encdec or self.w_perturb):
             latent = m.encode(clean)
             rec = m.decode(latent)

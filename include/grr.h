@@ -863,6 +863,36 @@ grr_status grr_u8_luma_ssim(const uint8_t* a, const uint8_t* b, int H, int W, in
 grr_status grr_u8_luma_ssim_images(const uint8_t* a, const uint8_t* b, int64_t arena_elems, const int64_t* img_table,
                                    int n_img, int max_h, int max_w, int64_t* out, void* stream);
 
+/* ---- the SSIM training loss on float32 planar batches (csrc/ssim_loss_ops.hip): the index of the uint8 section
+ * above -- the same taps, order of operations, valid positions and quantisation -- on planes of data range 1, so
+ * C1 = 1e-4 and C2 = 9e-4.  x is the prediction, y the target, both contiguous float32 [B, C, H, W]; neither is
+ * clamped, |s| <= 1 for any real input.  s is defined at N = B C (H - 10)(W - 10) positions and
+ * loss = 1 - (sum s) / N.  With A1 = 2 mx my + C1, A2 = 2 vxy + C2, B1 = mx^2 + my^2 + C1, B2 = vx + vy + C2:
+ *   c0 = ds/dmx = 2 my (A2 - A1) / (B1 B2) - 2 mx s / B1 + 2 mx s / B2,  c1 = ds/dE[x^2] = -s / B2,
+ *   c2 = ds/dE[xy] = 2 A1 / (B1 B2),
+ *   dloss/dx = -(1 / N) (F*(c0) + 2 x F*(c1) + y F*(c2)),
+ * F* the window's adjoint: the full 2-D correlation of a (H - 10) x (W - 10) plane back to H x W, zero outside.  The
+ * three terms cancel at the 1 / C2 scale where x is close to y, so c0, c1, c2 are float64 planes and the gradient is
+ * float64 up to its one rounding to float32.  The target takes no gradient.  Base pointers at any 4-byte aligned
+ * address, 8-byte for the int64 and float64 buffers. */
+
+/* 1 where the loss takes the batch: B, C >= 1, H, W >= 11, B C <= 65535 (one grid row per plane) and
+ * B C H W < 2^31. */
+int grr_ssim_loss_supported(int B, int C, int H, int W);
+/* qsum[b] = the sum of q = rint(2^32 s) over the C (H - 10)(W - 10) positions of batch item b, exact, the same on
+ * every run and independent of the grid; loss = 1 - (sum over b of qsum[b]) / (2^32 N), within 2^-32 of the float64
+ * value; equal x and y give exactly C (H - 10)(W - 10) 2^32 per item.  qsum: B int64 on the device, overwritten.
+ * coef: float64 [3, B, C, H - 10, W - 10] on the device, overwritten with c0, c1, c2, or NULL where no gradient is
+ * wanted (nothing is written then).  GRR_ERR_UNSUPPORTED where grr_ssim_loss_supported is 0. */
+grr_status grr_ssim_loss_forward(const float* x, const float* y, int B, int C, int H, int W, int64_t* qsum, double* coef,
+                                 void* stream);
+/* gx = gout[0] dloss/dx from the forward's coef: float32 [B, C, H, W], every element overwritten, each formed in
+ * float64 in one fixed order (a gather: no atomics, the same bits on every run) and rounded once.  gout: one float32
+ * on the device, the incoming gradient of the loss, read by the kernel (no host synchronisation).
+ * GRR_ERR_UNSUPPORTED where grr_ssim_loss_supported is 0. */
+grr_status grr_ssim_loss_backward(const float* x, const float* y, const double* coef, const float* gout, float* gx,
+                                  int B, int C, int H, int W, void* stream);
+
 /* ---- training batches cut from an arena of uint8 images (training.DevicePatchLoader; the reference's
  * lib/dataloader_v2.py:ImageSuperResolution does this per sample on the host).  arena, arena_elems, C, img_table,
  * n_img: as grr_tiles_gather takes them, uint8 only.  table: int32 [n, 4] on the device, rows (img, row, col,
